@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: fused MacCormack step on the 4096 x 4096 fp64 journal-bearing grid.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one full MacCormack time step (both stages, averaging, ghost cells, per-step
 scalars and the device-side dt/residual update) of BASELINE.json configs[2]: 2-D journal bearing,
@@ -12,7 +12,12 @@ For N > 1 one rank runs per GPU -- under the driver's torch.distributed.run, or 
 process when it is called as plain `python bench.py --gpus N`; the grid is cut into N x-slabs (strong scaling: the 4096^2
 problem is fixed) with one all-gather per step over RCCL (2 halo rows + a 64-byte record per rank).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times exactly K steps once and prints the line (`value`, `ms_per_step` of those K steps).
+--dump-outputs DIR then writes what the timed path holds after its last step (dump_outputs) as DIR/<name>.npy.
+
+With --full the line carries the extra objects below, the timed region is repeated GPF_BENCH_REPEATS (5) times on the running
+problem (`value` / `ms_per_step` are the median's, `spread` the rest) and the variants and CPU baselines are timed as well
+(--no-cpu / --no-variants / --no-gp / --cfg1 select among them):
   roofline     -- dominant kernel (k_step2, the fused step in one launch): bytes COMPULSORY for this workload per launch
                   (48 B x cells: the journal gap varies along x only, so the topography is one triple per row;
                   `frac_survey_8d` prices the same launch at SURVEY.md 8(d)'s 72 B) / its mean launch duration from
@@ -111,9 +116,31 @@ REPEATS = int(os.environ.get('GPF_BENCH_REPEATS', 5))
 PLAN_NOTES = []            # gpf_plan_note of every problem time_problem has run, in order
 
 
-def time_problem(text, steps, warmup):
-    """(wall seconds of `steps` steps: the median of REPEATS timed regions, k_step ms per launch, all kernels ms per step,
-    the walls of all repeats) for one YAML input."""
+DUMP_SAMPLE = 1 << 20       # cells of q written by --dump-outputs (3 x 8 MiB in fp64; the whole 4096^2 field is 400 MB)
+DUMP_SEED = 123
+
+
+def dump_outputs(prob, outdir):
+    """What a caller of the timed path holds after its last step, as outdir/<name>.npy (fp64): `q_sample` = the field q
+    (3, Nx+2, Ny+2: rho, jx, jy with ghost cells) at DUMP_SAMPLE cells drawn with a fixed seed, `q_sample_index` = their flat
+    indices in one (Nx+2, Ny+2) plane, and the run's scalars (step, simtime, dt, ekin, ...) one file each."""
+    import numpy as np
+    from gapflow_amd import _lib
+    os.makedirs(outdir, exist_ok=True)
+    q = prob._download(_lib.FIELD_Q, 3)         # the timed loop calls gpf_step itself: prob.q's host mirror is not refreshed
+    plane = q[0].size
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(plane, size=min(DUMP_SAMPLE, plane), replace=False))
+    np.save(os.path.join(outdir, 'q_sample.npy'), np.ascontiguousarray(q.reshape(3, plane)[:, idx]))
+    np.save(os.path.join(outdir, 'q_sample_index.npy'), idx.astype(np.float64))
+    sc = prob._scalars()
+    for name in ('step', 'simtime', 'dt', 'ekin', 'ekin_old', 'residual', 'v_max', 'v_sound', 'mass'):
+        np.save(os.path.join(outdir, f'{name}.npy'), np.array([getattr(sc, name)], dtype=np.float64))
+
+
+def time_problem(text, steps, warmup, repeats=1, kernel_timing=False, dump_dir=None):
+    """(wall seconds of `steps` steps: the median of `repeats` timed regions, k_step ms per launch and all kernels ms per step
+    (None without `kernel_timing`), the walls of all repeats) for one YAML input.  `dump_dir`: dump_outputs after the last
+    timed step."""
     import ctypes as C
     import statistics
     from gapflow_amd import Problem, _lib
@@ -123,11 +150,11 @@ def time_problem(text, steps, warmup):
         lib = prob._lib
         if warmup > 0:
             prob._advance(warmup, honor_stop=False)
-        # --- timed region: EXACTLY K steps enqueued back to back, one host sync at the end; repeated REPEATS times on the running
-        #     problem (the boxes of the pool and the clocks within a call vary: one region of a few ms is one sample) ---
+        # --- timed region: EXACTLY K steps enqueued back to back, one host sync at the end; with --full repeated REPEATS times on
+        #     the running problem (the boxes of the pool and the clocks within a call vary: one region of a few ms is one sample) ---
         nexec = C.c_int64(0)
         walls = []
-        for rep in range(max(1, REPEATS)):
+        for rep in range(max(1, repeats)):
             _lib.check(lib.gpf_scalars(prob._h, C.byref(_lib.GpfScalars())))      # drains the stream
             t0 = time.perf_counter()
             done = 0
@@ -138,15 +165,20 @@ def time_problem(text, steps, warmup):
             walls.append(time.perf_counter() - t0)
             assert int(nexec.value) == warmup + (rep + 1) * steps, "steps were skipped inside the timed region"
         t0, t1 = 0.0, statistics.median(walls)
-        # --- kernel time of the dominant kernel, HIP events on the launch stream ---
-        kt, tt = C.c_double(0), C.c_double(0)
-        nk = min(max(steps, 1), 200)
-        _lib.check(lib.gpf_step_timed(prob._h, nk, C.byref(kt), C.byref(tt)))
+        if dump_dir is not None:
+            dump_outputs(prob, dump_dir)
+        kernel_ms = all_ms = None
+        if kernel_timing:
+            # --- kernel time of the dominant kernel, HIP events on the launch stream ---
+            kt, tt = C.c_double(0), C.c_double(0)
+            nk = min(max(steps, 1), 200)
+            _lib.check(lib.gpf_step_timed(prob._h, nk, C.byref(kt), C.byref(tt)))
+            kernel_ms, all_ms = kt.value / nk, tt.value / nk
         sc = prob._scalars()
         assert sc.invalid == 0 and sc.ekin == sc.ekin, "state went invalid during the benchmark"
         PLAN_NOTES.append(lib.gpf_plan_note(prob._h).decode())
         del prob
-    return t1 - t0, kt.value / nk, tt.value / nk, walls
+    return t1 - t0, kernel_ms, all_ms, walls
 
 
 def stream_ceiling(planes_in, planes_out, cells):
@@ -175,8 +207,20 @@ def roofline(kernel_ms, cells, bytes_per_cell, traffic_kind, kernel):
 
 
 def run_single(args):
-    wall, kernel_ms, all_ms, walls = time_problem(WORKLOAD_YAML.format(N=N_GRID), args.steps, args.warmup)
+    full = dict(repeats=REPEATS, kernel_timing=True) if args.full else {}
+    wall, kernel_ms, all_ms, walls = time_problem(WORKLOAD_YAML.format(N=N_GRID), args.steps, args.warmup,
+                                                  dump_dir=args.dump_outputs, **full)
     cells = N_GRID * N_GRID
+    out = {
+        "metric": "Mcell-updates/s (fp64), 4096^2 grid", "value": cells * args.steps / wall / 1e6,
+        "unit": "Mcell-updates/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"2D journal bearing {N_GRID}x{N_GRID}, fixed DH EOS, all-periodic, adaptive CFL 0.5 "
+                               "(BASELINE.json configs[2])", "slabs": 1},
+    }
+    if not args.full:
+        return out
 
     def spread(ws):
         ms = sorted(w / args.steps * 1e3 for w in ws)
@@ -192,22 +236,14 @@ def run_single(args):
     roof["plan"] = PLAN_NOTES[-1]
     roof["note"] = ("x-only gap: 48 B per cell-update are compulsory (q read + q write), the topography is one triple per row; "
                     "frac_survey_8d prices the same launch at SURVEY.md 8(d)'s 72 B, which this workload does not move")
-    out = {
-        "metric": "Mcell-updates/s (fp64), 4096^2 grid", "value": cells * args.steps / wall / 1e6,
-        "unit": "Mcell-updates/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"2D journal bearing {N_GRID}x{N_GRID}, fixed DH EOS, all-periodic, adaptive CFL 0.5 "
-                               "(BASELINE.json configs[2])", "slabs": 1},
-        "roofline": roof, "spread": spread(walls),
-    }
+    out["roofline"], out["spread"] = roof, spread(walls)
     if not args.no_variants:
         # the journal gap is y-invariant, so also time a gap that varies in both directions with a
         # cross flow (all three topography planes are read: the full 72 B per cell-update are compulsory there)
         text = WORKLOAD_YAML.format(N=N_GRID).replace("type: journal\n    CR: 1.e-2\n    eps: 0.7\n    U: 0.1\n    V: 0.",
                                                       "type: asperity\n    hmin: 2.e-6\n    hmax: 1.e-5\n    num: 1\n    U: 0.1\n    V: 0.05")
         assert 'asperity' in text
-        w2, k2, a2, walls2 = time_problem(text, args.steps, args.warmup)
+        w2, k2, a2, walls2 = time_problem(text, args.steps, args.warmup, **full)
         r2 = roofline(k2, cells, BYTES_PER_CELL, 'planes', "k_step2<DH, topography planes>")
         r2["all_kernels_ms_per_step"] = a2
         r2["plan"] = PLAN_NOTES[-1]
@@ -221,7 +257,7 @@ def run_single(args):
         # run -- rocprofv3 --stats, the PMC means -- would then mix the two sizes)
         n3 = max(args.steps, 100)
         if args.cfg1:
-            w3, k3, a3, walls3 = time_problem(SLIDER_1024_YAML, n3, args.warmup)
+            w3, k3, a3, walls3 = time_problem(SLIDER_1024_YAML, n3, args.warmup, **full)
             out["variants"]["slider_1024x1024"] = {
                 "workload": "2D inclined slider 1024x1024, fixed DH EOS, D/N/N in x, periodic in y, adaptive CFL 0.4 (BASELINE.json configs[1])",
                 "value": 1024 * 1024 * n3 / w3 / 1e6, "unit": "Mcell-updates/s", "ms_per_step": w3 / n3 * 1e3, "steps": n3, "kernel_ms": k3,
@@ -608,11 +644,17 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline leg')
-    ap.add_argument('--no-variants', action='store_true', help='skip the 2-D-gap and GP-closure variants of the workload')
-    ap.add_argument('--no-gp', action='store_true', help='skip the GP-closure variant (BASELINE.json configs[3])')
-    ap.add_argument('--cfg1', action='store_true', help='also time BASELINE.json configs[1] (2-D inclined slider 1024^2) as variants.slider_1024x1024')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what they computed (a fixed sample of q, the scalars) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also the repeats / spread, roofline, variants and CPU baselines (off: the headline steps only)')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the cpu_baseline leg')
+    ap.add_argument('--no-variants', action='store_true', help='with --full: skip the 2-D-gap and GP-closure variants of the workload')
+    ap.add_argument('--no-gp', action='store_true', help='with --full: skip the GP-closure variant (BASELINE.json configs[3])')
+    ap.add_argument('--cfg1', action='store_true', help='with --full: also time BASELINE.json configs[1] (2-D inclined slider 1024^2) as variants.slider_1024x1024')
     args = ap.parse_args()
+    if args.dump_outputs is not None and (args.gpus > 1 or int(os.environ.get('WORLD_SIZE', '1')) > 1):
+        raise SystemExit("--dump-outputs is implemented for --gpus 1 (one process holds the whole field)")
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     # Native libraries (RCCL prints its version banner) write to file descriptor 1 directly: park the real stdout

@@ -3,7 +3,7 @@ the same device compare):
 
     python tools/ab_step.py [--rounds R] [--steps K] name=path/to/lib.so[,ENV=VAL...] ...
 
-Runs bench.py --no-cpu once per variant and round (alternating), with GPF_LIB_PATH set, and prints per variant the
+Runs bench.py --full --no-cpu once per variant and round (alternating), with GPF_LIB_PATH set, and prints per variant the
 median kernel / whole-step time of the x-only-gap workload (journal bearing) and of the 2-D-gap variant (asperity)."""
 import json
 import os
@@ -35,7 +35,7 @@ def main():
             e = dict(os.environ, **env)
             if lib:
                 e['GPF_LIB_PATH'] = os.path.join(ROOT, lib)
-            out = subprocess.run([sys.executable, 'bench.py', '--no-cpu', '--no-gp', '--steps', str(steps)], cwd=ROOT, env=e,
+            out = subprocess.run([sys.executable, 'bench.py', '--full', '--no-cpu', '--no-gp', '--steps', str(steps)], cwd=ROOT, env=e,
                                  capture_output=True, text=True, timeout=600)
             if out.returncode != 0:
                 print(name, 'FAILED', out.stderr[-500:], flush=True)

@@ -2,10 +2,10 @@
 
     cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && python tools/collect_profile.py gpurun_out/profile_<name>
 
-  bench.json                 python bench.py (the full default run: headline workload, 2-D-gap variant, GP variant, cpu_baseline)
-  kernel_stats.csv           rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --no-cpu
+  bench.json                 python bench.py --full (the whole run: headline workload, 2-D-gap variant, GP variant, cpu_baseline)
+  kernel_stats.csv           rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --no-cpu
   pmc_means_per_launch.json  per-kernel means of the counters, one rocprofv3 --pmc pass per group (never combined with other
-                             traces), python3 bench.py --steps 6 --warmup 2 --no-cpu --no-gp
+                             traces), python3 bench.py --full --steps 6 --warmup 2 --no-cpu --no-gp
   traffic_line.json          HBM bytes per launch of the step kernel on the headline workload (x-only gap, topography read as
   traffic_planes.json        a per-row profile) and on the 2-D-gap variant (three topography planes):
                              2 x FETCH_SIZE + WRITE_SIZE (gfx950 correction of MI355X_MICROARCH.md, HBM section:
@@ -36,13 +36,13 @@ def main():
     os.makedirs(out, exist_ok=True)
     # 1. the benchmark line itself
     with open(os.path.join(out, 'bench.json'), 'w') as f:
-        subprocess.run([sys.executable, 'bench.py'], stdout=f, stderr=open(os.path.join(out, 'bench.err'), 'w'), cwd=ROOT,
+        subprocess.run([sys.executable, 'bench.py', '--full'], stdout=f, stderr=open(os.path.join(out, 'bench.err'), 'w'), cwd=ROOT,
                        env=env, timeout=900, check=True)
     print('bench.json written', flush=True)
     # 2. kernel trace + stats of the same command (cpu leg off: it launches no kernels)
     kt = os.path.join(out, 'kt')
     run(['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', kt, '-o', 'kt', '--',
-         'python3', 'bench.py', '--no-cpu'], os.path.join(out, 'kt.log'), env)
+         'python3', 'bench.py', '--full', '--no-cpu'], os.path.join(out, 'kt.log'), env)
     stats = glob.glob(os.path.join(kt, '**', '*kernel_stats.csv'), recursive=True)
     if stats:
         os.replace(stats[0], os.path.join(out, 'kernel_stats.csv'))
@@ -51,7 +51,7 @@ def main():
     for i, group in enumerate(PMC_PASSES):
         d = os.path.join(out, f'pmc{i}')
         run(['rocprofv3', '--pmc'] + group + ['--kernel-trace', '--output-format', 'csv', '-d', d, '-o', 'pmc', '--',
-             'python3', 'bench.py', '--steps', '6', '--warmup', '2', '--no-cpu', '--no-gp'],
+             'python3', 'bench.py', '--full', '--steps', '6', '--warmup', '2', '--no-cpu', '--no-gp'],
             os.path.join(out, f'pmc{i}.log'), env)
         for fn in glob.glob(os.path.join(d, '**', '*counter_collection.csv'), recursive=True):
             for row in csv.DictReader(open(fn)):

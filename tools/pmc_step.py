@@ -2,8 +2,8 @@
 
     python tools/pmc_step.py OUTDIR [--planes] [--lib path/to/lib.so]
 
-Separate rocprofv3 --pmc passes (never combined with other traces) of `bench.py --steps 6 --warmup 2 --no-cpu
---no-variants`; prints the per-launch means for the step kernel and the derived figures (HBM bytes with the gfx950
+Separate rocprofv3 --pmc passes (never combined with other traces) of `bench.py --full --steps 6 --warmup 2
+--no-cpu --no-variants`; prints the per-launch means for the step kernel and the derived figures (HBM bytes with the gfx950
 FETCH_SIZE correction of MI355X_MICROARCH.md, VALU-active share per wave, wait share)."""
 import csv
 import glob
@@ -30,7 +30,7 @@ def main():
         d = os.path.join(out, f'pmc{i}')
         with open(os.path.join(out, f'pmc{i}.log'), 'w') as f:
             subprocess.run(['rocprofv3', '--pmc'] + group + ['--kernel-trace', '--output-format', 'csv', '-d', d, '-o', 'pmc', '--',
-                            'python3', 'bench.py', '--steps', '6', '--warmup', '2', '--no-cpu', '--no-variants'],
+                            'python3', 'bench.py', '--full', '--steps', '6', '--warmup', '2', '--no-cpu', '--no-variants'],
                            stdout=f, stderr=subprocess.STDOUT, cwd=ROOT, env=env, timeout=600)
         for fn in glob.glob(os.path.join(d, '**', '*counter_collection.csv'), recursive=True):
             for row in csv.DictReader(open(fn)):
