@@ -84,6 +84,13 @@ SIGNATURES = {
                               C.c_double, C.c_double, C.c_void_p]),
     'gpf_elastic_setup': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int]),
     'gpf_elastic_update': (C.c_int, [C.c_void_p]),
+    'gpf_elastic_slab_setup': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                         C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int]),
+    'gpf_elastic_slab_buffer': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    'gpf_elastic_slab_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    'gpf_elastic_slab_convolve': (C.c_int, [C.c_void_p]),
+    'gpf_elastic_slab_finish': (C.c_int, [C.c_void_p]),
+    'gpf_elastic_slab_apply': (C.c_int, [C.c_void_p]),
     'gpf_p2p_export': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     'gpf_p2p_connect': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     'gpf_p2p_set_timeout': (C.c_int, [C.c_void_p, C.c_double]),

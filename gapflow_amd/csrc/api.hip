@@ -122,6 +122,15 @@ struct gpf_handle {
     struct { bool on = false; int px = 0, py = 0, relative = 0; double alpha = 1.0, scale = 1.0; void* plan_f = nullptr; void* plan_b = nullptr;
              double2* greens = nullptr; double2* spec = nullptr; double* dense = nullptr;
              double* u_prev = nullptr; double* h0 = nullptr; double* deformation = nullptr; } el;
+    // elastic half-space on an x-slab (gpf_elastic_slab_*): this rank's transform rows, ky column slab, return rows, and the
+    // buffers of the two transposes (api_slab_elastic.inc)
+    struct { bool on = false; int px = 0, py = 0, nky = 0, nranks = 1, relative = 0;
+             int row0 = 0, nrows = 0, k0 = 0, nk = 0, nret = 0, nrows_all = 0, nmain = 0, main_g0 = 0, seam_side = -1, seam_g0 = 0, ref_row = -1;
+             double alpha = 1.0, scale = 1.0;
+             void* plan_y = nullptr; void* plan_x = nullptr; void* plan_yb = nullptr; int nxg = 0, g_lo = 0;
+             double* dense = nullptr; double2* spec = nullptr; double2* send1 = nullptr; double2* recv1 = nullptr; double2* xspec = nullptr;
+             double2* greens = nullptr; double2* send2 = nullptr; double2* recv2 = nullptr; double2* line = nullptr; double* ureal = nullptr;
+             double* u_prev = nullptr; double* h0 = nullptr; double* deformation = nullptr; double* ref = nullptr; int* rows_all = nullptr; } els;
     double* gptile = nullptr;               // Ks tile for the variance solve
     size_t gptile_doubles = 0;
     void* blas = nullptr;
@@ -292,6 +301,8 @@ extern "C" int gpf_create(const gpf_config* cfg, gpf_handle** out) {
 extern "C" int gpf_destroy(gpf_handle* h) {
     if (!h) return GPF_OK;
     hipSetDevice(h->cfg.device);
+    // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
+    hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
     void* ptrs[] = {h->topo_line, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
@@ -301,6 +312,12 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     if (h->el.plan_f) fftlib().destroy(h->el.plan_f);
     if (h->el.plan_b) fftlib().destroy(h->el.plan_b);
     for (void* p : {(void*)h->el.greens, (void*)h->el.spec, (void*)h->el.dense, (void*)h->el.u_prev})     // h0, deformation live in u_prev's block
+        if (p) hipFree(p);
+    for (void* pl : {h->els.plan_y, h->els.plan_x, h->els.plan_yb})
+        if (pl) fftlib().destroy(pl);
+    for (void* p : {(void*)h->els.dense, (void*)h->els.spec, (void*)h->els.send1, (void*)h->els.recv1, (void*)h->els.xspec, (void*)h->els.greens,
+                    (void*)h->els.send2, (void*)h->els.recv2, (void*)h->els.line, (void*)h->els.ureal, (void*)h->els.u_prev, (void*)h->els.ref,
+                    (void*)h->els.rows_all})      // h0, deformation live in u_prev's block
         if (p) hipFree(p);
     for (int r = 0; r < h->p2p.nranks; ++r)
         if (h->p2p.box[r] && r != h->p2p.rank) hipIpcCloseMemHandle(h->p2p.box[r]);
@@ -388,7 +405,7 @@ extern "C" int gpf_upload(gpf_handle* h, int field, const double* host, size_t c
             }
         const int mode = xonly ? 1 : (yonly ? 2 : 0);
         if (mode != h->topo_mode) { h->plan2_valid = false; }
-        h->topo_mode = h->el.on ? 0 : mode;         // an elastic gap changes on the device: always read the planes
+        h->topo_mode = (h->el.on || h->els.on) ? 0 : mode;         // an elastic gap changes on the device: always read the planes
         if (mode) {
             const int n = mode == 1 ? nx : ny;
             std::vector<double> line((size_t)3 * n);
@@ -436,8 +453,8 @@ extern "C" int gpf_download(gpf_handle* h, int field, double* host, size_t count
         if (!h->Ls) { std::memset(host, 0, count * sizeof(double)); return GPF_OK; }
         src = h->Ls; break;
     case GPF_FIELD_DEFORMATION:
-        if (!h->el.on) { std::memset(host, 0, count * sizeof(double)); return GPF_OK; }
-        src = h->el.deformation; break;
+        if (!h->el.on && !h->els.on) { std::memset(host, 0, count * sizeof(double)); return GPF_OK; }
+        src = h->el.on ? h->el.deformation : h->els.deformation; break;
     case GPF_FIELD_PRESSURE_VAR: case GPF_FIELD_WALL_XZ_VAR: case GPF_FIELD_WALL_YZ_VAR:
         if (!h->gpvar) return fail(GPF_ERR_STATE, "gpf_download: no GP variance has been computed");
         src = h->gpvar + (size_t)(field - GPF_FIELD_PRESSURE_VAR) * L.plane;
@@ -939,3 +956,4 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
 #include "api_gp.inc"
 #include "api_stagewise.inc"
 #include "api_slab_stagewise.inc"
+#include "api_slab_elastic.inc"

@@ -67,6 +67,8 @@ extern "C" int gpf_close_step_local(gpf_handle* h) {
     hipLaunchKernelGGL(k_bc_y, dim3((L.Nx + 2 + 255) / 256), dim3(256), 0, h->stream, q, L, h->E);
     GPF_TRY(launch_scalars(h, q, post));
     hipLaunchKernelGGL(k_record_unfused, dim3(1), dim3(1), 0, h->stream, pre, post, h->halo + (halo_len(h) - 8));
+    if (h->els.on && h->els.relative && h->E.halo[0] != 1)      // the slab holding global row 0: p_ref rides in its record
+        hipLaunchKernelGGL(k_els_record_pref, dim3(1), dim3(1), 0, h->stream, (const double*)h->fields, L, h->halo + (halo_len(h) - 8));
     HIP_TRY(hipGetLastError());
     return GPF_OK;
 }

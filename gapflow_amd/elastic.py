@@ -81,6 +81,20 @@ class ElasticDeformation:
                                                   float(self.alpha_underrelax), float(self.area_per_cell / self.area_per_pt),
                                                   0 if self.periodicity == 'full' else 1))
 
+    def attach_slab(self, problem, plan, rank, h0_rows):
+        """Upload this rank's share for the x-slab form (gpf_elastic_slab_setup): its ky slab of the Green's spectrum (the
+        whole spectrum is never resident on the device) and the undeformed gap of the rows it gets back."""
+        px, py = self.shape_fft
+        k0, nk = plan.ky[rank]
+        g = np.ascontiguousarray(np.stack([self.greens.real[:, k0:k0 + nk], self.greens.imag[:, k0:k0 + nk]], axis=-1),
+                                 dtype=np.float64)
+        ints = plan.c_plan(rank)
+        h0 = np.ascontiguousarray(h0_rows, dtype=np.float64)
+        _lib.check(problem.lib.gpf_elastic_slab_setup(problem._h, px, py, plan.world, ints.ctypes.data_as(C.c_void_p), ints.size,
+                                                      g.ctypes.data_as(C.c_void_p), g.size, h0.ctypes.data_as(C.c_void_p), h0.size,
+                                                      float(self.alpha_underrelax), float(self.area_per_cell / self.area_per_pt),
+                                                      0 if self.periodicity == 'full' else 1))
+
     # -- analysis helpers of the reference (topography.py:439-465) -----------------------------
     def get_G_real(self):
         if self._G_real is None:
@@ -90,3 +104,82 @@ class ElasticDeformation:
     def get_G_real_slices(self):
         G = self.get_G_real()
         return G[:, G.shape[1] // 2], G[G.shape[0] // 2, :]
+
+
+def ky_partition(nky, world):
+    """(k0, nk) of every rank: [0, nky) cut into `world` consecutive slabs, the first nky % world one column wider; a rank
+    may get none (csrc/elastic_kernels.hip: KySplit)."""
+    base, rem = divmod(nky, world)
+    out, k0 = [], 0
+    for r in range(world):
+        n = base + (1 if r < rem else 0)
+        out.append((k0, n))
+        k0 += n
+    return out
+
+
+class SlabElasticPlan:
+    """Who transforms, holds and receives what in the x-slab form of the half-space convolution (plain Python; the
+    device side is csrc/api_slab_elastic.inc).  Rows are global indices 0..Nx+1 of the (Nx+2)-row field, slabs are the
+    `parts` of slab.partition (contiguous in x, in rank order); the transform grid is px x py with nky = py/2 + 1 columns.
+
+      fwd[r]   = (row0, nrows)  transform rows rank r owns: its interior rows, + row 0 on the first rank, + row Nx+1 on the
+                                last.  The zero rows of a doubled x range are never transformed or sent.
+      ky[r]    = (k0, nk)       its ky column slab (ky_partition)
+      main[r]  = (g0, n)        rows it gets back: lo-2 .. hi+2 clipped to [0, Nx+1] -- its rows and the one beyond each,
+                                so that np.gradient is exact on all of them
+      seam[r]  = (side, g0)     on a periodic seam edge (world > 1): three more rows across the seam, Nx-1..Nx+1 for the
+                                first rank (side 0), 0..2 for the last (side 1); (-1, 0) elsewhere
+    Split sizes of the two all-to-alls are in complex numbers (two doubles each)."""
+
+    def __init__(self, Nx, px, py, parts, seam):
+        self.Nx, self.px, self.py, self.nky = Nx, px, py, py // 2 + 1
+        self.parts, self.world = list(parts), len(parts)
+        last = self.world - 1
+        self.fwd, self.main, self.seam = [], [], []
+        for r, (lo, hi) in enumerate(self.parts):
+            r0, r1 = (0 if r == 0 else lo), (Nx + 1 if r == last else hi)
+            self.fwd.append((r0, r1 - r0 + 1))
+            m0, m1 = max(0, lo - 2), min(Nx + 1, hi + 2)
+            self.main.append((m0, m1 - m0 + 1))
+            if seam and self.world > 1 and r == 0:
+                self.seam.append((0, Nx - 1))
+            elif seam and self.world > 1 and r == last:
+                self.seam.append((1, 0))
+            else:
+                self.seam.append((-1, 0))
+        self.ky = ky_partition(self.nky, self.world)
+
+    @classmethod
+    def for_grid(cls, grid, world, shape_fft):
+        from .slab import partition
+        periodic = all(grid['bc_xE_P']) and all(grid['bc_xW_P'])
+        return cls(grid['Nx'], shape_fft[0], shape_fft[1], partition(grid['Nx'], world), periodic)
+
+    def return_rows(self, r):
+        g0, n = self.main[r]
+        rows = list(range(g0, g0 + n))
+        side, s0 = self.seam[r]
+        if side >= 0:
+            rows += [s0, s0 + 1, s0 + 2]
+        return rows
+
+    def send1(self, r):
+        return [self.fwd[r][1] * self.ky[s][1] for s in range(self.world)]
+
+    def recv1(self, r):
+        return [self.fwd[s][1] * self.ky[r][1] for s in range(self.world)]
+
+    def send2(self, r):
+        return [len(self.return_rows(s)) * self.ky[r][1] for s in range(self.world)]
+
+    def recv2(self, r):
+        return [len(self.return_rows(r)) * self.ky[s][1] for s in range(self.world)]
+
+    def c_plan(self, r):
+        """int32 plan of rank r in the layout of gpf_elastic_slab_setup."""
+        lo, hi = self.parts[r]
+        rows_all = [g for s in range(self.world) for g in self.return_rows(s)]
+        head = [self.fwd[r][0], self.fwd[r][1], self.ky[r][0], self.ky[r][1], len(self.return_rows(r)), self.main[r][1],
+                self.main[r][0], self.seam[r][0], self.seam[r][1], len(rows_all), lo - 1, self.Nx, r]
+        return np.asarray(head + rows_all, dtype=np.int32)

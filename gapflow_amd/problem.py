@@ -37,7 +37,10 @@ def _termination_signals():
 class Problem:
     """Gap-averaged lubrication problem advanced by the fused MacCormack HIP kernel."""
 
-    def __init__(self, options, grid, numerics, prop, geo, gp=None, database=None, extra_field=None, device=0):
+    def __init__(self, options, grid, numerics, prop, geo, gp=None, database=None, extra_field=None, device=0,
+                 elastic_on_device=True):
+        """elastic_on_device=False: an elastic gap is flagged (topo.nc gets a frame with every solution frame) but not
+        deformed here -- the caller supplies the deformed gap (the output writer of gapflow_amd/slab.py)."""
         if gp is not None and database is None:
             raise IOError("GP closures need a training database (`db` section)")
         if database is not None and not getattr(database, 'has_mock_md', True):
@@ -74,7 +77,7 @@ class Problem:
         self.topo = Topography(grid, geo, prop, on_change=self._upload_topo)
         self._upload_topo()
         self._elastic = None
-        if self.topo.elastic:                   # topography.py:236-249
+        if self.topo.elastic and elastic_on_device:         # topography.py:236-249
             from .elastic import ElasticDeformation
             el = prop['elastic']
             self._elastic = ElasticDeformation(el['E'], el['v'], el['alpha_underrelax'], grid, el['n_images'])

@@ -108,6 +108,15 @@ class LoopbackGroup:
     def broadcast_object_list(self, box, src=0):
         pass
 
+    def all_to_all_single(self, out, inp, output_split_sizes, input_split_sizes):
+        """Chunk s of the output is the start of this rank's own chunk for s (message sizes and launches, not physics)."""
+        oo, io = 0, 0
+        for n_out, n_in in zip(output_split_sizes, input_split_sizes):
+            n = min(n_out, n_in)
+            out[oo:oo + n].copy_(inp[io:io + n])
+            out[oo + n:oo + n_out].zero_()
+            oo, io = oo + n_out, io + n_in
+
     def barrier(self):
         pass
 
@@ -140,6 +149,12 @@ class HostStagedGroup:
         self._d.all_reduce(c, op=op if op is not None else self.ReduceOp.SUM)
         t.copy_(c)
 
+    def all_to_all_single(self, out, inp, output_split_sizes, input_split_sizes):
+        self._t.cuda.synchronize()
+        o, i = out.cpu(), inp.cpu()
+        self._d.all_to_all_single(o, i, output_split_sizes, input_split_sizes)      # gloo: alltoall_base
+        out.copy_(o)
+
     def broadcast_object_list(self, box, src=0):
         self._d.broadcast_object_list(box, src=src)
 
@@ -158,8 +173,8 @@ class ThreadWorld:
     8-slab strong-scaling run) cannot be rehearsed with one process per rank there.  Every rank is a real SlabProblem with
     its own library handle, partition, halo kinds, seam topography and messages; only the transport is stood in for.  All
     ranks enqueue on the device's default stream, so "every rank has enqueued its part" (a thread barrier) is all the
-    ordering a collective needs.  All-gather transport only: the mailbox kernels poll for their peers and would wait for
-    launches queued behind them on the shared stream."""
+    ordering a collective needs.  All-gather and all-to-all transport only: the mailbox kernels poll for their peers and would
+    wait for launches queued behind them on the shared stream."""
 
     class ReduceOp:
         SUM, MAX, MIN = 'sum', 'max', 'min'
@@ -191,6 +206,22 @@ class ThreadWorld:
             parts = out.view(w.world, -1)
             for r in range(w.world):
                 parts[r].copy_(w._slots[r].view(-1))
+            w._barrier.wait()                           # every rank's copies are enqueued: the inputs may change again
+
+        def all_to_all_single(self, out, inp, output_split_sizes, input_split_sizes):
+            """Uneven all-to-all: chunk r of rank s's input goes to chunk s of rank r's output (device copies)."""
+            w = self._w
+            w._slots[self._rank] = (inp, list(input_split_sizes))
+            w._barrier.wait()                           # every rank's producers are enqueued
+            o = 0
+            for s in range(w.world):
+                src, splits = w._slots[s]
+                n, start = output_split_sizes[s], sum(splits[:self._rank])
+                if splits[self._rank] != n:
+                    raise ValueError(f"all_to_all_single: rank {s} sends {splits[self._rank]} elements, rank {self._rank} expects {n}")
+                if n:
+                    out[o:o + n].copy_(src[start:start + n])
+                o += n
             w._barrier.wait()                           # every rank's copies are enqueued: the inputs may change again
 
         def all_reduce(self, t, op=None):
@@ -438,6 +469,9 @@ class SlabProblem:
                 _lib.check(self.lib.gpf_set_seam_topo(self._h, side, _lib.as_dp(seam), seam.size))
         self.engine = HipSlabEngine(self.lib, self._h, torch, self.world)
         self.driver = SlabDriver(self.engine, L, dist, torch)
+        self._elastic = None
+        if prop.get('elastic', {}).get('enabled', False):
+            self._elastic = SlabElastic(self, grid, prop['elastic'], topo_rows)
 
         # surrogate closures: the database and the models are replicated on every rank
         self.grid, self._lib, self._closures_stale = grid, self.lib, True
@@ -550,7 +584,8 @@ class SlabProblem:
         return pairs[int(np.argmax(pairs[:, 0])), 1:].copy()
 
     def _features_local(self):
-        return np.vstack([self.local_q(), self._topo_local, self._extra]).reshape(7, -1).T
+        topo = self._topo_local if self._elastic is None else self._download(_lib.FIELD_TOPO, 3)
+        return np.vstack([self.local_q(), topo, self._extra]).reshape(7, -1).T
 
     def pre_run(self):
         """Problem._pre_run (problem.py:412-443) with domain-wide scalars."""
@@ -568,7 +603,7 @@ class SlabProblem:
         self._pre_run_done = True
 
     def advance(self, n, honor_stop=False, write_freq=None):
-        if not self._gp_models and not self._thinning:
+        if not self._gp_models and not self._thinning and self._elastic is None:
             return self.driver.advance(n, honor_stop)
         for _ in range(n):
             st = self.state()
@@ -612,6 +647,10 @@ class SlabProblem:
         self.dist.all_gather_into_tensor(d.gathered, d.message)
         sc = _lib.GpfScalars()
         _lib.check(lib.gpf_close_step_commit(h, gathered, self.world, C.byref(sc)))
+        if self._elastic is not None and not sc.invalid:
+            # Topography.update (problem.py:566) with the pressure of the corrector's closures; the record all-gather above
+            # carried p_ref; sc.invalid is the same on every rank (rank-ordered reduction)
+            self._elastic.step(gathered)
         return sc
 
     def state(self):
@@ -625,17 +664,25 @@ class SlabProblem:
     def gather_q(self):
         """The whole field (3, Nx+2, Ny+2) on every rank: owned rows from their owners, the domain's two ghost rows
         from the first and last rank.  Collective; meant for output frames, not for the time loop."""
+        return self._gather_rows(self.local_q())
+
+    def gather_topo(self):
+        """The whole deformed gap (4, Nx+2, Ny+2): h, dh/dx, dh/dy, displacement, gathered like gather_q."""
+        local = np.concatenate([self._download(_lib.FIELD_TOPO, 3), self._download(_lib.FIELD_DEFORMATION, 1)])
+        return self._gather_rows(local)
+
+    def _gather_rows(self, local):
         t, L = self.torch, self.layout
         parts = partition(L.Nx_global, self.world)
         max_nx = max(hi - lo + 1 for lo, hi in parts)
-        ny2 = self._shape[1]
-        mine = np.zeros((3, max_nx + 2, ny2))
-        mine[:, :L.nx + 2] = self.local_q()
+        ny2, nc = self._shape[1], local.shape[0]
+        mine = np.zeros((nc, max_nx + 2, ny2))
+        mine[:, :L.nx + 2] = local
         send = t.from_numpy(mine.reshape(-1)).to('cuda')
         recv = t.zeros(send.numel() * self.world, dtype=t.float64, device='cuda')
         self.dist.all_gather_into_tensor(recv, send)
-        allq = recv.cpu().numpy().reshape(self.world, 3, max_nx + 2, ny2)
-        out = np.empty((3, L.Nx_global + 2, ny2))
+        allq = recv.cpu().numpy().reshape(self.world, nc, max_nx + 2, ny2)
+        out = np.empty((nc, L.Nx_global + 2, ny2))
         for r, (lo, hi) in enumerate(parts):
             out[:, lo:hi + 1] = allq[r, :, 1:hi - lo + 2]
         out[:, 0] = allq[0, :, 0]
@@ -646,6 +693,7 @@ class SlabProblem:
         """One output frame through a whole-domain Problem that only rank 0 holds: it owns the output directory, the
         NetCDF / csv writers and the closures of the frame (Problem.write, problem.py:616-637)."""
         q = self.gather_q()
+        topo = self.gather_topo() if self._elastic is not None else None
         if self.rank != 0:
             return
         if self._writer_problem is None:
@@ -655,7 +703,8 @@ class SlabProblem:
             # hyper-parameters), so the closures of a frame are the surrogates' means as in a serial run
             self._writer_problem = Problem(d['options'], d['grid'], d['numerics'], d['properties'], d['geometry'],
                                            gp=d.get('gp') if self._gp_models else None,
-                                           database=self.database if self._gp_models else None, device=self._device)
+                                           database=self.database if self._gp_models else None, device=self._device,
+                                           elastic_on_device=False)
             w = self._writer_problem
             w.history = {k: [] for k in ('step', 'time', 'ekin', 'residual', 'vsound')}
         w = self._writer_problem
@@ -664,6 +713,9 @@ class SlabProblem:
             if wm.theta is None or wm.last_fit_train_size != m.last_fit_train_size or not np.array_equal(wm.theta, m.theta):
                 wm.theta, wm.last_fit_train_size = np.array(m.theta), m.last_fit_train_size
                 wm.attach()
+        if topo is not None:            # the deformed gap of the slabs: topo.nc's frame and the frame's closures
+            w.topo.full[...] = topo
+            w._upload_topo()
         st = self.state()
         w.q[...] = q
         w.step, w.simtime, w.dt, w.residual = int(st.step), st.simtime, st.dt, st.residual
@@ -715,3 +767,42 @@ class SlabProblem:
         out = np.empty((3,) + self._shape)
         _lib.check(self.lib.gpf_download(self._h, _lib.FIELD_Q, _lib.as_dp(out), out.size))
         return out
+
+
+class SlabElastic:
+    """Elastic deformation of the gap on an x-slab: the distributed half-space convolution (gapflow_amd/elastic.py:
+    SlabElasticPlan, csrc/api_slab_elastic.inc) and its collectives -- two uneven all-to-alls and, unless the half-space
+    is fully periodic, an all-gather of 8 doubles that hands rank 0's reference displacement to every rank."""
+
+    def __init__(self, slab, grid, el, topo_rows):
+        from .elastic import ElasticDeformation, SlabElasticPlan
+        self.slab, torch, lib, h = slab, slab.torch, slab.lib, slab._h
+        self.host = ElasticDeformation(el['E'], el['v'], el['alpha_underrelax'], grid, el['n_images'])
+        self.plan = P = SlabElasticPlan.for_grid(grid, slab.world, self.host.shape_fft)
+        r = slab.rank
+        h0 = topo_rows(P.return_rows(r))[0]
+        self.host.attach_slab(slab, P, r, h0)
+        self.relative = self.host.periodicity != 'full'
+
+        def buf(which):
+            p, n = C.c_void_p(), C.c_size_t(0)
+            _lib.check(lib.gpf_elastic_slab_buffer(h, which, C.byref(p), C.byref(n)))
+            if n.value == 0:
+                return torch.empty(0, dtype=torch.float64, device='cuda')
+            return torch.as_tensor(_DeviceArray(p.value, n.value), device='cuda')
+        self.send1, self.recv1, self.send2, self.recv2, self.ref, self.refs = (buf(i) for i in range(6))
+        two = lambda counts: [2 * c for c in counts]          # complex numbers -> doubles
+        self.splits1 = (two(P.recv1(r)), two(P.send1(r)))
+        self.splits2 = (two(P.recv2(r)), two(P.send2(r)))
+
+    def step(self, gathered):
+        s = self.slab
+        lib, h, dist = s.lib, s._h, s.dist
+        _lib.check(lib.gpf_elastic_slab_forward(h, gathered, s.world))
+        dist.all_to_all_single(self.recv1, self.send1, *self.splits1)
+        _lib.check(lib.gpf_elastic_slab_convolve(h))
+        dist.all_to_all_single(self.recv2, self.send2, *self.splits2)
+        _lib.check(lib.gpf_elastic_slab_finish(h))
+        if self.relative:
+            dist.all_gather_into_tensor(self.refs, self.ref)
+        _lib.check(lib.gpf_elastic_slab_apply(h))

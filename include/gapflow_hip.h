@@ -180,10 +180,32 @@ int gpf_step_commit(gpf_handle* h, int honor_stop, const void* gathered, int nra
  * displacement are taken relative to cell [0, 0] (every case but the fully periodic one).  The handle's current
  * topography is kept as the undeformed one.  gpf_elastic_update convolves the pressure of the last closure evaluation,
  * under-relaxes, and rewrites h, dh/dx, dh/dy (np.gradient stencil) in place; GPF_FIELD_DEFORMATION downloads the
- * displacement.  Undivided problems only. */
+ * displacement.  Undivided problems; slabs use gpf_elastic_slab_* below. */
 int gpf_elastic_setup(gpf_handle* h, int px, int py, const double* greens_ri, size_t count, double alpha,
                       double force_scale, int relative);
 int gpf_elastic_update(gpf_handle* h);
+/* The same deformation on an x-slab (topography.py:257-280, 404-437 as a distributed transform; no rank holds the whole
+ * spectrum).  gpf_elastic_slab_setup takes this rank's plan (gapflow_amd/elastic.py: SlabElasticPlan; layout in
+ * csrc/api_slab_elastic.inc): transform rows it owns, its ky column slab of [0, py/2], the rows it gets back (its rows and
+ * one more on each side, plus three seam rows on a periodic seam edge) and every rank's return rows; greens_ri = its slab
+ * of the Green's spectrum [px][nk][2]; h0_rows = the undeformed gap of its return rows [nret][Ny+2].  Per step, after
+ * gpf_close_step_commit of a valid step:
+ *   gpf_elastic_slab_forward   forces of the owned rows (p_ref from rank 0's record in `gathered`), D2Z, column pack
+ *   -- all-to-all of buffer 0 into buffer 1 (caller) --
+ *   gpf_elastic_slab_convolve  x-transforms, Green's multiply, inverse x-transforms, row pack
+ *   -- all-to-all of buffer 2 into buffer 3 (caller) --
+ *   gpf_elastic_slab_finish    unpack, Z2D, under-relaxation; reference displacement into buffer 4
+ *   -- relative mode: all-gather of buffer 4 into buffer 5 (caller) --
+ *   gpf_elastic_slab_apply     h, dh/dx, dh/dy and the displacement of the slab's rows and of its seam block
+ * gpf_elastic_slab_buffer returns those device buffers (count in doubles).  Every call only enqueues on the handle's stream. */
+int gpf_elastic_slab_setup(gpf_handle* h, int px, int py, int nranks, const int32_t* plan, size_t plan_count,
+                           const double* greens_ri, size_t greens_count, const double* h0_rows, size_t h0_count,
+                           double alpha, double force_scale, int relative);
+int gpf_elastic_slab_buffer(gpf_handle* h, int which, void** ptr, size_t* count);
+int gpf_elastic_slab_forward(gpf_handle* h, const void* gathered, int nranks);
+int gpf_elastic_slab_convolve(gpf_handle* h);
+int gpf_elastic_slab_finish(gpf_handle* h);
+int gpf_elastic_slab_apply(gpf_handle* h);
 
 /* Peer-to-peer slab transport (GPUs of one node, one process each).  Instead of a collective library the step's own
  * kernels store the two boundary rows and the 64-byte record straight into the peers' mailboxes (device memory mapped
