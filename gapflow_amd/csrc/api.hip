@@ -146,6 +146,7 @@ struct gpf_handle {
     int nchunks2 = 0, nblocks2 = 0, npartials2_cap = 0, nblock_partials_cap = 0;
     bool plan2_valid = false;
     int nt_policy2 = 0;                     // k_step2's traffic with the non-temporal hint: 0 none, 1 the stores, 2 stores and loads (plan_step2)
+    int keep_rows2 = 0;                     // with nt stores: rows with (ix & 7) < keep_rows2 are stored to stay in the Infinity Cache (plan_step2)
     StepState* st_trial = nullptr;          // plan_step2's timing launches commit into this copy of the run state
     double* plan_master = nullptr;          // copy of the current state while plan_step2 runs its trials
     char plan2_note[400] = "";              // how the plan was arrived at (gpf_plan_note)
@@ -766,7 +767,8 @@ static void fill_step2_args(gpf_handle* h, Step2Args& a2, int D, int honor_stop,
     a2.g1x = h->g1; a2.g1y = h->g1 + 3 * L.pitch;
     a2.st = h->st; a2.partials = h->partials; a2.block_partials = h->block_partials; a2.arrive = h->arrive;
     a2.log = h->log; a2.log_base = log_base; a2.log_cap = h->log_cap;
-    a2.L = L; a2.E = h->E; a2.G = G2; a2.nchunks = h->nchunks2; a2.fused = (fused ? 1 : 0) | (h->nt_policy2 >= 1 ? 2 : 0) | (h->nt_policy2 >= 2 ? 4 : 0); a2.honor_stop = honor_stop;
+    a2.L = L; a2.E = h->E; a2.G = G2; a2.nchunks = h->nchunks2; a2.fused = (fused ? 1 : 0) | (h->nt_policy2 >= 1 ? 2 : 0) | (h->nt_policy2 >= 2 ? 4 : 0) |
+               (h->nt_policy2 >= 1 ? h->keep_rows2 << 3 : 0); a2.honor_stop = honor_stop;
     const bool slab = slab_out != nullptr;
     for (int e = 0; e < 2; ++e) a2.seam[e] = (h->E.halo[e] == 2 && h->has_seam[e]) ? h->seam + (size_t)e * 8 * L.pitch : nullptr;
     a2.out = slab_out; a2.msg = (slab && !p2p) ? h->halo : nullptr; a2.p2p = p2p_args(h, p2p);

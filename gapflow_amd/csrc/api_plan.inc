@@ -5,12 +5,13 @@ constexpr int K2_LONG_MARCH_ROWS = 100;    // rows per wave from which plan_step
 
 // One wave marches over one row chunk of one 126-column strip; the chunks are sized so that all waves are resident at
 // once (a single round, no tail) when the problem is big enough: two waves per SIMD, or one.
-static int plan_apply(gpf_handle* h, int nchunks, int nt) {
+static int plan_apply(gpf_handle* h, int nchunks, int nt, int keep = 0) {
     const Layout& L = h->L;
     const int nstrips = std::max(h->geom2[0].nstrips, h->geom2[1].nstrips);
     nchunks = std::max(1, std::min(nchunks, std::max(1, L.Nx / 4)));        // small grids: >= 4 rows per chunk
     h->nchunks2 = nchunks;
     h->nt_policy2 = nt;
+    h->keep_rows2 = nt >= 1 ? std::max(0, std::min(7, keep)) : 0;
     const int nwaves = nstrips * nchunks;
     h->nblocks2 = (((nwaves + 3) / 4) + 7) / 8 * 8;
     if (nwaves > h->npartials2_cap) {
@@ -221,7 +222,21 @@ static int plan_placement(gpf_handle* h, int D, std::string& note) {
 // stores, 4 % with two waves and plain ones; round 2's runs on other boxes favoured one wave per SIMD for both), so grids of a
 // million cells and more TIME the candidates once, on their own data (plan_trial: ~8 ms per handle), and keep the fastest.
 // Smaller grids and GPF_PLAN_TUNE=0 take the rule of thumb; GPF_CHUNKS / GPF_NT_STORES pin a choice (A/B runs).
+// The keep-set: with non-temporal stores, rows with (ix & 7) < k are stored plain, so that they stay in the Infinity Cache and the
+// next step reads them on the die (step2_kernel.hip).  Only the kept lines compete for the cache between a row's store and its next
+// load, so k / 8 of a state may be nearly as large as the cache.  At 4096^2 (x-only gap, in-process pairs on one box) k = 2 / 3 / 4 /
+// 5 took 0.95 / 0.93 / 0.92 / 0.93 of the time of k = 0 (profiles/r04_keep/).  Where the plan is timed, k in {0, 3, 4} is timed on
+// the chosen chunks and hint, launches back to back (plan_trial's `both`: each launch reads what the one before wrote); the rule of
+// thumb takes 4.  GPF_KEEP_ROWS=k pins it.
 static const char* const NT_NAME[3] = {"plain loads and stores", "non-temporal stores", "non-temporal loads and stores"};
+constexpr int K2_KEEP_ROWS_DEFAULT = 4;
+static const int K2_KEEP_CANDIDATES[2] = {3, 4};
+static std::string keep_note(const gpf_handle* h) {
+    if (h->nt_policy2 < 1) return "";
+    char buf[64];
+    std::snprintf(buf, sizeof buf, ", keep %d/8 rows on-die", h->keep_rows2);
+    return buf;
+}
 static int plan_step2(gpf_handle* h, int D) {
     if (h->plan2_valid) return GPF_OK;
     const Layout& L = h->L;
@@ -246,13 +261,16 @@ static int plan_step2(gpf_handle* h, int D) {
     int nt = nt_possible ? 2 : 0;
     if (env_chunks && std::atoi(env_chunks) > 0) nchunks = std::atoi(env_chunks);
     if (env_nt) nt = std::max(0, std::min(2, std::atoi(env_nt)));
+    const char* env_keep = std::getenv("GPF_KEEP_ROWS");
+    int keep = nt_possible ? K2_KEEP_ROWS_DEFAULT : 0;
+    if (env_keep) keep = std::max(0, std::min(7, std::atoi(env_keep)));
     // (a slab tunes like any other handle: the trial launches commit into the scratch state and send nothing)
     const bool tune = !(env_tune && std::atoi(env_tune) == 0) && !h->split_edges && h->pre_run_done && (long long)L.Nx * L.Ny >= (1ll << 20) &&
                       one_per_simd >= 1 && L.Nx / one_per_simd >= 16 && !(env_chunks && env_nt);
     if (!tune) {
-        GPF_TRY(plan_apply(h, nchunks, nt));
-        std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s (rule of thumb%s)", h->nchunks2,
-                      NT_NAME[h->nt_policy2], (env_chunks || env_nt) ? ", pinned by the environment" : "");
+        GPF_TRY(plan_apply(h, nchunks, nt, keep));
+        std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s%s (rule of thumb%s)", h->nchunks2,
+                      NT_NAME[h->nt_policy2], keep_note(h).c_str(), (env_chunks || env_nt || env_keep) ? ", pinned by the environment" : "");
         h->plan2_valid = true;
         return GPF_OK;
     }
@@ -274,7 +292,8 @@ static int plan_step2(gpf_handle* h, int D) {
     float best = 0.f;
     int best_chunks = nchunks;
     int best_nt = nt;
-    std::string seen;
+    int best_keep = 0;
+    std::string seen, keep_seen;
     auto pick_plan = [&]() -> int {
         best = 0.f;
         seen.clear();
@@ -292,7 +311,27 @@ static int plan_step2(gpf_handle* h, int D) {
             }
             if ((env_chunks && std::atoi(env_chunks) > 0) || one_per_simd == all_resident) break;
         }
-        return plan_apply(h, best_chunks, best_nt);
+        // the keep-set on the plan just chosen (k = 0 is the figure above)
+        best_keep = 0;
+        keep_seen.clear();
+        if (best_nt >= 1) {
+            if (env_keep) best_keep = keep;
+            else if (nt_possible) {
+                char buf[48];
+                std::snprintf(buf, sizeof buf, " 0 %.0f", best);
+                keep_seen = buf;
+                float best_k = best;
+                for (int k : K2_KEEP_CANDIDATES) {
+                    GPF_TRY(plan_apply(h, best_chunks, best_nt, k));
+                    float us = 0.f;
+                    GPF_TRY(plan_trial(h, D, &us, 6, true));
+                    std::snprintf(buf, sizeof buf, ", %d %.0f", k, us);
+                    keep_seen += buf;
+                    if (us < best_k) { best_k = us; best_keep = k; }
+                }
+            }
+        }
+        return plan_apply(h, best_chunks, best_nt, best_keep);
     };
     // the plan on the memory the handle has, the memory under that plan (which pages are good depends on how many streams run),
     // the plan once more on the memory kept
@@ -315,9 +354,11 @@ static int plan_step2(gpf_handle* h, int D) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     field_free(h->plan_master);
     h->plan_master = nullptr;
-    GPF_TRY(plan_apply(h, best_chunks, best_nt));
-    std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s (timed, us:%s;%s%s%s)", h->nchunks2,
-                  NT_NAME[h->nt_policy2], seen.c_str(), placement_note.c_str(),
+    GPF_TRY(plan_apply(h, best_chunks, best_nt, best_keep));
+    const std::string kept = keep_note(h) + (keep_seen.empty() ? (env_keep && h->nt_policy2 >= 1 ? " (pinned by the environment)" : "")
+                                                               : " (timed, us: k" + keep_seen + ")");
+    std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s%s (timed, us:%s;%s%s%s)", h->nchunks2,
+                  NT_NAME[h->nt_policy2], kept.c_str(), seen.c_str(), placement_note.c_str(),
                   placement_note.empty() ? "" : "; before the placement:", placement_note.empty() ? "" : first_seen.c_str());
     DBG("plan_step2: %s", h->plan2_note);
     h->plan2_valid = true;

@@ -90,7 +90,8 @@ struct Step2Args {
     LogEntry* log; long long log_base, log_cap;
     Layout L; Edges E; Strip2Geom G;
     int nchunks;
-    int fused;                              // bit 0: edge work inside this kernel; bit 1: non-temporal stores, bit 2: non-temporal loads (plan_step2)
+    int fused;                              // bit 0: edge work inside this kernel; bit 1: non-temporal stores, bit 2: non-temporal loads,
+                                            // bits 3-5: k, rows with (ix & 7) < k stored plain to stay in the Infinity Cache (plan_step2)
     int honor_stop;
 };
 
@@ -581,6 +582,9 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
                 }
                 const int ixo = D > 0 ? n - 1 : L.Nx + 2 - n;
                 const long long rbo = (long long)ixo * L.pitch;     // wave-uniform
+#if GPF_K2_NT & 2
+                const bool store_nt = (policy & 2) && (ixo & 7) >= ((policy >> 3) & 7);     // wave-uniform
+#endif
                 auto st16 = [&](double* __restrict__ rowp, double va, double vb) {
                     dpair v;
                     v.x = D > 0 ? va : vb; v.y = D > 0 ? vb : va;
@@ -590,9 +594,20 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
                     // 8-GPU run, 2 x 50 MB -- finds its previous output still on the die.)  The hinted store is written in asm:
                     // given `if (nt) __builtin_nontemporal_store(v, p); else *p = v;` hipcc sinks the two stores into one and
                     // drops the hint -- the library of the first half of round 3 held no `nt` store at all (llvm-objdump).
-                    // s_nop: a store of more than 8 bytes must not be followed at once by a write of its data registers.
-                    if (policy & 2) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 0" :: "v"(p), "v"(v) : "memory");
-                    else *p = v;
+                    // The keep-set: where the plan asks for it (bits 3-5 of the policy word: k), rows with (ix & 7) < k are stored plain
+                    // instead -- they allocate in the Infinity Cache, and the next step's `nt` loads find them there (`nt` traffic
+                    // neither allocates there nor displaces what does: tools/mall_keep_probe.hip, profiles/r04_keep/).  Write-through
+                    // `sc1` stores would keep L2 clean as well, but here they made the step 1.8x slower (k = 4; why is not measured --
+                    // the exact vmcnt waits below count stores too, and a write-through store may count until the far side has
+                    // taken it).  Both forms sit in ONE statement, the choice a scalar branch inside it, so that hipcc cannot merge
+                    // them; a row still issues exactly three stores.  (readfirstlane at the operand: computed earlier, the flag ends
+                    // up in a VGPR in some instantiations.)  s_nop: a store of more than 8 bytes must not be followed at once by a
+                    // write of its data registers.
+                    asm volatile("s_cmp_lg_u32 %[nt], 0\n\ts_cbranch_scc1 .Lgpf_stnt_%=\n\t"
+                                 "global_store_dwordx4 %0, %1, off\n\ts_branch .Lgpf_stdone_%=\n"
+                                 ".Lgpf_stnt_%=:\n\tglobal_store_dwordx4 %0, %1, off nt\n"
+                                 ".Lgpf_stdone_%=:\n\ts_nop 0"
+                                 :: "v"(p), "v"(v), [nt] "s"(__builtin_amdgcn_readfirstlane(store_nt ? 1 : 0)) : "memory", "scc");
 #else
                     *p = v;
 #endif
