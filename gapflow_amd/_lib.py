@@ -33,6 +33,9 @@ BC_P, BC_D, BC_N = 0, 1, 2
 FIELD_Q, FIELD_TOPO, FIELD_EXTRA, FIELD_PRESSURE, FIELD_TAU_AVG, FIELD_WALL_LOWER, FIELD_WALL_UPPER = range(7)
 FIELD_PRESSURE_VAR, FIELD_WALL_XZ_VAR, FIELD_WALL_YZ_VAR = 7, 8, 9
 FIELD_DEFORMATION = 10
+PROFILE_Z, PROFILE_U, PROFILE_V, PROFILE_TAU = 1, 2, 4, 8          # gpf_gap_profiles field_mask bits
+PROFILE_GRADIENTS = 1
+PROFILE_MODES = {'both': 0, 'top': 1, 'bottom': 2, 'none': 3}
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -120,6 +123,10 @@ SIGNATURES = {
     'gpf_gp_nll_open': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _DP, _DP, C.c_double, C.POINTER(C.c_void_p)]),
     'gpf_gp_nll_eval': (C.c_int, [C.c_void_p, _DP, _DP, _DP, C.POINTER(C.c_int)]),
     'gpf_gp_nll_close': (C.c_int, [C.c_void_p]),
+    'gpf_gap_profiles_op': (C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                                                              C.c_void_p]),
+    'gpf_gap_profiles': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'gpf_profile_store_probe': (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _DP]),
 }
 
 _lib = None

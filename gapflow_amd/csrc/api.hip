@@ -19,6 +19,7 @@
 #include "gp_kernels.hip"
 #include "elastic_kernels.hip"
 #include "small_kernel.hip"
+#include "profile_kernels.hip"
 
 using namespace gpf;
 
@@ -959,3 +960,4 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
 #include "api_stagewise.inc"
 #include "api_slab_stagewise.inc"
 #include "api_slab_elastic.inc"
+#include "api_profiles.inc"

@@ -582,4 +582,56 @@ GPF_HD void cell_fields(const CellIn& c, const Phys& P, CellFields& o, double et
     o.lower[4] = 2.0 * eta * (a3 * c.jx - a2 * Urho) / den;
 }
 
+// ---- through-gap profiles (models/profiles.py: get_velocity_profiles, get_stress_profiles) ------------------------
+// The slip parabola of viscous_general evaluated at an arbitrary z instead of at the walls or on average.  Everything
+// that depends on the cell only is folded once into coefficients of a polynomial in z,
+//     u(z) = (a z + b) z + c,   du/dx(z) = (ah hx + am mux) z^2 + (bh hx + bm mux) z + (ch hx + cm mux),   ...
+// and the Newtonian combinations (v1, v2, eta) are applied to the coefficients, so one level costs two FMAs per output
+// (one for the linear tau_yz, tau_xz).  profiles.py's modes as (lo, hi): both (Ls, Ls), top (0, Ls), bottom (Ls, 0),
+// none (0, 0).  Outputs in the order u, v, then tau in Voigt order xx, yy, zz, yz, xz, xy (profiles.py:138, 1323).
+enum { PROFILE_BOTH = 0, PROFILE_TOP = 1, PROFILE_BOTTOM = 2, PROFILE_NONE = 3 };
+
+GPF_HD void profile_slip(int mode, double Ls, double& lo, double& hi) {
+    lo = (mode == PROFILE_BOTH || mode == PROFILE_BOTTOM) ? Ls : 0.0;
+    hi = (mode == PROFILE_BOTH || mode == PROFILE_TOP) ? Ls : 0.0;
+}
+
+struct ProfileCoef {
+    double u[3], v[3];      // z^2, z, 1
+    double t[6][3];         // xx, yy, zz, yz, xz, xy: z^2, z, 1 (yz and xz have no z^2 term)
+};
+
+GPF_HD void profile_coefficients(const double q[3], const double hh[3], const double dqx[3], const double dqy[3],
+                                 double U, double V, double eta, double zeta, double lo, double hi, ProfileCoef& o) {
+    const double h = hh[0], irho = 1.0 / q[0];
+    const double mu = q[1] * irho, mv = q[2] * irho;
+    const Parabola pu = slip_parabola(h, U, mu, lo, hi), pv = slip_parabola(h, V, mv, lo, hi);
+    const double mux = (dqx[1] - mu * dqx[0]) * irho, muy = (dqy[1] - mu * dqy[0]) * irho;
+    const double mvx = (dqx[2] - mv * dqx[0]) * irho, mvy = (dqy[2] - mv * dqy[0]) * irho;
+    const double ux[3] = {pu.ah * hh[1] + pu.am * mux, pu.bh * hh[1] + pu.bm * mux, pu.ch * hh[1] + pu.cm * mux};
+    const double uy[3] = {pu.ah * hh[2] + pu.am * muy, pu.bh * hh[2] + pu.bm * muy, pu.ch * hh[2] + pu.cm * muy};
+    const double vx[3] = {pv.ah * hh[1] + pv.am * mvx, pv.bh * hh[1] + pv.bm * mvx, pv.ch * hh[1] + pv.cm * mvx};
+    const double vy[3] = {pv.ah * hh[2] + pv.am * mvy, pv.bh * hh[2] + pv.bm * mvy, pv.ch * hh[2] + pv.cm * mvy};
+    const double v1 = zeta + (4.0 / 3.0) * eta, v2 = zeta - (2.0 / 3.0) * eta;
+    o.u[0] = pu.a; o.u[1] = pu.b; o.u[2] = pu.c;
+    o.v[0] = pv.a; o.v[1] = pv.b; o.v[2] = pv.c;
+    for (int k = 0; k < 3; ++k) {
+        o.t[0][k] = v1 * ux[k] + v2 * vy[k];
+        o.t[1][k] = v2 * ux[k] + v1 * vy[k];
+        o.t[2][k] = v2 * (ux[k] + vy[k]);
+        o.t[5][k] = eta * (uy[k] + vx[k]);
+    }
+    o.t[3][0] = 0.0; o.t[3][1] = 2.0 * eta * pv.a; o.t[3][2] = eta * pv.b;        // eta dv/dz = eta (2 a z + b)
+    o.t[4][0] = 0.0; o.t[4][1] = 2.0 * eta * pu.a; o.t[4][2] = eta * pu.b;
+}
+
+GPF_HD double profile_horner(const double c[3], double z) { return fma(fma(c[0], z, c[1]), z, c[2]); }
+
+// out: u, v, xx, yy, zz, yz, xz, xy at height z
+GPF_HD void profile_at(const ProfileCoef& c, double z, double out[8]) {
+    out[0] = profile_horner(c.u, z);
+    out[1] = profile_horner(c.v, z);
+    for (int k = 0; k < 6; ++k) out[2 + k] = (k == 3 || k == 4) ? fma(c.t[k][1], z, c.t[k][2]) : profile_horner(c.t[k], z);
+}
+
 }  // namespace gpf

@@ -16,7 +16,7 @@ import ctypes as C
 import io as _io
 import os
 import signal
-from collections import deque
+from collections import deque, namedtuple
 from datetime import datetime
 
 import numpy as np
@@ -26,6 +26,9 @@ from . import __version__
 from .io import read_yaml_input, write_yaml, create_output_directory, history_to_csv
 from .topography import Topography
 from .stress import Pressure, WallStress, BulkStress
+
+GapProfiles = namedtuple('GapProfiles', 'z u v tau')
+GapProfiles.__doc__ = """Through-gap profiles of Problem.gap_profiles: z, u, v (nz, nrows, Ny+2), tau (6, nz, nrows, Ny+2); None if not asked for."""
 
 
 def _termination_signals():
@@ -509,6 +512,49 @@ class Problem:
                 history_to_csv(os.path.join(self.outdir, f'gp_{name}.csv'), m.history)
                 with open(os.path.join(self.outdir, f'gp_{name}.txt'), 'w') as f:
                     print(m, file=f)
+
+    def gap_profiles(self, nz=32, rows=None, fields=('z', 'u', 'v', 'tau'), gradients=False):
+        """Velocity and viscous stress across the film of the current state (models/profiles.py on the whole field).
+
+        Evaluates the state ``q`` holds (not the corrector-stage closures of ``wall_stress_*``) on the gap ``topo`` holds
+        (deformed, for an elastic gap), at nz levels z_k = h k / (nz - 1) per cell, with the solver's closure branch: slip
+        at the upper wall with the slip-length field, the closures' shear viscosity (piezo-viscosity included) and
+        zeta = prop['bulk'].  grad q enters only with ``gradients=True`` (np.gradient over the ghosted field / dx, dy).
+        ``rows``: a slice of the ghosted x index (default: all Nx + 2).  Returns GapProfiles(z, u, v, tau) with z, u, v of
+        shape (nz, nrows, Ny + 2) and tau (6, nz, nrows, Ny + 2) in Voigt order; fields not asked for are None.  Reads only:
+        q, the run state and later steps are unchanged."""
+        if self._gp_models:
+            raise NotImplementedError("gap_profiles: surrogate (GP) closures have no through-gap profile")
+        if self._cfg.thinning:
+            raise NotImplementedError("gap_profiles: shear thinning needs grad p, which the profile does not model")
+        if isinstance(nz, bool) or not isinstance(nz, (int, np.integer)) or nz < 2:
+            raise ValueError(f"gap_profiles: nz must be an integer >= 2, got {nz!r}")
+        nxg, nyg = self._shape
+        rows = slice(None) if rows is None else rows
+        if not isinstance(rows, slice) or rows.step not in (None, 1):
+            raise ValueError("gap_profiles: rows must be a slice of the ghosted x index with step 1")
+        ix0 = 0 if rows.start is None else rows.start
+        ix1 = nxg if rows.stop is None else rows.stop
+        if not (0 <= ix0 < ix1 <= nxg):
+            raise ValueError(f"gap_profiles: rows {ix0}:{ix1} outside 0:{nxg} or empty")
+        fields = (fields,) if isinstance(fields, str) else tuple(fields)
+        bits = {'z': _lib.PROFILE_Z, 'u': _lib.PROFILE_U, 'v': _lib.PROFILE_V, 'tau': _lib.PROFILE_TAU}
+        if not fields or any(f not in bits for f in fields):
+            raise ValueError(f"gap_profiles: fields must be taken from {tuple(bits)}, got {fields!r}")
+        mask = 0
+        for f in fields:
+            mask |= bits[f]
+        self._sync_to_device()
+        names = [f for f in ('z', 'u', 'v', 'tau') if mask & bits[f]]
+        nplanes = sum(6 if f == 'tau' else 1 for f in names)
+        out = np.empty((nplanes, int(nz), ix1 - ix0, nyg))
+        _lib.check(self._lib.gpf_gap_profiles(self._h, int(nz), ix0, ix1, mask, _lib.PROFILE_GRADIENTS if gradients else 0,
+                                              out.ctypes.data_as(C.c_void_p)))
+        res, k = {}, 0
+        for f in names:
+            res[f] = out[k:k + 6] if f == 'tau' else out[k]
+            k += 6 if f == 'tau' else 1
+        return GapProfiles(res.get('z'), res.get('u'), res.get('v'), res.get('tau'))
 
     def write(self, scalars=True, fields=True, params=True):
         # problem.py:616-637

@@ -410,6 +410,11 @@ class _DomainFeatures:
 class SlabProblem:
     """A Problem cut into x-slabs; construct it on every rank of an initialised process group."""
 
+    def gap_profiles(self, *args, **kwargs):
+        """Through-gap profiles are not evaluated on x-slabs: gather the state and use Problem.gap_profiles or
+        gapflow_amd.models.profiles on it."""
+        raise NotImplementedError("gap_profiles: not available on a SlabProblem")
+
     def __init__(self, input_dict, device=0, dist=None):
         import torch
         if dist is None:

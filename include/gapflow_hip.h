@@ -332,6 +332,37 @@ int gpf_gp_nll_open(int device, int n, int d, int m, const double* Xn, const dou
 int gpf_gp_nll_eval(gpf_nll* s, const double* theta, double* value, double* grad, int* info);
 int gpf_gp_nll_close(gpf_nll* s);
 
+/* ---- through-gap profiles: GaPFlow/models/profiles.py ------------------------------------------------------------ */
+/* field_mask bits of both entry points; output planes come in this order, only the selected ones */
+enum {
+    GPF_PROFILE_Z = 1,        /* z of every level (problem form; the operator echoes its input) */
+    GPF_PROFILE_U = 2,        /* u(z) */
+    GPF_PROFILE_V = 4,        /* v(z) */
+    GPF_PROFILE_TAU = 8       /* 6 planes: viscous stress in Voigt order xx, yy, zz, yz, xz, xy */
+};
+enum { GPF_PROFILE_GRADIENTS = 1 };                 /* gpf_gap_profiles flags: include grad q (np.gradient stencil) */
+enum { GPF_PROFILE_BOTH = 0, GPF_PROFILE_TOP = 1, GPF_PROFILE_BOTTOM = 2, GPF_PROFILE_NONE = 3 };     /* slip modes */
+/* get_velocity_profiles / get_stress_profiles (models/profiles.py:33-138, 141-1323) for n cells x nz levels.  Bit b of
+ * per_cell set: input b holds one value per cell ([comp][n]), else one value for all; bits 0 q, 1 hh (h, dh/dx, dh/dy),
+ * 2 dqx, 3 dqy, 4 eta, 5 zeta, 6 Ls, 7 z ([nz][n], else [nz]).  hh NULL: the gap height is each cell's last z and the slopes
+ * are zero (get_velocity_profiles takes h = z[-1], profiles.py:58); dqx / dqy NULL: zero gradients.  mode: GPF_PROFILE_*
+ * slip mode (both: both walls slip with Ls, top / bottom: that wall only, none: no slip).  out: [plane][nz][n] for the
+ * planes of field_mask.  The slip parabola of gpf_viscous_stress, evaluated at z (csrc/closures.hpp profile_coefficients). */
+int gpf_gap_profiles_op(int64_t n, int nz, const double* z, const double* q, const double* hh, const double* dqx,
+                        const double* dqy, const double* eta, const double* zeta, const double* Ls, int per_cell,
+                        double U, double V, int mode, int field_mask, double* out);
+/* The same on the handle's current state (the q that gpf_download returns), the gap planes of GPF_FIELD_TOPO (deformed h
+ * on an elastic problem) and the slip length field: ghosted rows [ix0, ix1), levels z_k = h k / (nz - 1), slip at the
+ * upper wall only and the closures' shear viscosity (the branch stress.py:328-345 uses), zeta = the bulk viscosity.  flags
+ * GPF_PROFILE_GRADIENTS: grad q by np.gradient over the ghosted field divided by dx, dy.  host_out: [plane][nz][ix1-ix0][Ny+2].
+ * Runs on the handle's stream through a device scratch of GPF_PROFILE_SCRATCH_MB MiB (default 256) with double-buffered
+ * copies to the host; reads only (the state, the step count and later steps are unchanged).  Refused: shear thinning,
+ * surrogate closures, x-slab handles (no reference counterpart: profiles.py is a function of arrays). */
+int gpf_gap_profiles(gpf_handle* h, int nz, int ix0, int ix1, int field_mask, int flags, double* host_out);
+/* Diagnostic: time of one launch of a store-only kernel on k_gap_profiles' grid and store pattern, writing nplanes planes
+ * of ncell x nlev doubles (tools/profile_time.py; no reference counterpart). */
+int gpf_profile_store_probe(int device, int64_t ncell, int nlev, int nplanes, int reps, double* ms_per_pass);
+
 /* Diagnostic: time of one pass of an elementwise kernel that reads `nin` and writes `nout` fp64 planes of
  * `doubles_per_plane` elements (16 bytes per lane, grid-stride): what THIS device streams for the byte count of a fused
  * step.  bench.py reports it beside the step kernel's HBM figure (no reference counterpart: the reference has no device). */
