@@ -65,6 +65,8 @@ struct gpf_handle {
     double* q[2] = {nullptr, nullptr};      // ping-pong, 3 planes each
     double* topo = nullptr;                 // 3 planes
     double* topo_line = nullptr;            // [3][max(Nx,Ny)+2]: the profile when the topography varies along one axis only
+    RowCoef* rowcoef = nullptr;             // x-only gap: closure coefficients per row ix = 0 .. Nx+1, then [2 edges][2] seam records (build_rowcoef)
+    bool rowcoef_table = true;              // GPF_ROWCOEF_TABLE=0 at gpf_create: k_step2 evaluates the coefficients itself (TOPO 3 instead of 4)
     int topo_mode = 0;                      // 0: 2-D planes, 1: function of ix only, 2: function of iy only
     bool topo_hy0 = false;                  // topo_mode 1 and dh/dy == 0 in every row
     double* Ls = nullptr;                   // 1 plane (allocated on first non-zero upload)
@@ -262,6 +264,7 @@ extern "C" int gpf_create(const gpf_config* cfg, gpf_handle** out) {
     }
     h->E.halo[0] = cfg->halo_lo; h->E.halo[1] = cfg->halo_hi;
     h->split_edges = std::getenv("GPF_STEP_UNFUSED_EDGES") != nullptr;
+    if (const char* s = std::getenv("GPF_ROWCOEF_TABLE")) h->rowcoef_table = std::atoi(s) != 0;
     h->gp_reuse_state_mean = std::getenv("GPF_GP_NO_STATE_MEAN") == nullptr;
     make_phys(*cfg, h->P);
 
@@ -306,7 +309,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->topo_line, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -368,6 +371,27 @@ static int ensure_fields(gpf_handle* h) {
     return GPF_OK;
 }
 
+// The row-coefficient table of an x-only gap (k_step2, TOPO 4): `rows` -- the records of rows 0 .. Nx+1 from the profile in
+// topo_line; `side` 0 / 1 -- the two records behind them for that periodic seam edge, from the seam's topography rows (the far
+// slab's row 1, then its row 0, as k_step2's prologue uses them).  Rebuilt whenever either source is uploaded.
+static int build_rowcoef(gpf_handle* h, bool rows, int side) {
+    const Layout& L = h->L;
+    const int n = L.Nx + 2;
+    if (!h->rowcoef) {
+        HIP_TRY(hipMalloc(&h->rowcoef, (size_t)(n + 4) * sizeof(RowCoef)));
+        HIP_TRY(hipMemsetAsync(h->rowcoef, 0, (size_t)(n + 4) * sizeof(RowCoef), h->stream));
+    }
+    if (rows)
+        hipLaunchKernelGGL(k_row_coef_table, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const double*)h->topo_line,
+                           (const double*)h->topo_line + n, 1ll, n, h->P, h->rowcoef);
+    if (side >= 0 && h->seam) {
+        const double* t = h->seam + (size_t)side * 8 * L.pitch + L.off + 1;
+        hipLaunchKernelGGL(k_row_coef_table, dim3(1), dim3(64), 0, h->stream, t, t + L.pitch, 4ll * L.pitch, 2, h->P, h->rowcoef + n + 2 * side);
+    }
+    HIP_TRY(hipGetLastError());
+    return GPF_OK;
+}
+
 extern "C" int gpf_upload(gpf_handle* h, int field, const double* host, size_t count) {
     if (!h || !host) return fail(GPF_ERR_INVALID, "gpf_upload: null argument");
     GPF_TRY(enter(h));
@@ -420,6 +444,12 @@ extern "C" int gpf_upload(gpf_handle* h, int field, const double* host, size_t c
             h->topo_hy0 = hy0;
             if (!h->topo_line) HIP_TRY(hipMalloc(&h->topo_line, (size_t)3 * (std::max(nx, ny)) * sizeof(double)));
             HIP_TRY(hipMemcpy(h->topo_line, line.data(), line.size() * sizeof(double), hipMemcpyHostToDevice));
+            if (hy0 && h->rowcoef_table) {
+                const bool fresh = h->rowcoef == nullptr;
+                GPF_TRY(build_rowcoef(h, true, -1));
+                for (int e = 0; e < 2 && fresh; ++e)
+                    if (h->has_seam[e]) GPF_TRY(build_rowcoef(h, false, e));
+            }
         }
     }
     GPF_TRY(ensure_stage(h, count));
@@ -672,10 +702,41 @@ extern "C" int gpf_pre_run(gpf_handle* h) {
 // 0 planes, 1 profile over ix, 2 profile over iy, 3 profile over ix with dh/dy = 0 (the x-only-gap closure); the line
 // modes only without slip-length field / piezo-viscosity.  GPF_TOPO_PLANES / GPF_TOPO_GENERIC switch the specialisations
 // off for A/B runs.
+// 4 is 3 with the rows' closure coefficients read from the handle's table (GPF_ROWCOEF_TABLE=0 at gpf_create: 3).
 static int topo_mode_of(const gpf_handle* h) {
     if (h->Ls != nullptr || h->cfg.piezo != 0 || std::getenv("GPF_TOPO_PLANES")) return 0;
-    if (h->topo_mode == 1 && h->topo_hy0 && !std::getenv("GPF_TOPO_GENERIC")) return 3;
+    if (h->topo_mode == 1 && h->topo_hy0 && !std::getenv("GPF_TOPO_GENERIC")) return (h->rowcoef_table && h->rowcoef) ? 4 : 3;
     return h->topo_mode;
+}
+static bool topo_xonly(const gpf_handle* h) { return topo_mode_of(h) >= 3; }
+
+extern "C" int gpf_row_coefficients(gpf_handle* h, int source, double* host, size_t count) {
+    if (!h || !host || source < 0 || source > 1) return fail(GPF_ERR_INVALID, "gpf_row_coefficients: bad argument");
+    const Layout& L = h->L;
+    const int n = L.Nx + 2;
+    if (count != (size_t)8 * (n + 4)) return fail(GPF_ERR_INVALID, "gpf_row_coefficients: count must be 8*(Nx+2+4)");
+    if (topo_mode_of(h) != 4) return fail(GPF_ERR_STATE, "gpf_row_coefficients: this handle's step does not read a row-coefficient table");
+    GPF_TRY(enter(h, true));
+    const RowCoef* src = h->rowcoef;
+    RowCoef* fresh = nullptr;
+    if (source == 1) {
+        HIP_TRY(hipMalloc(&fresh, (size_t)(n + 4) * sizeof(RowCoef)));
+        HIP_TRY(hipMemsetAsync(fresh, 0, (size_t)(n + 4) * sizeof(RowCoef), h->stream));
+        const double* col = h->topo + L.off + 1;
+        hipLaunchKernelGGL(k_row_coef_table, dim3((n + 255) / 256), dim3(256), 0, h->stream, col, col + L.plane, (long long)L.pitch, n, h->P, fresh);
+        for (int e = 0; e < 2; ++e) {
+            if (!h->has_seam[e]) continue;
+            const double* t = h->seam + (size_t)e * 8 * L.pitch + L.off + 1;
+            hipLaunchKernelGGL(k_row_coef_table, dim3(1), dim3(64), 0, h->stream, t, t + L.pitch, 4ll * L.pitch, 2, h->P, fresh + n + 2 * e);
+        }
+        src = fresh;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host, src, count * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (fresh) hipFree(fresh);
+    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_row_coefficients: ") + hipGetErrorString(e));
+    return GPF_OK;
 }
 
 // ---- two-columns-per-lane step kernel (step2_kernel.hip) ----
@@ -695,6 +756,8 @@ static step2_kernel_t step2_kernel(int eos, bool has_ls, bool piezo, int D, int 
             k = D > 0 ? k_step2<EOS_, false, false, 1, 2> : k_step2<EOS_, false, false, -1, 2>;
         } else if (topo_mode == 3) {
             k = D > 0 ? k_step2<EOS_, false, false, 1, 3> : k_step2<EOS_, false, false, -1, 3>;
+        } else if (topo_mode == 4) {
+            k = D > 0 ? k_step2<EOS_, false, false, 1, 4> : k_step2<EOS_, false, false, -1, 4>;
         } else {
             k = D > 0 ? k_step2<EOS_, false, false, 1, 0> : k_step2<EOS_, false, false, -1, 0>;
         }
@@ -765,6 +828,7 @@ static void fill_step2_args(gpf_handle* h, Step2Args& a2, int D, int honor_stop,
     const bool fused = step2_fused(h);
     const Strip2Geom& G2 = h->geom2[D > 0 ? 0 : 1];
     a2.qa = h->q[0]; a2.qb = h->q[1]; a2.topo = h->topo; a2.topo_line = h->topo_line; a2.Ls = h->Ls;
+    a2.rowcoef = h->rowcoef;
     a2.g1x = h->g1; a2.g1y = h->g1 + 3 * L.pitch;
     a2.st = h->st; a2.partials = h->partials; a2.block_partials = h->block_partials; a2.arrive = h->arrive;
     a2.log = h->log; a2.log_base = log_base; a2.log_cap = h->log_cap;
@@ -837,7 +901,7 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
     }
     EOS_DISPATCH(h->cfg.eos, {
         if (!h->g1_ready) {
-            if (topo_mode_of(h) == 3) hipLaunchKernelGGL((k_ghost_stage1<EOS_, false, false, true>), ggrid, dim3(256), 0, h->stream, g, h->P);
+            if (topo_xonly(h)) hipLaunchKernelGGL((k_ghost_stage1<EOS_, false, false, true>), ggrid, dim3(256), 0, h->stream, g, h->P);
             else LS_PIEZO_DISPATCH(has_ls, h->cfg.piezo != 0, hipLaunchKernelGGL((k_ghost_stage1<EOS_, LS_, PZ_, false>), ggrid, dim3(256), 0, h->stream, g, h->P));
         }
         if (ev0) hipEventRecord(ev0, h->stream);
@@ -845,7 +909,7 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
         if (ev1) hipEventRecord(ev1, h->stream);
         hipLaunchKernelGGL((k_ghost_fill<EOS_>), dim3(h->nghost_blocks + nsend), dim3(256), 0, h->stream, gf, f, h->nghost_blocks, h->P);
         if (p2p) {                          // wait for the peers, commit, stage-1 ghost data of the next step
-            if (topo_mode_of(h) == 3) hipLaunchKernelGGL((k_begin_slab<EOS_, false, false, true, true>), ggrid, dim3(256), 0, h->stream, g, w, h->P);
+            if (topo_xonly(h)) hipLaunchKernelGGL((k_begin_slab<EOS_, false, false, true, true>), ggrid, dim3(256), 0, h->stream, g, w, h->P);
             else LS_PIEZO_DISPATCH(has_ls, h->cfg.piezo != 0, hipLaunchKernelGGL((k_begin_slab<EOS_, LS_, PZ_, false, true>), ggrid, dim3(256), 0, h->stream, g, w, h->P));
         }
     });

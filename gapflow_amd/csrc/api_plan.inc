@@ -237,6 +237,11 @@ static std::string keep_note(const gpf_handle* h) {
     std::snprintf(buf, sizeof buf, ", keep %d/8 rows on-die", h->keep_rows2);
     return buf;
 }
+// where an x-only-gap kernel takes its row coefficients from: the handle's table (TOPO 4), or its own arithmetic (GPF_ROWCOEF_TABLE=0)
+static const char* coef_note(const gpf_handle* h) {
+    const int topo = topo_mode_of(h);
+    return topo == 4 ? ", row coefficients from the table" : topo == 3 ? ", row coefficients evaluated in the kernel" : "";
+}
 static int plan_step2(gpf_handle* h, int D) {
     if (h->plan2_valid) return GPF_OK;
     const Layout& L = h->L;
@@ -269,8 +274,8 @@ static int plan_step2(gpf_handle* h, int D) {
                       one_per_simd >= 1 && L.Nx / one_per_simd >= 16 && !(env_chunks && env_nt);
     if (!tune) {
         GPF_TRY(plan_apply(h, nchunks, nt, keep));
-        std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s%s (rule of thumb%s)", h->nchunks2,
-                      NT_NAME[h->nt_policy2], keep_note(h).c_str(), (env_chunks || env_nt || env_keep) ? ", pinned by the environment" : "");
+        std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s%s%s (rule of thumb%s)", h->nchunks2,
+                      NT_NAME[h->nt_policy2], coef_note(h), keep_note(h).c_str(), (env_chunks || env_nt || env_keep) ? ", pinned by the environment" : "");
         h->plan2_valid = true;
         return GPF_OK;
     }
@@ -357,8 +362,8 @@ static int plan_step2(gpf_handle* h, int D) {
     GPF_TRY(plan_apply(h, best_chunks, best_nt, best_keep));
     const std::string kept = keep_note(h) + (keep_seen.empty() ? (env_keep && h->nt_policy2 >= 1 ? " (pinned by the environment)" : "")
                                                                : " (timed, us: k" + keep_seen + ")");
-    std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s%s (timed, us:%s;%s%s%s)", h->nchunks2,
-                  NT_NAME[h->nt_policy2], kept.c_str(), seen.c_str(), placement_note.c_str(),
+    std::snprintf(h->plan2_note, sizeof h->plan2_note, "%d chunks per strip, %s%s%s (timed, us:%s;%s%s%s)", h->nchunks2,
+                  NT_NAME[h->nt_policy2], coef_note(h), kept.c_str(), seen.c_str(), placement_note.c_str(),
                   placement_note.empty() ? "" : "; before the placement:", placement_note.empty() ? "" : first_seen.c_str());
     DBG("plan_step2: %s", h->plan2_note);
     h->plan2_valid = true;

@@ -65,7 +65,7 @@ extern "C" int gpf_step_commit(gpf_handle* h, int honor_stop, const void* gather
     const dim3 ggrid(fused ? SLAB_COMMIT_BLOCKS : std::min((L.Nx + L.Ny + 63) / 64, 512));
     EOS_DISPATCH(h->cfg.eos, {
         if (fused) hipLaunchKernelGGL((k_begin_slab<EOS_, false, false, false, false>), ggrid, dim3(256), 0, h->stream, g, w, h->P);
-        else if (topo_mode_of(h) == 3) hipLaunchKernelGGL((k_begin_slab<EOS_, false, false, true, false>), ggrid, dim3(256), 0, h->stream, g, w, h->P);
+        else if (topo_xonly(h)) hipLaunchKernelGGL((k_begin_slab<EOS_, false, false, true, false>), ggrid, dim3(256), 0, h->stream, g, w, h->P);
         else LS_PIEZO_DISPATCH(h->Ls != nullptr, h->cfg.piezo != 0, hipLaunchKernelGGL((k_begin_slab<EOS_, LS_, PZ_, false, false>), ggrid, dim3(256), 0, h->stream, g, w, h->P));
     });
     HIP_TRY(hipGetLastError());

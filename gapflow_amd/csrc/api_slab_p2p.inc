@@ -91,5 +91,9 @@ extern "C" int gpf_set_seam_topo(gpf_handle* h, int side, const double* host, si
         for (int iy = 0; iy < L.Ny + 2; ++iy) tmp[(size_t)r * L.pitch + L.off + iy] = host[(size_t)r * (L.Ny + 2) + iy];
     HIP_TRY(hipMemcpy(h->seam + (size_t)side * 8 * L.pitch, tmp.data(), tmp.size() * sizeof(double), hipMemcpyHostToDevice));
     h->has_seam[side] = true;
+    if (h->rowcoef) {
+        GPF_TRY(build_rowcoef(h, false, side));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
     return GPF_OK;
 }

@@ -790,6 +790,16 @@ __global__ __launch_bounds__(256) void k_average(double* q, const double* q0, La
     }
 }
 
+// The closure coefficients of `count` rows of an x-only gap (closures.hpp, row_coefficients), one 64-byte record each: row i's gap
+// and slope are h[i * stride], hx[i * stride].  k_step2's TOPO 4 form reads the records instead of evaluating them on every row of
+// every step; the device function is the one the march of TOPO 3 calls, so the records hold its values bit for bit (the host's
+// reciprocal rounds differently: the table is never built there).
+__global__ void k_row_coef_table(const double* __restrict__ h, const double* __restrict__ hx, long long stride, int count, Phys P,
+                                 RowCoef* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = row_coefficients(h[i * stride], hx[i * stride], P);
+}
+
 __global__ void k_copy3(const double* src, double* dst, long long n) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         dst[i] = src[i];

@@ -78,6 +78,7 @@ struct Strip2Geom {
 struct Step2Args {
     const double* qa; const double* qb;
     const double* topo; const double* topo_line; const double* Ls;
+    const RowCoef* rowcoef;                 // TOPO 4: one record per row ix = 0 .. Nx+1, then two per periodic seam edge (k_row_coef_table)
     const double* g1x; const double* g1y;   // fused = 0: stage-1 ghost data prepared by k_ghost_stage1 / k_begin_slab
     const double* seam[2];                  // topography rows across a periodic slab seam (gpf_set_seam_topo), per x edge
     double* out;                            // slab: the rank's 8-double record goes here and nothing is committed
@@ -162,13 +163,24 @@ __device__ __forceinline__ double uniform_load(const double* p) {
     return *(cptr)(unsigned long long)p;
 }
 
+// TOPO 4: a row's closure coefficients, ONE 64-byte scalar load from the table (s_load_dwordx16, counted by lgkmcnt like the
+// profile values above -- the compiler's waits for it leave the row loads alone).
+__device__ __forceinline__ RowCoef uniform_load_coef(const RowCoef* p) {
+    typedef double d8 __attribute__((ext_vector_type(8)));
+    typedef const __attribute__((address_space(4))) d8* cptr;
+    const d8 v = *(cptr)(unsigned long long)p;
+    RowCoef r;
+    r.A = v[0]; r.B = v[1]; r.C = v[2]; r.S0 = v[3]; r.S1a = v[4]; r.S1b = v[5]; r.S2a = v[6]; r.S2b = v[7];
+    return r;
+}
+
 // one row as loaded: .x is the lower physical column of the lane's pair
 template <int TOPO, bool HAS_LS>
 struct RawRow {
     dpair q[3];
     dpair t[TOPO == 0 ? 3 : 1];     // h, hx, hy planes (TOPO = 0 only)
     dpair ls[HAS_LS ? 1 : 1];
-    double th, thx, thy;            // TOPO = 1, 3: the row's (h, hx, hy), wave-uniform
+    double th, thx, thy;            // TOPO = 1, 3: the row's (h, hx, hy), wave-uniform (TOPO = 4: unused, the gap never enters the march)
 };
 
 // two adjacent cells of one row, as one lane holds them
@@ -252,6 +264,11 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
     // step's HBM reads is then redundant.  1 = one (h, hx, hy) triple per ROW through the scalar cache, 2 = the lane's
     // two column triples stay in registers for the whole march (flipped geometries); the values are bitwise those of
     // the planes.  3 = as 1 with dh/dy = 0 throughout: the x-only-gap closure (closures.hpp, cell_closure_xonly).
+    // 4 = as 3, but the row's closure coefficients -- functions of the row's gap and of run constants only -- come from a table
+    // built once per upload of the gap by the same device function (k_row_coef_table, aux_kernels.hip) instead of being
+    // evaluated by every wave on every row of every step: bitwise the same values, a reciprocal and ~17 multiplications
+    // less per row of the march.  (GPF_ROWCOEF_TABLE=0 at gpf_create keeps form 3.)
+    constexpr bool TABLE = TOPO == 4;
     double lh[2] = {0.0, 0.0}, lhx[2] = {0.0, 0.0}, lhy[2] = {0.0, 0.0};
     if (TOPO == 2) {
         const int c0 = min(max(iy0, 0), L.Ny + 1), c1 = min(max(iy1, 0), L.Ny + 1);
@@ -274,6 +291,8 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
         } else if (TOPO == 1 || TOPO == 3) {
             const double th = a.topo_line[ix], thx = a.topo_line[(L.Nx + 2) + ix], thy = TOPO == 1 ? a.topo_line[2 * (L.Nx + 2) + ix] : 0.0;
             r.h[0] = r.h[1] = th; r.hx[0] = r.hx[1] = thx; r.hy[0] = r.hy[1] = thy;
+        } else if (TABLE) {
+            r.h[0] = r.h[1] = r.hx[0] = r.hx[1] = r.hy[0] = r.hy[1] = 0.0;
         } else {
             r.h[0] = lh[0]; r.h[1] = lh[1]; r.hx[0] = lhx[0]; r.hx[1] = lhx[1]; r.hy[0] = lhy[0]; r.hy[1] = lhy[1];
         }
@@ -344,7 +363,7 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
     constexpr bool HEAVY = Step2Weight<EOS, HAS_LS, PIEZO>::heavy;
     // (TOPO 1 -- a row profile with all three of h, hx, hy, reached only through GPF_TOPO_GENERIC -- keeps six scalar registers per
     // row buffer: with five buffers hipcc runs out of them)
-    constexpr int AHEAD_ROWS = PIEZO ? 1 : (TOPO == 3 ? (HEAVY ? 2 : GPF_K2_AHEAD_LINE) : GPF_K2_AHEAD);
+    constexpr int AHEAD_ROWS = PIEZO ? 1 : ((TOPO == 3 || TABLE) ? (HEAVY ? 2 : GPF_K2_AHEAD_LINE) : GPF_K2_AHEAD);
     // The stores of the rows finished in between are vector-memory operations too and sit in the same counter, in issue order:
     // once the march is AHEAD rows past its first output row, every loop body since row r's request has issued three of them
     // (a wave with at least one output lane takes at least one of the three store branches below), so the exact number of younger
@@ -386,6 +405,8 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
             o.hy[0] = D > 0 ? r.t[2].x : r.t[2].y; o.hy[1] = D > 0 ? r.t[2].y : r.t[2].x;
         } else if (TOPO == 1 || TOPO == 3) {
             o.h[0] = o.h[1] = r.th; o.hx[0] = o.hx[1] = r.thx; o.hy[0] = o.hy[1] = r.thy;
+        } else if (TABLE) {
+            o.h[0] = o.h[1] = o.hx[0] = o.hx[1] = o.hy[0] = o.hy[1] = 0.0;
         } else {
             o.h[0] = lh[0]; o.h[1] = lh[1]; o.hx[0] = lhx[0]; o.hx[1] = lhx[1]; o.hy[0] = lhy[0]; o.hy[1] = lhy[1];
         }
@@ -396,7 +417,7 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
     // Three forms of one closure: the x-only-gap form (TOPO = 3), the Ls = 0 / constant-viscosity form, the general one.
     constexpr bool LS0 = !HAS_LS && !PIEZO;
     auto closure = [&](const Row2& r, int k, const double* q, const TopoRcp& t, const GapCoef& gc, const RowCoef& rc, CellFlux& f) {
-        if (TOPO == 3) {
+        if (TOPO == 3 || TABLE) {
             cell_closure_xonly<EOS>(q ? q[0] : r.rho[k], q ? q[1] : r.jx[k], q ? q[2] : r.jy[k], rc, P, f);
         } else if (LS0) {
             cell_closure_ls0<EOS>(q ? q[0] : r.rho[k], q ? q[1] : r.jx[k], q ? q[2] : r.jy[k], gc, P, f);
@@ -427,7 +448,9 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
             load(L.Nx, r0);
             load(L.Nx + 1, r1);
             auto seam_topo = [&](const double* __restrict__ t, Row2& r) {
-                if (TOPO == 1 || TOPO == 3) {
+                if (TABLE) {
+                    r.h[0] = r.h[1] = r.hx[0] = r.hx[1] = r.hy[0] = r.hy[1] = 0.0;
+                } else if (TOPO == 1 || TOPO == 3) {
                     r.h[0] = r.h[1] = t[L.off + 1]; r.hx[0] = r.hx[1] = t[L.pitch + L.off + 1];
                     r.hy[0] = r.hy[1] = TOPO == 1 ? t[2 * L.pitch + L.off + 1] : 0.0;
                 } else {
@@ -443,8 +466,18 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
         }
         double fy[2][3], q1[2][3];
         CellFlux f0[2], f1[2];
-        const RowCoef rc0 = TOPO == 3 ? row_coefficients(r0.h[0], r0.hx[0], P) : RowCoef();
-        const RowCoef rc1 = TOPO == 3 ? row_coefficients(r1.h[0], r1.hx[0], P) : RowCoef();
+        RowCoef rc0 = RowCoef(), rc1 = RowCoef();
+        if (TOPO == 3) {
+            rc0 = row_coefficients(r0.h[0], r0.hx[0], P);
+            rc1 = row_coefficients(r1.h[0], r1.hx[0], P);
+        } else if (TABLE) {
+            // logical rows 0 and 1, or the seam edge's two records (far slab's row 1, then its row 0) behind the rows of the table
+            const bool seam = a.E.halo[e_dw_x] == 2;
+            const int i0 = seam ? L.Nx + 2 + 2 * e_dw_x + 1 : (D > 0 ? 0 : L.Nx + 1);
+            const int i1 = seam ? L.Nx + 2 + 2 * e_dw_x : (D > 0 ? 1 : L.Nx);
+            rc0 = uniform_load_coef(a.rowcoef + i0);
+            rc1 = uniform_load_coef(a.rowcoef + i1);
+        }
         for (int k = 0; k < 2; ++k) {
             closure(r0, k, nullptr, topo_rcp<HAS_LS>(cell_of(r0, k)), gap_coefficients(r0.h[k], r0.hx[k], r0.hy[k]), rc0, f0[k]);
             closure(r1, k, nullptr, topo_rcp<HAS_LS>(cell_of(r1, k)), gap_coefficients(r1.h[k], r1.hx[k], r1.hy[k]), rc1, f1[k]);
@@ -491,6 +524,19 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
     double fx1p[2][3] = {{0, 0, 0}, {0, 0, 0}};     // stage-1 x-flux of row n-1
     double part[2][3] = {{0, 0, 0}, {0, 0, 0}};     // row n-1: q(t0) + q1 - dt*(-cx*Fx2 + cy*dFy2 - S2)
 
+    // TOPO 4: the coefficients of the row about to be computed.  ONE set of scalar registers, whatever the number of row buffers:
+    // the record of row n+1 is requested at the END of row n, at one place and unconditionally -- the next row's request, its wait
+    // and the reciprocal that opens its closure cover a scalar-cache hit -- so the march holds 16 scalar registers of gap data where
+    // form 3 holds 4 per row buffer.  (Requested earlier, after the row's last closure in both branches of the first-row test,
+    // hipcc kept the coefficients in VGPRs behind 31 more v_mov_b64 per row -- the whole saving: profiles/r05_rowcoef/.)  Beyond
+    // the chunk's last row the last record is read again.
+    auto coef_of = [&](int n) {
+        const int m = min(n, n_last + 1);
+        return uniform_load_coef(a.rowcoef + (D > 0 ? m : L.Nx + 1 - m));
+    };
+    RowCoef rc_row = RowCoef();
+    if (TABLE) rc_row = coef_of(n_first - 1);
+
     // one row of the march: `raw` holds (or is about to hold) row n, `spare` is the buffer row n-1 has vacated
     auto march = [&](const int n, Raw& raw, Raw& spare) {
         // (beyond the chunk's last row `issue` sends a dummy request: the number of loads in flight behind `raw` is the
@@ -508,6 +554,8 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
         RowCoef rc = RowCoef();
         if (TOPO == 3) {
             rc = row_coefficients(cur.h[0], cur.hx[0], P);      // one set per row: the gap is the same in every column
+        } else if (TABLE) {
+            rc = rc_row;
         } else if (LS0) {
             gc[0] = gap_coefficients(cur.h[0], cur.hx[0], cur.hy[0]);   // once per cell and step: both stages use them
             gc[1] = gap_coefficients(cur.h[1], cur.hx[1], cur.hy[1]);
@@ -636,6 +684,7 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
                 part[k][2] = (cur.jy[k] + q1[k][2]) - dt * (-cx * g[k].fx2 + cy * (dn[k][2] - gy[k][2]) - g[k].s2);
             }
         }
+        if (TABLE) rc_row = coef_of(n + 1);
     };
     for (int n = n_first - 1;;) {
         march(n, rowbuf[0], rowbuf[AHEAD]); if (++n > n_last + 1) break;
@@ -766,7 +815,7 @@ __device__ __forceinline__ void step_strip2(const Step2Args& a, const Phys& P, c
 // device-side step counter.  Grid: gridDim.x = a multiple of 8 blocks of 4 waves; wave w of the XCD-ordered numbering
 // works on strip w % nstrips of chunk w / nstrips.
 template <int EOS, bool HAS_LS, bool PIEZO, int D, int TOPO>
-__global__ __launch_bounds__(256, (Step2Weight<EOS, HAS_LS, PIEZO>::heavy ? 1 : ((TOPO == 1 || TOPO == 3) ? GPF_K2_MINWAVES_LINE : GPF_K2_MINWAVES)))
+__global__ __launch_bounds__(256, (Step2Weight<EOS, HAS_LS, PIEZO>::heavy ? 1 : ((TOPO == 1 || TOPO == 3 || TOPO == 4) ? GPF_K2_MINWAVES_LINE : GPF_K2_MINWAVES)))
 void k_step2(const Step2Args a, const Phys P) {
     __shared__ double stash[4][3][128];         // per wave: stage-1 field on the downwind ghost row (fused)
     __shared__ Acc red_sm[4];

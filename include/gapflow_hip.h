@@ -148,6 +148,13 @@ int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, double* total_ms
  * (GPF_PLAN_TUNE=0: rule of thumb; GPF_CHUNKS / GPF_NT_STORES pin a choice).  Empty until the first step has been planned.
  * The choice changes the order in which the kinetic energy is summed (last bits of the residual), nothing else. */
 const char* gpf_plan_note(gpf_handle* h);
+/* The closure coefficients of an x-only gap, one record of 8 doubles (A, B, C, S0, S1a, S1b, S2a, S2b: closures.hpp, RowCoef) per
+ * row ix = 0 .. Nx+1, then two per x edge for the rows across a periodic slab seam (zero where there is none): count = 8 (Nx+2+4).
+ * source 0: the table the fused step reads (built on the device at every upload of the gap and by gpf_set_seam_topo);
+ * source 1: the same function evaluated now, row by row, on column 1 of the handle's gap PLANES and on its seam rows.
+ * GPF_ERR_STATE unless the handle holds a table: the gap varies along x only, no slip-length field or piezo-viscosity, and
+ * GPF_ROWCOEF_TABLE was not 0 at gpf_create (the step kernel then evaluates the coefficients itself, as before the table). */
+int gpf_row_coefficients(gpf_handle* h, int source, double* host, size_t count);
 /* The reference-ordered, unfused stage pipeline (closures -> flux -> source -> axpy -> ghost),
  * one kernel per reference function; same results as gpf_step(h,1,...).  Kept for
  * cross-checking and for _finalize (problem.py:588-610). */
