@@ -6,7 +6,9 @@ Several GPUs of one node: start one process per GPU,
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m gapflow_amd -i input.yaml
 
 and the problem is cut into x-slabs (gapflow_amd/slab.py); rank 0 writes the output.  GPF_SLAB_TRANSPORT=p2p selects the
-peer-to-peer mailbox transport instead of one all-gather per step."""
+peer-to-peer mailbox transport instead of one all-gather per step.
+
+``python -m gapflow_amd --restart out/checkpoint.gpf [--output DIR] [--max-it N]`` continues a run from a checkpoint."""
 import argparse
 import os
 import sys
@@ -14,12 +16,43 @@ import sys
 from . import Problem
 
 
-def main(argv=None):
+def make_parser():
     cli = argparse.ArgumentParser(prog='python -m gapflow_amd',
                                   description="Advance a GaPFlow YAML problem on an MI355X.")
-    cli.add_argument('-i', '--input', dest='filename', required=True, metavar='YAML', help="problem definition")
+    src = cli.add_mutually_exclusive_group(required=True)
+    src.add_argument('-i', '--input', dest='filename', metavar='YAML', help="problem definition")
+    src.add_argument('--restart', metavar='CHECKPOINT', help="continue the run a checkpoint file was written from (options.checkpoint_freq, "
+                     "Problem.save_checkpoint); slab runs: the name without .rankNNN, on the same number of processes")
+    cli.add_argument('--output', metavar='DIR', help="with --restart: a new output directory for the continued run (default: the saved run's "
+                     "options, with '_restart' appended when they name a fixed directory; frames go into a new sol.nc, history.csv "
+                     "continues the saved history)")
+    cli.add_argument('--max-it', type=int, metavar='N', help="with --restart: run until step N instead of the saved run's max_it")
     cli.add_argument('--device', type=int, default=0, help="HIP device ordinal of a single-process run (default 0)")
+    return cli
+
+
+def restart_overrides(opts):
+    """(options, numerics) overrides of Problem.from_checkpoint from the command line.  Without --output a saved run that
+    wrote into a fixed directory (use_tstamp: False) continues in `<that directory>_restart`: the old one is not empty."""
+    options = {'output': opts.output} if opts.output else None
+    if options is None:
+        from . import checkpoint
+        first = opts.restart if os.path.exists(opts.restart) else checkpoint.rank_path(opts.restart, 0)
+        try:
+            saved = checkpoint.read_file(first)[0]['inputs']['options']
+        except (OSError, ValueError, KeyError):
+            saved = None                        # from_checkpoint reports what is wrong with the file
+        if saved is not None and not saved.get('use_tstamp', True):
+            options = {'output': saved['output'].rstrip('/') + '_restart'}
+    numerics = {'max_it': opts.max_it} if opts.max_it is not None else None
+    return options, numerics
+
+
+def main(argv=None):
+    cli = make_parser()
     opts = cli.parse_args(argv)
+    if opts.restart is None and (opts.output or opts.max_it is not None):
+        cli.error("--output and --max-it go with --restart")
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         import torch
         import torch.distributed as dist
@@ -28,11 +61,19 @@ def main(argv=None):
         torch.cuda.set_device(local)
         dist.init_process_group('nccl', device_id=torch.device('cuda', local))
         try:
-            SlabProblem.from_yaml(opts.filename, device=local).run()
+            if opts.restart:
+                options, numerics = restart_overrides(opts)
+                SlabProblem.from_checkpoint(opts.restart, device=local, options=options, numerics=numerics).run()
+            else:
+                SlabProblem.from_yaml(opts.filename, device=local).run()
         finally:
             dist.destroy_process_group()
         return 0
-    Problem.from_yaml(opts.filename, device=opts.device).run()
+    if opts.restart:
+        options, numerics = restart_overrides(opts)
+        Problem.from_checkpoint(opts.restart, device=opts.device, options=options, numerics=numerics).run()
+    else:
+        Problem.from_yaml(opts.filename, device=opts.device).run()
     return 0
 
 

@@ -127,6 +127,10 @@ SIGNATURES = {
     'gpf_gap_profiles_op': (C.c_int, [C.c_int64, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                                                               C.c_void_p]),
     'gpf_gap_profiles': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'gpf_checkpoint_size': (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    'gpf_checkpoint_save': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    'gpf_checkpoint_load': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    'gpf_checkpoint_pack_probe': (C.c_int, [C.c_void_p, C.c_int, _DP]),
     'gpf_profile_store_probe': (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _DP]),
 }
 

@@ -20,6 +20,7 @@
 #include "elastic_kernels.hip"
 #include "small_kernel.hip"
 #include "profile_kernels.hip"
+#include "checkpoint_kernels.hip"
 
 using namespace gpf;
 
@@ -141,6 +142,9 @@ struct gpf_handle {
     int open_parity = 0;
     bool has_q = false, has_topo = false, pre_run_done = false;
     bool prev_state_valid = false;          // the OTHER q buffer holds the state before the last committed fused step (gpf_update_closures)
+    long long fields_step = -1;             // the derived fields hold the closures the reference's field objects hold at this step count
+                                            // (the corrector stage's: gpf_close_step, gpf_update_closures); -1: something else
+    bool fields_restored = false;           // ... and came from a checkpoint: gpf_update_closures keeps them (nothing could recompute them)
     long long host_step = 0;                // step count at the last sync
     long long next_step = 0;                // index of the next step to be enqueued (== device step unless halted)
     // two-columns-per-lane step kernel (step2_kernel.hip): window geometry per predictor direction [0: D=+1, 1: D=-1],
@@ -157,7 +161,7 @@ struct gpf_handle {
 
 static int enter(gpf_handle* h, bool reads_only) {
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (!reads_only) h->gp_state_mean_valid = false;
+    if (!reads_only) { h->gp_state_mean_valid = false; h->fields_restored = false; }
     return GPF_OK;
 }
 
@@ -392,6 +396,47 @@ static int build_rowcoef(gpf_handle* h, bool rows, int side) {
     return GPF_OK;
 }
 
+// What a handle derives from the gap planes it is given (host: [3][Nx+2][Ny+2]): whether the gap varies along one axis only
+// (bitwise test), the profile along that axis and, for an x-only gap, the row-coefficient table with its seam records.
+static int derive_from_topo(gpf_handle* h, const double* host) {
+    const Layout& L = h->L;
+    // does the topography vary along one axis only?  (bitwise test on the host array)
+    const int nx = L.Nx + 2, ny = L.Ny + 2;
+    bool xonly = true, yonly = true;
+    for (int c = 0; c < 3 && (xonly || yonly); ++c)
+        for (int ix = 0; ix < nx && (xonly || yonly); ++ix) {
+            const double* row = host + ((size_t)c * nx + ix) * ny;
+            const double* row0 = host + (size_t)c * nx * ny;
+            for (int iy = 0; iy < ny; ++iy) {
+                if (std::memcmp(&row[iy], &row[0], 8) != 0) xonly = false;
+                if (std::memcmp(&row[iy], &row0[iy], 8) != 0) yonly = false;
+            }
+        }
+    const int mode = xonly ? 1 : (yonly ? 2 : 0);
+    if (mode != h->topo_mode) { h->plan2_valid = false; }
+    h->topo_mode = (h->el.on || h->els.on) ? 0 : mode;         // an elastic gap changes on the device: always read the planes
+    if (mode) {
+        const int n = mode == 1 ? nx : ny;
+        std::vector<double> line((size_t)3 * n);
+        for (int c = 0; c < 3; ++c)
+            for (int i = 0; i < n; ++i)
+                line[(size_t)c * n + i] = mode == 1 ? host[((size_t)c * nx + i) * ny] : host[(size_t)c * nx * ny + i];
+        bool hy0 = mode == 1;
+        for (int i = 0; i < n && hy0; ++i) hy0 = line[(size_t)2 * n + i] == 0.0;
+        if (hy0 != h->topo_hy0) h->plan2_valid = false;
+        h->topo_hy0 = hy0;
+        if (!h->topo_line) HIP_TRY(hipMalloc(&h->topo_line, (size_t)3 * (std::max(nx, ny)) * sizeof(double)));
+        HIP_TRY(hipMemcpy(h->topo_line, line.data(), line.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (hy0 && h->rowcoef_table) {
+            const bool fresh = h->rowcoef == nullptr;
+            GPF_TRY(build_rowcoef(h, true, -1));
+            for (int e = 0; e < 2 && fresh; ++e)
+                if (h->has_seam[e]) GPF_TRY(build_rowcoef(h, false, e));
+        }
+    }
+    return GPF_OK;
+}
+
 extern "C" int gpf_upload(gpf_handle* h, int field, const double* host, size_t count) {
     if (!h || !host) return fail(GPF_ERR_INVALID, "gpf_upload: null argument");
     GPF_TRY(enter(h));
@@ -416,42 +461,7 @@ extern "C" int gpf_upload(gpf_handle* h, int field, const double* host, size_t c
         HIP_TRY(hipMemsetAsync(h->Ls, 0, (size_t)L.plane * sizeof(double), h->stream));
         dst = h->Ls;
     }
-    if (field == GPF_FIELD_TOPO) {
-        // does the topography vary along one axis only?  (bitwise test on the host array)
-        const int nx = L.Nx + 2, ny = L.Ny + 2;
-        bool xonly = true, yonly = true;
-        for (int c = 0; c < 3 && (xonly || yonly); ++c)
-            for (int ix = 0; ix < nx && (xonly || yonly); ++ix) {
-                const double* row = host + ((size_t)c * nx + ix) * ny;
-                const double* row0 = host + (size_t)c * nx * ny;
-                for (int iy = 0; iy < ny; ++iy) {
-                    if (std::memcmp(&row[iy], &row[0], 8) != 0) xonly = false;
-                    if (std::memcmp(&row[iy], &row0[iy], 8) != 0) yonly = false;
-                }
-            }
-        const int mode = xonly ? 1 : (yonly ? 2 : 0);
-        if (mode != h->topo_mode) { h->plan2_valid = false; }
-        h->topo_mode = (h->el.on || h->els.on) ? 0 : mode;         // an elastic gap changes on the device: always read the planes
-        if (mode) {
-            const int n = mode == 1 ? nx : ny;
-            std::vector<double> line((size_t)3 * n);
-            for (int c = 0; c < 3; ++c)
-                for (int i = 0; i < n; ++i)
-                    line[(size_t)c * n + i] = mode == 1 ? host[((size_t)c * nx + i) * ny] : host[(size_t)c * nx * ny + i];
-            bool hy0 = mode == 1;
-            for (int i = 0; i < n && hy0; ++i) hy0 = line[(size_t)2 * n + i] == 0.0;
-            if (hy0 != h->topo_hy0) h->plan2_valid = false;
-            h->topo_hy0 = hy0;
-            if (!h->topo_line) HIP_TRY(hipMalloc(&h->topo_line, (size_t)3 * (std::max(nx, ny)) * sizeof(double)));
-            HIP_TRY(hipMemcpy(h->topo_line, line.data(), line.size() * sizeof(double), hipMemcpyHostToDevice));
-            if (hy0 && h->rowcoef_table) {
-                const bool fresh = h->rowcoef == nullptr;
-                GPF_TRY(build_rowcoef(h, true, -1));
-                for (int e = 0; e < 2 && fresh; ++e)
-                    if (h->has_seam[e]) GPF_TRY(build_rowcoef(h, false, e));
-            }
-        }
-    }
+    if (field == GPF_FIELD_TOPO) GPF_TRY(derive_from_topo(h, host));
     GPF_TRY(ensure_stage(h, count));
     HIP_TRY(hipMemcpyAsync(h->stage, host, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_pack, dim3(blocks_for((long long)count)), dim3(256), 0, h->stream, h->stage, dst, L, nc);
@@ -460,6 +470,7 @@ extern "C" int gpf_upload(gpf_handle* h, int field, const double* host, size_t c
     if (field == GPF_FIELD_Q) h->has_q = true;
     h->g1_ready = false;
     h->prev_state_valid = false;
+    h->fields_step = -1;                    // the derived fields belong to what was there before
     if (field == GPF_FIELD_TOPO) h->has_topo = true;
     return GPF_OK;
 }
@@ -522,6 +533,7 @@ static const double* beyond_rows(gpf_handle* h, const double* q) {
 // `pressure_mean_cached`: the pressure surrogate's mean of this very field is in gp_state_mean (see gpf_handle)
 static int launch_fields(gpf_handle* h, const double* q, bool pressure_mean_cached = false) {
     GPF_TRY(ensure_fields(h));
+    h->fields_step = -1; h->fields_restored = false;
     const Layout& L = h->L;
     const long long n = (long long)(L.Nx + 2) * (L.Ny + 2);
     FieldPtrs F = field_ptrs(h);
@@ -550,6 +562,7 @@ static int launch_fields(gpf_handle* h, const double* q, bool pressure_mean_cach
 extern "C" int gpf_update_closures(gpf_handle* h) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
     if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_update_closures: upload q and topography first");
+    if (h->fields_restored) return GPF_OK;  // a checkpoint brought the corrector-stage closures of this very state (gpf_checkpoint_load)
     GPF_TRY(enter(h));
     int par = 0;
     GPF_TRY(current_parity(h, &par));
@@ -580,6 +593,7 @@ extern "C" int gpf_update_closures(gpf_handle* h) {
         HIP_TRY(hipGetLastError());
         GPF_TRY(launch_fields(h, w));
         h->prev_state_valid = false;        // the buffer now holds the predictor's field; the closures stay in the derived fields
+        h->fields_step = s.step;
     } else {
         GPF_TRY(launch_fields(h, h->q[par]));
     }
@@ -692,6 +706,7 @@ extern "C" int gpf_pre_run(gpf_handle* h) {
     h->pre_run_done = true;
     h->g1_ready = false;
     h->prev_state_valid = false;
+    h->fields_step = -1;
     h->host_step = 0; h->next_step = 0;
     return GPF_OK;
 }
@@ -1025,3 +1040,4 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
 #include "api_slab_stagewise.inc"
 #include "api_slab_elastic.inc"
 #include "api_profiles.inc"
+#include "api_checkpoint.inc"

@@ -11,6 +11,26 @@ static dim3 profile_grid(long long ncell, int nlev) {
 
 static constexpr int PROFILE_MAX_LEVELS = 65535 * PROFILE_LEVELS_PER_THREAD;
 
+// The double-buffered device scratch that large results leave the device through (gpf_gap_profiles, the checkpoint calls):
+// doubles per half (GPF_PROFILE_SCRATCH_MB MiB for both, default 256), and the pipeline over the chunks of a request -- the
+// kernel of chunk c + 1 is queued into one half ahead of the copy of chunk c in the other, so nothing waits on the host.
+static long long scratch_half_doubles() {
+    const char* env = std::getenv("GPF_PROFILE_SCRATCH_MB");
+    const double mb = env ? std::atof(env) : 256.0;
+    return (long long)(std::max(mb, 0.0) * (1 << 20) / 16.0);
+}
+template <class Launch, class Copy>
+static hipError_t run_double_buffered(hipStream_t stream, size_t nchunks, Launch launch, Copy copy) {
+    hipError_t e = nchunks ? launch((size_t)0) : hipSuccess;
+    for (size_t c = 0; c < nchunks && e == hipSuccess; ++c) {
+        if (c + 1 < nchunks && (e = launch(c + 1)) != hipSuccess) break;      // into the other half
+        e = copy(c);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    else (void)hipStreamSynchronize(stream);
+    return e;
+}
+
 // get_velocity_profiles / get_stress_profiles (profiles.py:33-138, 141-1323) for n cells x nz levels
 extern "C" int gpf_gap_profiles_op(int64_t n, int nz, const double* z, const double* q, const double* hh, const double* dqx,
                                    const double* dqy, const double* eta, const double* zeta, const double* Ls, int per_cell,
@@ -80,9 +100,7 @@ extern "C" int gpf_gap_profiles(gpf_handle* h, int nz, int ix0, int ix1, int fie
     GPF_TRY(current_parity(h, &par));
     const int np = profile_nplanes(field_mask);
     const int W = L.Ny + 2, nrows = ix1 - ix0;
-    const char* env = std::getenv("GPF_PROFILE_SCRATCH_MB");
-    const double mb = env ? std::atof(env) : 256.0;
-    long long half = (long long)(std::max(mb, 0.0) * (1 << 20) / 16.0);           // doubles per half
+    long long half = scratch_half_doubles();
     half = std::max(half, (long long)np * (W + 1));                                 // at least one (row, level) unit
     int R, Lv;
     if ((long long)np * nz * ((long long)W + 1) <= half) {
@@ -130,13 +148,8 @@ extern "C" int gpf_gap_profiles(gpf_handle* h, int nz, int ix0, int ix1, int fie
         }
         return hipSuccess;
     };
-    e = launch(0);
-    for (size_t c = 0; c < chunks.size() && e == hipSuccess; ++c) {
-        if (c + 1 < chunks.size() && (e = launch(c + 1)) != hipSuccess) break;      // into the other half
-        e = copy(c);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); rc = fail(GPF_ERR_HIP, hipGetErrorString(e)); }
+    e = run_double_buffered(h->stream, chunks.size(), launch, copy);
+    if (e != hipSuccess) rc = fail(GPF_ERR_HIP, hipGetErrorString(e));
     hipFree(d);
     return rc;
 }

@@ -86,6 +86,7 @@ extern "C" int gpf_close_step(gpf_handle* h, gpf_scalars_t* out) {
         h->gp_state_mean_step = s.step;
     }
     h->gp_state_mean_fresh = false;
+    h->fields_step = (!s.invalid && s.step == h->host_step + 1) ? s.step : -1;      // the corrector stage's closures
     h->host_step = s.step; h->next_step = s.step;
     if (out) fill_scalars(s, nullptr, 0.0, out);
     return GPF_OK;

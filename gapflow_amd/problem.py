@@ -103,6 +103,8 @@ class Problem:
         self._ekin_old_user = None
         self._stop = False
         self.history = {k: [] for k in ('step', 'time', 'ekin', 'residual', 'vsound')}
+        self._restart_history = None            # from_checkpoint: the saved run's history, which run() continues
+        self._has_extra_field = extra_field is not None
 
         if not options['silent']:
             self.outdir = create_output_directory(options['output'], options['use_tstamp'])
@@ -132,12 +134,14 @@ class Problem:
     def from_yaml(cls, fname, device=0):
         print(f"Reading input file: {fname}")
         with open(fname, "r") as f:
-            return cls._from_dict(read_yaml_input(f), device=device)
+            return cls.from_string(f.read(), device=device)
 
     @classmethod
     def from_string(cls, ymlstring, device=0):
         with _io.StringIO(ymlstring) as f:
-            return cls._from_dict(read_yaml_input(f), device=device)
+            input_dict = read_yaml_input(f)
+        _keep_checkpoint_freq(input_dict, ymlstring)
+        return cls._from_dict(input_dict, device=device)
 
     @classmethod
     def _from_dict(cls, input_dict, device=0):
@@ -338,6 +342,85 @@ class Problem:
         return bool(np.all(np.array(self.residual_buffer) < self.tol))
 
     # -------------------------------------------------------------------------------------
+    # checkpoint and restart (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _checkpoint_refusal(self):
+        if self.has_gp_model or self._gp_models:
+            from .checkpoint import NOT_SAVED
+            raise NotImplementedError(NOT_SAVED['surrogate'])
+        if self.step is None:
+            raise RuntimeError("checkpoint: call _pre_run() (or run()) first")
+
+    def save_checkpoint(self, path):
+        """Write everything the run needs to continue bit for bit into one file (atomically: path + '.tmp', then os.replace):
+        the device's checkpoint blob (gpf_checkpoint_save) behind the sanitised input dictionaries and the host's mirror of the run."""
+        from . import checkpoint
+        self._checkpoint_refusal()
+        self._sync_to_device()
+        meta = {'kind': 'problem', 'version': __version__,
+                'inputs': checkpoint.input_dicts(self.options, self.grid, self.numerics, self.prop, self.geo),
+                'extra_field': bool(self._has_extra_field),
+                'mirror': {'step': self.step, 'simtime': self.simtime, 'dt': self.dt, 'residual': self.residual,
+                           'residual_buffer': list(self.residual_buffer), 'history': self.history,
+                           'kinetic_energy_old': self._kinetic_energy_old}}
+        checkpoint.write_file(path, meta, checkpoint.device_blob(self._lib, self._h))
+
+    def load_checkpoint(self, path):
+        """Continue from a file of save_checkpoint in THIS problem (after _pre_run): the library refuses a checkpoint of another
+        configuration, a truncated or a damaged one with a RuntimeError that names what differs, and the problem stays as it was."""
+        from . import checkpoint
+        self._checkpoint_refusal()
+        try:
+            meta, blob = checkpoint.read_file(path)
+        except ValueError as e:
+            raise RuntimeError(str(e)) from None
+        if meta.get('kind') != 'problem':
+            raise RuntimeError(f"checkpoint: {path} holds one rank of a slab run (kind '{meta.get('kind')}'); load it with SlabProblem")
+        self._sync_to_device()
+        checkpoint.load_device_blob(self._lib, self._h, blob)
+        self._restore_mirror(meta['mirror'])
+
+    def _restore_mirror(self, m):
+        self.step, self.simtime, self.dt, self.residual = int(m['step']), m['simtime'], m['dt'], m['residual']
+        self.residual_buffer = deque(m['residual_buffer'], 5)
+        self._kinetic_energy_old = m['kinetic_energy_old']
+        self.history = {k: list(v) for k, v in m['history'].items()}
+        self._restart_history = {k: list(v) for k, v in m['history'].items()}
+        self._mark_device_advanced()                        # q and the closures are read from the device again
+        if self._has_extra_field:
+            self._extra = self._download(_lib.FIELD_EXTRA, 1)
+        self._download_topo(self.topo._field)               # the gap as the device holds it (deformed; drawn asperity heights)
+        self.topo._stale = False
+
+    @classmethod
+    def from_checkpoint(cls, path, device=0, options=None, numerics=None):
+        """A new problem that continues the saved one: built from the stored input dictionaries, `_pre_run`, then the blob.
+        `options` may override 'output' and 'silent' (and 'use_tstamp', 'write_freq', 'checkpoint_freq'), `numerics` 'max_it' and
+        'tol' -- when to stop is not part of the state."""
+        from . import checkpoint
+        try:
+            meta, _ = checkpoint.read_file(path)
+        except ValueError as e:
+            raise RuntimeError(str(e)) from None
+        inp = meta['inputs']
+        for given, allowed, target in ((options, ('output', 'silent', 'use_tstamp', 'write_freq', 'checkpoint_freq'), inp['options']),
+                                       (numerics, ('max_it', 'tol'), inp['numerics'])):
+            for k, v in (given or {}).items():
+                if k not in allowed:
+                    raise ValueError(f"from_checkpoint: '{k}' cannot be overridden (only {allowed})")
+                target[k] = v
+        extra = None
+        if meta.get('extra_field'):          # a placeholder that makes the handle allocate the field; the blob brings its values
+            extra = np.ones((1, inp['grid']['Nx'] + 2, inp['grid']['Ny'] + 2))
+        p = cls(inp['options'], inp['grid'], inp['numerics'], inp['properties'], inp['geometry'], extra_field=extra, device=device)
+        p._pre_run()
+        p.load_checkpoint(path)
+        return p
+
+    def _write_checkpoint(self):
+        self.save_checkpoint(os.path.join(self.outdir, 'checkpoint.gpf'))
+
+    # -------------------------------------------------------------------------------------
     # run loop (problem.py:368-503)
     # -------------------------------------------------------------------------------------
     def _features(self):
@@ -460,13 +543,16 @@ class Problem:
         if self.step is None:
             self._pre_run()
         self._stop = False
-        self.history = {k: [] for k in ('step', 'time', 'ekin', 'residual', 'vsound')}
+        self.history = self._restart_history or {k: [] for k in ('step', 'time', 'ekin', 'residual', 'vsound')}
+        self._restart_history = None
         silent = self.options['silent']
+        cf = 0 if silent else int(self.options.get('checkpoint_freq', 0) or 0)      # steps between checkpoint.gpf; 0: none
         if not silent:
             print(61 * '-')
             print(f"{'Step':6s} {'Timestep':10s} {'Time':10s} {'CFL':10s} {'Residual':10s}")
             print(61 * '-')
-            self.write(params=False)
+            # (a restarted run's history already ends with the row of the step it starts from)
+            self.write(scalars=not (self.history['step'] and self.history['step'][-1] == self.step), params=False)
         old = {s: signal.signal(s, self._receive_signal) for s in _termination_signals()} \
             if _in_main_thread() else {}
         self._tic = datetime.now()
@@ -476,18 +562,24 @@ class Problem:
                 self.update()                   # surrogates: one host-driven step at a time
                 if self.step % wf == 0 and not silent and not self._stop:
                     self.write()
+                if cf > 0 and self.step % cf == 0 and not self._stop and not self.converged and self.step < self.max_it:
+                    self._write_checkpoint()    # (a run that ends here writes its checkpoint once, below)
             while not self.converged and self.step < self.max_it and not self._stop:
                 # steps until the next frame (problem.py:404) or max_it, whichever comes first; the
                 # device stops by itself at convergence, so a batch never overshoots the reference's loop
-                n = min(wf - self.step % wf, self.max_it - self.step, 4096)
+                n = min(wf - self.step % wf, self.max_it - self.step, 4096, *([cf - self.step % cf] if cf > 0 else []))
                 self._advance(n, honor_stop=True)
                 if self.step % wf == 0 and not silent and not self._stop:
                     self.write()
+                if cf > 0 and self.step % cf == 0 and not self._stop and not self.converged and self.step < self.max_it:
+                    self._write_checkpoint()    # (a run that ends here writes its checkpoint once, below)
         finally:
             for s, hdl in old.items():
                 signal.signal(s, hdl)
         if not keep_open:
             self._post_run()
+        if cf > 0:
+            self._write_checkpoint()            # the state the run ends on, with the history _post_run completed
 
     def _post_run(self):
         walltime = datetime.now() - self._tic
@@ -572,6 +664,16 @@ class Problem:
         if params:
             for m in self._gp_models.values():
                 m.write()
+
+
+def _keep_checkpoint_freq(input_dict, ymlstring):
+    """`options.checkpoint_freq` is this project's own key: the sanitiser keeps the reference's keys only (as the reference, which
+    ignores unknown ones), so it is read from the YAML text and set beside them."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    freq = (raw.get('options') or {}).get('checkpoint_freq', 0)
+    if input_dict.get('options') is not None:
+        input_dict['options']['checkpoint_freq'] = int(freq or 0)
 
 
 def _in_main_thread():

@@ -421,6 +421,7 @@ class SlabProblem:
             import torch.distributed as dist
         self.torch, self.dist = torch, dist
         self._device, self._writer_problem, self._pre_run_done = device, None, False
+        self._restart_history = None            # rank 0 after load_checkpoint: the saved run's frame history
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.input = input_dict
         grid, prop, geo = input_dict['grid'], input_dict['properties'], input_dict['geometry']
@@ -541,17 +542,104 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None):
+        from .problem import _keep_checkpoint_freq
         with _io.StringIO(text) as f:
-            return cls(read_yaml_input(f), device=device, dist=dist)
+            d = read_yaml_input(f)
+        _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
+        return cls(d, device=device, dist=dist)
 
     @classmethod
     def from_yaml(cls, fname, device=0):
         with open(fname) as f:
-            return cls(read_yaml_input(f), device=device)
+            return cls.from_string(f.read(), device=device)
 
     def _upload(self, field, arr):
         a = _lib.f64c(arr)
         _lib.check(self.lib.gpf_upload(self._h, field, _lib.as_dp(a), a.size))
+
+    # -- checkpoint and restart -------------------------------------------------
+    def _checkpoint_refusal(self):
+        from .checkpoint import NOT_SAVED
+        if self._gp_models or self.input.get('gp') is not None:
+            raise NotImplementedError(NOT_SAVED['surrogate'])
+        if self._elastic is not None:
+            raise NotImplementedError(NOT_SAVED['elastic slab'])
+        geo = self.input['geometry']
+        if geo['type'] == 'asperity' and geo['num'] != 1:
+            # the seam rows and the writer's gap are rebuilt from the YAML, and these heights are an unseeded random draw
+            raise NotImplementedError(NOT_SAVED['random asperities on slabs'])
+        if not self._pre_run_done:
+            raise RuntimeError("checkpoint: call pre_run() (or run()) first")
+
+    def save_checkpoint(self, path):
+        """Every rank writes its own rows into ``path.rankNNN`` (atomically, as Problem.save_checkpoint); rank 0's file also
+        carries the history of the output frames.  Collective only in that every rank has to call it at the same step."""
+        from . import checkpoint
+        self._checkpoint_refusal()
+        self.torch.cuda.current_stream().synchronize()
+        d = self.input
+        meta = {'kind': 'slab', 'world': self.world, 'rank': self.rank,
+                'inputs': checkpoint.input_dicts(d['options'], d['grid'], d['numerics'], d['properties'], d['geometry'])}
+        if self.rank == 0:
+            w = self._writer_problem
+            meta['mirror'] = {'history': w.history if w is not None else (self._restart_history or {})}
+        checkpoint.write_file(checkpoint.rank_path(path, self.rank), meta, checkpoint.device_blob(self.lib, self._h))
+
+    def _write_checkpoint(self):
+        """checkpoint.gpf.rankNNN in rank 0's output directory (every rank learns its name from rank 0)."""
+        box = [self._writer_problem.outdir if self.rank == 0 else None]
+        self.dist.broadcast_object_list(box, src=0)
+        self.save_checkpoint(os.path.join(box[0], 'checkpoint.gpf'))
+
+    def load_checkpoint(self, path):
+        """This rank's file of a save on the same number of ranks, into this problem (after pre_run).  The all-gather transport
+        only: a problem connected for the peer-to-peer transport refuses (its mailboxes' sequence numbers cannot be put back)."""
+        from . import checkpoint
+        self._checkpoint_refusal()
+        try:
+            meta, blob = checkpoint.read_file(checkpoint.rank_path(path, self.rank))
+        except ValueError as e:
+            raise RuntimeError(str(e)) from None
+        if meta.get('kind') != 'slab' or meta.get('world') != self.world or meta.get('rank') != self.rank:
+            raise RuntimeError(f"checkpoint: {checkpoint.rank_path(path, self.rank)} was written by rank {meta.get('rank')} of "
+                               f"{meta.get('world')} (kind '{meta.get('kind')}'); this is rank {self.rank} of {self.world}")
+        self.torch.cuda.current_stream().synchronize()
+        checkpoint.load_device_blob(self.lib, self._h, blob)
+        st = self.state()
+        self.driver.enqueued = int(st.step)         # the sweep direction of a captured pair of steps follows it
+        self.driver.graph = None
+        self._closures_stale = True
+        if self.rank == 0:
+            self._restart_history = {k: list(v) for k, v in (meta.get('mirror', {}).get('history') or {}).items()} or None
+
+    @classmethod
+    def from_checkpoint(cls, path, device=0, dist=None, options=None, numerics=None):
+        """A new slab problem on every rank that continues the saved one; the process group must have the world size of the save."""
+        from . import checkpoint
+        if dist is None:
+            import torch.distributed as dist
+        rank, world = dist.get_rank(), dist.get_world_size()
+        first = checkpoint.rank_path(path, rank)
+        if not os.path.exists(first):
+            raise RuntimeError(f"checkpoint: {first} not found: a slab checkpoint loads on the world size it was written on "
+                               f"(this one: {world})")
+        try:
+            meta, _ = checkpoint.read_file(first)
+        except ValueError as e:
+            raise RuntimeError(str(e)) from None
+        if meta.get('world') != world:
+            raise RuntimeError(f"checkpoint: written on {meta.get('world')} ranks, this process group has {world}")
+        inp = meta['inputs']
+        for given, allowed, target in ((options, ('output', 'silent', 'use_tstamp', 'write_freq'), inp['options']),
+                                       (numerics, ('max_it', 'tol'), inp['numerics'])):
+            for k, v in (given or {}).items():
+                if k not in allowed:
+                    raise ValueError(f"from_checkpoint: '{k}' cannot be overridden (only {allowed})")
+                target[k] = v
+        p = cls(inp, device=device, dist=dist)
+        p.pre_run()
+        p.load_checkpoint(path)
+        return p
 
     def global_scalars(self):
         """Ekin, v_max, v_sound, mass over the whole domain (sum / max over the slabs)."""
@@ -711,7 +799,7 @@ class SlabProblem:
                                            database=self.database if self._gp_models else None, device=self._device,
                                            elastic_on_device=False)
             w = self._writer_problem
-            w.history = {k: [] for k in ('step', 'time', 'ekin', 'residual', 'vsound')}
+            w.history = self._restart_history or {k: [] for k in ('step', 'time', 'ekin', 'residual', 'vsound')}
         w = self._writer_problem
         for name, m in self._gp_models.items():
             wm = w._gp_models[name]
@@ -724,7 +812,8 @@ class SlabProblem:
         st = self.state()
         w.q[...] = q
         w.step, w.simtime, w.dt, w.residual = int(st.step), st.simtime, st.dt, st.residual
-        w.write(params=False)
+        # (a restarted run's history already ends with the row of the step it starts from)
+        w.write(scalars=not (w.history['step'] and w.history['step'][-1] == w.step), params=False)
 
     def run(self):
         """Problem.run (problem.py:368-410) for a slab-decomposed problem: same stopping rules (tolerance on the last
@@ -732,6 +821,7 @@ class SlabProblem:
         import datetime as _dt
         opt, num = self.input['options'], self.input['numerics']
         silent, wf, max_it = opt['silent'], opt['write_freq'], num['max_it']
+        cf = 0 if silent else int(opt.get('checkpoint_freq', 0) or 0)        # steps between checkpoints; 0: none
         if not self._pre_run_done:
             self.pre_run()
         if not silent:
@@ -743,7 +833,7 @@ class SlabProblem:
         tic = _dt.datetime.now()
         st = self.state()
         while not st.converged and st.step < max_it and not st.invalid:
-            n = min(wf - st.step % wf, max_it - st.step, 4096)
+            n = min(wf - st.step % wf, max_it - st.step, 4096, *([cf - st.step % cf] if cf > 0 else []))
             self.advance(n, honor_stop=True)
             st = self.state()
             if st.invalid:
@@ -753,8 +843,12 @@ class SlabProblem:
                 break
             if st.step % wf == 0 and not silent:
                 self._frame()
+            if cf > 0 and st.step % cf == 0 and not st.converged and st.step < max_it:
+                self._write_checkpoint()
         if not silent and st.step % wf != 0:
             self._frame()
+        if cf > 0 and not st.invalid:
+            self._write_checkpoint()            # the state the run ends on
         if self.rank == 0:
             wall = _dt.datetime.now() - tic
             print(33 * '=')

@@ -370,6 +370,34 @@ int gpf_gap_profiles(gpf_handle* h, int nz, int ix0, int ix1, int field_mask, in
  * of ncell x nlev doubles (tools/profile_time.py; no reference counterpart). */
 int gpf_profile_store_probe(int device, int64_t ncell, int nlev, int nplanes, int reps, double* ms_per_pass);
 
+/* ---- checkpoint and restart (no reference counterpart: the reference has no solution restart) ---------------------- */
+/* Everything the next step of this handle depends on, as one blob of host memory, so that a handle made by gpf_create from the
+ * same configuration -- in another process, with another pitch, placement or kernel form (GPF_SCATTER_MB, GPF_KEEP_ROWS,
+ * GPF_CHUNKS, GPF_ROWCOEF_TABLE, GPF_SMALL_GRID) -- continues the run bit for bit.  The blob holds a header (magic, format
+ * version, Nx, Ny, component counts, the parts of gpf_config that decide the arithmetic, one 64-bit digest per plane), the
+ * device's run state (dt, Ekin_old, the residual ring, step, simtime, sweep parity, the last step's dt), and planes in the
+ * host layout [ix][iy] with ghost cells: the current q, the q before the last fused step when the handle still has it
+ * (gpf_update_closures forms the corrector-stage closures from it), h, dh/dx, dh/dy as the device holds them, an elastic gap's
+ * under-relaxed displacement, undeformed gap and deformation, the slip length when there is such a field, the densities a thinning slab keeps
+ * beyond its halo, and the 16 derived planes when they hold the corrector-stage closures of a stage-wise step.
+ *   gpf_checkpoint_size  bytes the blob of the handle's present state needs
+ *   gpf_checkpoint_save  writes it (capacity >= that size; *written may be NULL).  Reads only.
+ *   gpf_checkpoint_load  on a handle after gpf_pre_run.  GPF_ERR_INVALID with a message that names the first header field that
+ *                        differs, for a truncated blob, and for a digest that does not match what arrived on the device -- all
+ *                        found before the handle is touched, which then stays as it was.  The planes are then written and digested
+ *                        again from the handle's memory (a mismatch there is GPF_ERR_HIP and the handle needs a fresh upload).
+ *                        The row profile, the row-coefficient table and its seam records are rebuilt from the loaded gap; tol and
+ *                        max_it stay the handle's own and `converged` follows from the loaded residual ring.
+ * Slab handles save and load their own rows; a handle connected for the peer-to-peer transport refuses gpf_checkpoint_load with
+ * GPF_ERR_STATE (the mailbox sequence numbers advance on all ranks together and cannot be put back on one): restart such a run
+ * with the all-gather transport.  Not saved: surrogate models, elastic slabs (GPF_ERR_INVALID). */
+int gpf_checkpoint_size(gpf_handle* h, size_t* bytes);
+int gpf_checkpoint_save(gpf_handle* h, void* host, size_t capacity, size_t* written);
+int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes);
+/* Diagnostic: time of one pass of k_ckpt_pack over the three planes of the current q, chunked through the scratch as
+ * gpf_checkpoint_save does, without the copies to the host (tools/checkpoint_time.py; yardstick: gpf_stream_probe(3, 3, ...)). */
+int gpf_checkpoint_pack_probe(gpf_handle* h, int reps, double* ms_per_pass);
+
 /* Diagnostic: time of one pass of an elementwise kernel that reads `nin` and writes `nout` fp64 planes of
  * `doubles_per_plane` elements (16 bytes per lane, grid-stride): what THIS device streams for the byte count of a fused
  * step.  bench.py reports it beside the step kernel's HBM figure (no reference counterpart: the reference has no device). */
