@@ -36,6 +36,7 @@ FIELD_DEFORMATION = 10
 PROFILE_Z, PROFILE_U, PROFILE_V, PROFILE_TAU = 1, 2, 4, 8          # gpf_gap_profiles field_mask bits
 PROFILE_GRADIENTS = 1
 PROFILE_MODES = {'both': 0, 'top': 1, 'bottom': 2, 'none': 3}
+PROBE_MAX = 256                     # gpf_probes_set: cells per handle
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -132,6 +133,10 @@ SIGNATURES = {
     'gpf_checkpoint_load': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     'gpf_checkpoint_pack_probe': (C.c_int, [C.c_void_p, C.c_int, _DP]),
     'gpf_profile_store_probe': (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _DP]),
+    'gpf_probes_set': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
+    'gpf_probes_clear': (C.c_int, [C.c_void_p]),
+    'gpf_probes_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_probes_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
 }
 
 _lib = None

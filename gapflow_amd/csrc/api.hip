@@ -18,6 +18,7 @@
 #include "step2_kernel.hip"
 #include "gp_kernels.hip"
 #include "elastic_kernels.hip"
+#include "probe_kernels.hip"
 #include "small_kernel.hip"
 #include "profile_kernels.hip"
 #include "checkpoint_kernels.hip"
@@ -92,6 +93,11 @@ struct gpf_handle {
     int nspart = 0;
     LogEntry* log = nullptr;
     long long log_cap = 0;
+    // point probes (api_probes.inc): n cells, nv values per record; the device records of the batch in flight ([log_cap][n][nv],
+    // allocated by the first stepping call after gpf_probes_set); the records of the last stepping call on the host
+    // `dev`: the ProbeArgs of these buffers in device memory, for k_small_steps
+    struct { int n = 0, nv = 0; int* cells = nullptr; double* buf = nullptr; ProbeArgs* dev = nullptr; std::vector<double> host;
+             long long first_step = 0; } probes;
     double* stage = nullptr;                // contiguous staging for upload/download
     size_t stage_doubles = 0;
     // unfused pipeline scratch (lazy)
@@ -313,7 +319,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -933,6 +939,8 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
     return GPF_OK;
 }
 
+#include "api_probes.inc"
+
 // Problems that fit one workgroup's LDS advance whole batches of steps in one launch (small_kernel.hip).
 static bool small_grid_eligible(gpf_handle* h) {
     static const bool off = getenv("GPF_SMALL_GRID") && atoi(getenv("GPF_SMALL_GRID")) == 0;
@@ -946,6 +954,7 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
     SmallArgs a;
     a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
     a.log = h->log; a.log_base = log_base; a.log_cap = h->log_cap; a.L = L; a.E = h->E; a.nsteps = nsteps; a.honor_stop = honor_stop;
+    a.probe = h->probes.n ? h->probes.dev : nullptr;
     const size_t lds = (size_t)(L.Nx + 2) * (L.Ny + 2) * SMALL_DOUBLES_PER_CELL * 8;
     EOS_DISPATCH(h->cfg.eos, {
         if (h->Ls) {
@@ -973,14 +982,19 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     GPF_TRY(enter(h));
     int64_t done = 0, logged = 0;
     const bool small = small_grid_eligible(h);
+    GPF_TRY(probes_begin(h));
     while (done < n) {
         const int64_t batch = std::min<int64_t>(n - done, h->log_cap);
         const long long base = h->host_step;
         if (small) GPF_TRY(enqueue_small_steps(h, (int)batch, honor_stop, base));
-        else for (int64_t i = 0; i < batch; ++i) GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
+        else for (int64_t i = 0; i < batch; ++i) {
+            GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
+            GPF_TRY(probes_launch(h, base + i + 1, base));      // no launch without probes
+        }
         StepState s;
         GPF_TRY(read_state(h, s));
         const long long ran = s.step - base;
+        GPF_TRY(probes_collect(h, ran));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);
         if (log && entries > 0) {
             const long long take = std::min<long long>(entries, log_capacity - logged);

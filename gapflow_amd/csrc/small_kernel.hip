@@ -18,6 +18,7 @@ struct SmallArgs {
     LogEntry* log; long long log_base, log_cap;
     Layout L; Edges E;
     int nsteps, honor_stop;
+    const ProbeArgs* probe; // point probes (probe_kernels.hip), in device memory; null: none
 };
 
 template <int EOS, bool HAS_LS>
@@ -142,6 +143,7 @@ __global__ __launch_bounds__(512) void k_small_steps(const SmallArgs a, const Ph
         if (sh_flags[1]) break;                     // rolled back: q0 still holds the last valid state
         double* tmp = q0; q0 = q; q = tmp;          // the averaged field is the current one now
         committed += 1;
+        if (a.probe) probe_record_block<EOS>(*a.probe, q0, nc, w, st->step - 1 - a.log_base, a.log_cap, P);     // block-uniform; reads only
     }
     // the current state -> the buffer the (final) parity designates; the run state back to global memory
     __syncthreads();

@@ -29,6 +29,8 @@ from .stress import Pressure, WallStress, BulkStress
 
 GapProfiles = namedtuple('GapProfiles', 'z u v tau')
 GapProfiles.__doc__ = """Through-gap profiles of Problem.gap_profiles: z, u, v (nz, nrows, Ny+2), tau (6, nz, nrows, Ny+2); None if not asked for."""
+ProbeSeries = namedtuple('ProbeSeries', 'step time cells rho jx jy p')
+ProbeSeries.__doc__ = """Time series of Problem.probes: step, time (nrecords,), cells (nprobes, 2), rho, jx, jy, p (nrecords, nprobes); p None if not asked for."""
 
 
 def _termination_signals():
@@ -105,6 +107,9 @@ class Problem:
         self.history = {k: [] for k in ('step', 'time', 'ekin', 'residual', 'vsound')}
         self._restart_history = None            # from_checkpoint: the saved run's history, which run() continues
         self._has_extra_field = extra_field is not None
+        self._probe_cells = None
+        if options.get('probes') is not None:       # options.probes (from the YAML text, or carried by a checkpoint's dictionaries)
+            self.set_probes(options['probes'], pressure=bool(options.get('probes_pressure', True)))
 
         if not options['silent']:
             self.outdir = create_output_directory(options['output'], options['use_tstamp'])
@@ -141,6 +146,7 @@ class Problem:
         with _io.StringIO(ymlstring) as f:
             input_dict = read_yaml_input(f)
         _keep_checkpoint_freq(input_dict, ymlstring)
+        _keep_probes(input_dict, ymlstring)
         return cls._from_dict(input_dict, device=device)
 
     @classmethod
@@ -421,6 +427,69 @@ class Problem:
         self.save_checkpoint(os.path.join(self.outdir, 'checkpoint.gpf'))
 
     # -------------------------------------------------------------------------------------
+    # point probes (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def set_probes(self, cells, pressure=True):
+        """Record rho, jx, jy (and p) at `cells` after every committed step, on the device, whichever way the steps are taken
+        (`update()`, `run()`, batches of any length): the series is what reading ``q`` after every single step would give,
+        bit for bit, without leaving the batched path.
+
+        cells: up to 256 pairs (ix, iy) of the ghosted index space, 0 <= ix <= Nx+1, 0 <= iy <= Ny+1 -- ghost cells are legal,
+        that is where boundary conditions show.  pressure: also keep p = eos_pressure(rho), the equation of state applied to
+        the COMMITTED density by the device function `models.pressure.eos_pressure` runs -- not the corrector-stage pressure
+        that the ``pressure`` member holds after a step.  Not available with a pressure surrogate.
+        A step that is rolled back as invalid leaves no record.  Starts a new series (see ``probes``).  Checkpoints do not carry
+        the series: a problem restored from one whose options hold `probes` has them armed again and its series begins at
+        the restart step."""
+        cells = _probe_cells(cells, self._shape)
+        if pressure and self._gp_models.get('zz') is not None:
+            raise ValueError("probes: pressure=True records the equation of state's pressure; this problem's pressure is a surrogate")
+        ix = np.ascontiguousarray(cells[:, 0], dtype=np.int32)
+        iy = np.ascontiguousarray(cells[:, 1], dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(self._lib.gpf_probes_set(self._h, len(cells), ix.ctypes.data_as(i32p), iy.ctypes.data_as(i32p), int(bool(pressure))))
+        self._probe_cells, self._probe_pressure = cells, bool(pressure)
+        self._probe_steps, self._probe_times, self._probe_data = [], [], []
+
+    def clear_probes(self):
+        """Stop recording and drop the series."""
+        if self._probe_cells is not None:
+            _lib.check(self._lib.gpf_probes_clear(self._h))
+        self._probe_cells = None
+
+    @property
+    def probes(self):
+        """ProbeSeries(step, time, cells, rho, jx, jy, p) of every step committed since set_probes (or _pre_run), across
+        `update()` and `run()` calls; None when no probes are set.  `time` is the simulation time the scalar log holds for
+        the same steps; p is None unless pressure was asked for."""
+        if self._probe_cells is None:
+            return None
+        n, nv = len(self._probe_cells), 4 if self._probe_pressure else 3
+        data = np.concatenate(self._probe_data) if self._probe_data else np.empty((0, n, nv))
+        return ProbeSeries(np.array(self._probe_steps, dtype=np.int64), np.array(self._probe_times, dtype=np.float64),
+                           self._probe_cells.copy(), data[:, :, 0], data[:, :, 1], data[:, :, 2], data[:, :, 3] if nv == 4 else None)
+
+    def _collect_probes(self, entries):
+        """The probe records of the stepping call that returned `entries` (its committed steps' scalar records)."""
+        if self._probe_cells is None or not entries:
+            return
+        n, nv = len(self._probe_cells), 4 if self._probe_pressure else 3
+        out = np.empty((len(entries), n, nv))
+        first, have = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.gpf_probes_read(self._h, _lib.as_dp(out), len(entries), C.byref(first), C.byref(have)))
+        if have.value != len(entries) or first.value != entries[0].step:
+            raise _lib.GapflowHipError(f"probes: {have.value} records from step {first.value} for {len(entries)} committed steps "
+                                       f"from step {entries[0].step}")
+        self._probe_steps.extend(int(e.step) for e in entries)
+        self._probe_times.extend(e.simtime for e in entries)
+        self._probe_data.append(out)
+
+    def _write_probes(self):
+        s = self.probes
+        arrays = {k: v for k, v in s._asdict().items() if v is not None}
+        np.savez(os.path.join(self.outdir, 'probes.npz'), **arrays)
+
+    # -------------------------------------------------------------------------------------
     # run loop (problem.py:368-503)
     # -------------------------------------------------------------------------------------
     def _features(self):
@@ -445,6 +514,8 @@ class Problem:
         self.dt = sc.dt
         self.tol = self.numerics['tol']
         self.max_it = self.numerics['max_it']
+        if self._probe_cells is not None:           # the step count starts over: so does the series
+            self._probe_steps, self._probe_times, self._probe_data = [], [], []
 
     def _absorb(self, entries):
         """Fold the per-step records of a batch into the host-side mirror of the run state."""
@@ -467,6 +538,7 @@ class Problem:
         ran = int(nexec.value) - before
         entries = [log[i] for i in range(ran)]
         self._absorb(entries)
+        self._collect_probes(entries)
         if ran > 0:
             self._mark_device_advanced()
         failed = ran < n and log[ran].invalid != 0 if ran < n else False
@@ -523,6 +595,7 @@ class Problem:
             _lib.check(lib.gpf_elastic_update(h))
             self.topo.mark_stale()
         self._absorb([sc])
+        self._collect_probes([sc])
         self._mark_device_advanced()
         # the derived fields on the device ARE what the reference's field objects hold now: the closures of the corrector stage
         # (problem.py:531-560; neither the averaging nor Topography.update re-evaluates them)
@@ -600,6 +673,8 @@ class Problem:
         print(33 * '=')
         if not silent:
             history_to_csv(os.path.join(self.outdir, 'history.csv'), self.history)
+            if self._probe_cells is not None:
+                self._write_probes()
             for name, m in self._gp_models.items():  # problem.py:490-503
                 history_to_csv(os.path.join(self.outdir, f'gp_{name}.csv'), m.history)
                 with open(os.path.join(self.outdir, f'gp_{name}.txt'), 'w') as f:
@@ -674,6 +749,45 @@ def _keep_checkpoint_freq(input_dict, ymlstring):
     freq = (raw.get('options') or {}).get('checkpoint_freq', 0)
     if input_dict.get('options') is not None:
         input_dict['options']['checkpoint_freq'] = int(freq or 0)
+
+
+def _probe_cells(cells, shape=None):
+    """Probe cells as an (n, 2) integer array; ValueError for anything that is not 1..256 pairs of integers or, when the ghosted
+    shape (Nx+2, Ny+2) is given, for a cell outside it.  Host only: no library call."""
+    if isinstance(cells, (str, bytes, dict)) or not hasattr(cells, '__len__'):
+        raise ValueError(f"probes: a list of [ix, iy] cells is required, got {cells!r}")
+    if len(cells) < 1:
+        raise ValueError("probes: at least one cell is required (clear_probes removes them)")
+    if len(cells) > _lib.PROBE_MAX:
+        raise ValueError(f"probes: {len(cells)} cells, at most {_lib.PROBE_MAX} per problem")
+    out = np.empty((len(cells), 2), dtype=np.int64)
+    for k, c in enumerate(cells):
+        ok = not isinstance(c, (str, bytes, dict)) and hasattr(c, '__len__') and len(c) == 2 and \
+            all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in c)
+        if not ok:
+            raise ValueError(f"probes: entry {k} must be a pair of integers [ix, iy], got {c!r}")
+        ix, iy = int(c[0]), int(c[1])
+        if shape is not None and not (0 <= ix < shape[0] and 0 <= iy < shape[1]):
+            raise ValueError(f"probes: cell ({ix}, {iy}) (entry {k}) lies outside the ghosted grid 0..{shape[0] - 1} x 0..{shape[1] - 1}")
+        out[k] = ix, iy
+    return out
+
+
+def _keep_probes(input_dict, ymlstring):
+    """`options.probes: [[ix, iy], ...]` and `options.probes_pressure` are this project's own keys: read from the YAML text and set
+    beside the sanitised ones, like checkpoint_freq -- but only when given, so that every other input's dictionaries stay as
+    they are.  The cells are checked here, on the host (against the grid, when the input has one)."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    if opts.get('probes') is not None:
+        grid = input_dict.get('grid') or {}
+        shape = (int(grid['Nx']) + 2, int(grid['Ny']) + 2) if 'Nx' in grid and 'Ny' in grid else None
+        input_dict['options']['probes'] = _probe_cells(opts['probes'], shape).tolist()
+        if 'probes_pressure' in opts:
+            input_dict['options']['probes_pressure'] = bool(opts['probes_pressure'])
 
 
 def _in_main_thread():

@@ -415,7 +415,13 @@ class SlabProblem:
         gapflow_amd.models.profiles on it."""
         raise NotImplementedError("gap_profiles: not available on a SlabProblem")
 
+    def set_probes(self, *args, **kwargs):
+        """Point probes are recorded on unsliced problems only."""
+        raise NotImplementedError("probes: not available on a SlabProblem")
+
     def __init__(self, input_dict, device=0, dist=None):
+        if (input_dict.get('options') or {}).get('probes') is not None:
+            raise NotImplementedError("probes: not available on a SlabProblem")      # options.probes: as set_probes
         import torch
         if dist is None:
             import torch.distributed as dist
@@ -542,10 +548,11 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None):
-        from .problem import _keep_checkpoint_freq
+        from .problem import _keep_checkpoint_freq, _keep_probes
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
+        _keep_probes(d, text)                       # options.probes: refused below
         return cls(d, device=device, dist=dist)
 
     @classmethod

@@ -398,6 +398,37 @@ int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes);
  * gpf_checkpoint_save does, without the copies to the host (tools/checkpoint_time.py; yardstick: gpf_stream_probe(3, 3, ...)). */
 int gpf_checkpoint_pack_probe(gpf_handle* h, int reps, double* ms_per_pass);
 
+/* ---- point probes (no reference counterpart: the reference's transient tests read q on the host after every step) -------- */
+/* Per-step time series at up to 256 cells, recorded on the device so that gpf_step keeps advancing whole batches.  A probe is
+ * a cell (ix, iy) of the ghosted index space, 0 <= ix <= Nx+1, 0 <= iy <= Ny+1 (ghost cells show the boundary conditions).
+ * For every step that is executed AND committed, one record per probe is kept: rho, jx, jy of the committed state -- the q a
+ * host would download after that step -- and, with_pressure != 0, p = eos_pressure(rho) of that same state, evaluated with the
+ * handle's constants by the device function gpf_eos uses.  p is the pressure OF THE COMMITTED STATE, not the corrector-stage
+ * pressure plane of the derived fields (GPF_FIELD_PRESSURE).  A step that did not run (converged / max_it under honor_stop)
+ * leaves no record, nor does one that was rolled back as invalid: the scalar log keeps its entry for the invalid step, the
+ * probe series ends one entry earlier.  Recording only reads: q and all scalars of a run are bitwise those of the same run
+ * without probes, and with no probes set no launch and no kernel argument of the step kernel differs.
+ *   gpf_probes_set    replaces the handle's probes.  GPF_ERR_INVALID with a message that names the offending probe for a cell
+ *                     out of range, n > 256, or with_pressure on a handle whose pressure comes from a surrogate; GPF_ERR_STATE
+ *                     on a slab handle (halo_lo / halo_hi != 0) and while a stage-wise step is open.
+ *   gpf_probes_clear  removes them and frees the buffers.
+ *   gpf_probes_read   the records of the steps the LAST gpf_step or gpf_close_step call committed (one per closed step), host
+ *                     layout [step][probe][value], value order rho, jx, jy, (p): *first_step is the step count of the first
+ *                     record, *n_steps how many the call left (either may be NULL); min(*n_steps, capacity_steps) records are
+ *                     copied to out (NULL: none).  The next stepping call replaces them.  GPF_ERR_STATE without probes.
+ * Where they are written: one launch of k_probe_record behind every launch-per-step step and behind gpf_close_step, told the
+ * step count its step produces if it commits and writing only if the device's run state shows that count and a valid state;
+ * inside k_small_steps after each commit.  The device buffer, log_cap (4096) x n x values doubles (at most 32 MiB), is
+ * allocated by the first stepping call after gpf_probes_set and freed by gpf_probes_clear / gpf_destroy once the stream is
+ * idle.  gpf_step_unfused records through its gpf_close_step; gpf_step_timed and the slab calls record nothing. */
+int gpf_probes_set(gpf_handle* h, int n, const int32_t* ix, const int32_t* iy, int with_pressure);
+int gpf_probes_clear(gpf_handle* h);
+int gpf_probes_read(gpf_handle* h, double* out, int64_t capacity_steps, int64_t* first_step, int64_t* n_steps);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording (set probes are put aside for the call), 1 k_probe_record behind every step (k_small_steps: recording
+ * inside), 2 an empty kernel in k_probe_record's place -- the floor of one more launch per step (tools/probe_time.py). */
+int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* Diagnostic: time of one pass of an elementwise kernel that reads `nin` and writes `nout` fp64 planes of
  * `doubles_per_plane` elements (16 bytes per lane, grid-stride): what THIS device streams for the byte count of a fused
  * step.  bench.py reports it beside the step kernel's HBM figure (no reference counterpart: the reference has no device). */
