@@ -37,6 +37,8 @@ PROFILE_Z, PROFILE_U, PROFILE_V, PROFILE_TAU = 1, 2, 4, 8          # gpf_gap_pro
 PROFILE_GRADIENTS = 1
 PROFILE_MODES = {'both': 0, 'top': 1, 'bottom': 2, 'none': 3}
 PROBE_MAX = 256                     # gpf_probes_set: cells per handle
+INTEGRAL_MAX_SECTIONS = 8           # gpf_integrals_set: flow cross-sections per direction
+INTEGRAL_SUMS = ('load', 'load_x', 'load_y', 'p_hx', 'p_hy', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -137,6 +139,11 @@ SIGNATURES = {
     'gpf_probes_clear': (C.c_int, [C.c_void_p]),
     'gpf_probes_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_probes_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_integrals_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
+    'gpf_integrals_clear': (C.c_int, [C.c_void_p]),
+    'gpf_integrals_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_integrals_now': (C.c_int, [C.c_void_p, _DP, C.c_int64]),
+    'gpf_integrals_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@
 #include "small_kernel.hip"
 #include "profile_kernels.hip"
 #include "checkpoint_kernels.hip"
+#include "integral_kernels.hip"
 
 using namespace gpf;
 
@@ -98,6 +99,11 @@ struct gpf_handle {
     // `dev`: the ProbeArgs of these buffers in device memory, for k_small_steps
     struct { int n = 0, nv = 0; int* cells = nullptr; double* buf = nullptr; ProbeArgs* dev = nullptr; std::vector<double> host;
              long long first_step = 0; } probes;
+    // film integrals (api_integrals.inc): recording stride (0: not armed), sections (nsx 0: not chosen yet), the device records of
+    // the batch in flight ([log_cap + 1][9 + nsx + nsy]) and the row scratch ([Nx][FILM_NV]), both allocated on first use (`narrow`:
+    // GPF_FILM_NARROW was set then, 8-byte loads); the records of the last stepping call and their step counts on the host
+    struct { long long every = 0; int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
+             double* rec = nullptr; double* part = nullptr; bool narrow = false; std::vector<double> host; std::vector<long long> steps; } integ;
     double* stage = nullptr;                // contiguous staging for upload/download
     size_t stage_doubles = 0;
     // unfused pipeline scratch (lazy)
@@ -319,7 +325,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -971,6 +977,8 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
     return GPF_OK;
 }
 
+#include "api_integrals.inc"
+
 extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t* log, int64_t log_capacity,
                         int64_t* n_executed) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
@@ -983,18 +991,22 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     int64_t done = 0, logged = 0;
     const bool small = small_grid_eligible(h);
     GPF_TRY(probes_begin(h));
+    GPF_TRY(integrals_begin(h));
     while (done < n) {
         const int64_t batch = std::min<int64_t>(n - done, h->log_cap);
         const long long base = h->host_step;
-        if (small) GPF_TRY(enqueue_small_steps(h, (int)batch, honor_stop, base));
+        if (small && h->integ.every) GPF_TRY(integrals_small_batch(h, batch, honor_stop, base));     // the batch, cut at the recorded steps
+        else if (small) GPF_TRY(enqueue_small_steps(h, (int)batch, honor_stop, base));
         else for (int64_t i = 0; i < batch; ++i) {
             GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
             GPF_TRY(probes_launch(h, base + i + 1, base));      // no launch without probes
+            GPF_TRY(integrals_launch(h, base + i + 1, base));   // nor without integrals, nor off their stride
         }
         StepState s;
         GPF_TRY(read_state(h, s));
         const long long ran = s.step - base;
         GPF_TRY(probes_collect(h, ran));
+        GPF_TRY(integrals_collect(h, base, ran));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);
         if (log && entries > 0) {
             const long long take = std::min<long long>(entries, log_capacity - logged);

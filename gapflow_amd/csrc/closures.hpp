@@ -247,6 +247,23 @@ GPF_HD double eos_pressure(double rho, const Phys& P) {
     }
 }
 
+// The pressure the film integrals' load is made of (integral_kernels.hip).  Dowson-Higginson, p = P0 + C1 (s - 1) / (C2 - s) with
+// s = rho / rho0, is stiff: near rho0 it turns a relative change d of s into C1 / ((C2 - s) p) d of p, 1.5e6 d for C1 = 3.5e10
+// against P0 = 1e5.  eos_pressure<EOS_DH> above forms s = rho * (1 / rho0) with a reciprocal rounded once on the host; that is up
+// to an ulp of s away from the reference's rho / rho0, with one sign for all cells, so a sum over the film would sit 1e-10 of
+// itself beside the reference's (pressure.py:79-109) where the wall stresses and flow rates sit at 1e-15.  Here the law is
+// evaluated as the reference writes it, with IEEE divisions.  SAME clamp and SAME formula as eos_pressure<EOS_DH>: change them
+// together (tests/test_integrals_host.py holds the two within the amplified rounding of each other).  The step kernels, the
+// derived fields and the probes keep eos_pressure; the other laws have no such amplification and use it here too.
+template <int EOS>
+GPF_HD double film_pressure(double rho, const Phys& P) {
+    if (EOS == EOS_DH) {
+        const double s = fmin(rho, P.e[4]) / P.e[0];
+        return P.e[1] + (P.e[2] * (s - 1.0)) / (P.e[3] - s);
+    }
+    return eos_pressure<EOS>(rho, P);
+}
+
 // dp/drho (the square of the sound speed); NaN/negative values propagate like np.sqrt would.
 template <int EOS>
 GPF_HD double eos_c2(double rho, const Phys& P) {

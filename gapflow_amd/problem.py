@@ -31,6 +31,8 @@ GapProfiles = namedtuple('GapProfiles', 'z u v tau')
 GapProfiles.__doc__ = """Through-gap profiles of Problem.gap_profiles: z, u, v (nz, nrows, Ny+2), tau (6, nz, nrows, Ny+2); None if not asked for."""
 ProbeSeries = namedtuple('ProbeSeries', 'step time cells rho jx jy p')
 ProbeSeries.__doc__ = """Time series of Problem.probes: step, time (nrecords,), cells (nprobes, 2), rho, jx, jy, p (nrecords, nprobes); p None if not asked for."""
+FilmIntegrals = namedtuple('FilmIntegrals', ('step', 'time') + _lib.INTEGRAL_SUMS + ('flow_x', 'flow_y', 'sections_x', 'sections_y'))
+FilmIntegrals.__doc__ = """Time series of Problem.integrals: step, time and the nine area integrals (nrecords,), flow_x (nrecords, len(sections_x)), flow_y (nrecords, len(sections_y)), the sections' interior rows / columns."""
 
 
 def _termination_signals():
@@ -110,6 +112,9 @@ class Problem:
         self._probe_cells = None
         if options.get('probes') is not None:       # options.probes (from the YAML text, or carried by a checkpoint's dictionaries)
             self.set_probes(options['probes'], pressure=bool(options.get('probes_pressure', True)))
+        self._integral_every = None
+        if options.get('integrals') is not None:    # options.integrals (from the YAML text, or carried by a checkpoint's dictionaries)
+            self.set_integrals(options['integrals'], options.get('integrals_sections_x'), options.get('integrals_sections_y'))
 
         if not options['silent']:
             self.outdir = create_output_directory(options['output'], options['use_tstamp'])
@@ -147,6 +152,7 @@ class Problem:
             input_dict = read_yaml_input(f)
         _keep_checkpoint_freq(input_dict, ymlstring)
         _keep_probes(input_dict, ymlstring)
+        _keep_integrals(input_dict, ymlstring)
         return cls._from_dict(input_dict, device=device)
 
     @classmethod
@@ -490,6 +496,104 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'probes.npz'), **arrays)
 
     # -------------------------------------------------------------------------------------
+    # film integrals (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _integrals_refusal(self):
+        if self.has_gp_model or self._gp_models:
+            raise NotImplementedError("integrals: surrogate (GP) closures replace the pressure and wall stress the integrals evaluate")
+        if self._cfg.thinning:
+            raise NotImplementedError("integrals: shear thinning needs grad p, which the reduction does not model")
+        if self._elastic or self.topo.elastic:
+            raise NotImplementedError("integrals: an elastic gap steps stage-wise and deforms between steps (not supported)")
+
+    def set_integrals(self, every=1, sections_x=None, sections_y=None):
+        """Record whole-film integrals of the committed state after every step whose count is a multiple of `every`, on the
+        device, whichever way the steps are taken (`update()`, `run()`, batches of any length).
+
+        Per record, summed over the interior cells and multiplied by dx dy: load = p (the equation of state's pressure of the
+        committed density; Dowson-Higginson as the reference writes it, with rho / rho0 divided, so that the sum sits at rounding
+        distance from the reference's -- the probes' p may differ from it by 1e-10 of p for a stiff law), load_x, load_y = p x, p y at the cell centres of `topography.create_midpoint_grid`
+        (centre of pressure: load_x / load), p_hx, p_hy = p dh/dx, p dh/dy (the pressure's in-plane resultant on the profiled
+        wall), tau_xz_bot, tau_yz_bot, tau_xz_top, tau_yz_top = the walls' shear stresses, evaluated on the state with the
+        closures' viscosity; and the mass-flow rates flow_x[k] = sum_iy jx h dy on interior row sections_x[k], flow_y[k] =
+        sum_ix jy h dx on interior column sections_y[k] (at most 8 each; default: first and last interior row / column).
+        These are plain integrals of the named fields: NO sign convention (outward normals, which wall acts on which) is applied.
+        The same state gives the same bits whatever the batch size or stride.  On grids small enough for the one-workgroup
+        kernel the batch is cut at every recorded step: choose a stride there (every=1 costs one launch per step).
+        A step that is rolled back as invalid leaves no record.  Starts a new series (see ``integrals``).  Checkpoints do not
+        carry the series: a problem restored from one whose options hold `integrals` has them armed again and its series
+        begins at the restart step.  Not available with surrogate closures, shear thinning or an elastic gap."""
+        self._integrals_refusal()
+        every = _integral_stride(every)
+        sx = _integral_sections(sections_x, self.grid['Nx'], 'sections_x')
+        sy = _integral_sections(sections_y, self.grid['Ny'], 'sections_y')
+        ax, ay = np.array(sx, dtype=np.int32), np.array(sy, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        _lib.check(self._lib.gpf_integrals_set(self._h, every, len(sx), ax.ctypes.data_as(i32p), len(sy), ay.ctypes.data_as(i32p)))
+        self._integral_every, self._integral_sections = every, (sx, sy)
+        self._integral_steps, self._integral_times, self._integral_data = [], [], []
+
+    def clear_integrals(self):
+        """Stop recording and drop the series."""
+        if self._integral_every is not None:
+            _lib.check(self._lib.gpf_integrals_clear(self._h))
+        self._integral_every = None
+
+    def _integral_layout(self):
+        if self._integral_every is not None:
+            return self._integral_sections
+        return _integral_sections(None, self.grid['Nx'], 'sections_x'), _integral_sections(None, self.grid['Ny'], 'sections_y')
+
+    @property
+    def integrals(self):
+        """FilmIntegrals(step, time, load, ..., flow_x, flow_y, sections_x, sections_y) of every recorded step since
+        set_integrals (or _pre_run), across `update()` and `run()` calls; None when no integrals are armed."""
+        if self._integral_every is None:
+            return None
+        sx, sy = self._integral_sections
+        ns = len(_lib.INTEGRAL_SUMS)
+        data = np.concatenate(self._integral_data) if self._integral_data else np.empty((0, ns + len(sx) + len(sy)))
+        return FilmIntegrals(np.array(self._integral_steps, dtype=np.int64), np.array(self._integral_times, dtype=np.float64),
+                             *[data[:, k] for k in range(ns)], data[:, ns:ns + len(sx)], data[:, ns + len(sx):],
+                             np.array(sx, dtype=np.int64), np.array(sy, dtype=np.int64))
+
+    def film_integrals(self):
+        """The same record for the current state, as a dict of the names of ``integrals`` (flow_x, flow_y arrays over the
+        sections): bit for bit what a step committing this state would have recorded.  Armed or not (then with the default
+        sections).  Reads only."""
+        self._integrals_refusal()
+        self._sync_to_device()
+        sx, sy = self._integral_layout()
+        ns = len(_lib.INTEGRAL_SUMS)
+        out = np.empty(ns + len(sx) + len(sy))
+        _lib.check(self._lib.gpf_integrals_now(self._h, _lib.as_dp(out), out.size))
+        res = {name: np.float64(out[k]) for k, name in enumerate(_lib.INTEGRAL_SUMS)}
+        res.update(flow_x=out[ns:ns + len(sx)].copy(), flow_y=out[ns + len(sx):].copy(),
+                   sections_x=np.array(sx, dtype=np.int64), sections_y=np.array(sy, dtype=np.int64))
+        return res
+
+    def _collect_integrals(self, entries, before):
+        """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
+        if self._integral_every is None or not entries:
+            return
+        n = _integral_records(before, len(entries), self._integral_every)
+        sx, sy = self._integral_sections
+        out = np.empty((n, len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy)))
+        steps = np.zeros(n, dtype=np.int64)
+        have = C.c_int64(0)
+        _lib.check(self._lib.gpf_integrals_read(self._h, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
+        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._integral_every == 0]
+        if have.value != n or steps.tolist() != want:
+            raise _lib.GapflowHipError(f"integrals: {have.value} records of steps {steps.tolist()} for the committed steps "
+                                       f"{before + 1}..{before + len(entries)} at stride {self._integral_every}")
+        self._integral_steps.extend(want)
+        self._integral_times.extend(entries[s - before - 1].simtime for s in want)
+        self._integral_data.append(out)
+
+    def _write_integrals(self):
+        np.savez(os.path.join(self.outdir, 'integrals.npz'), **self.integrals._asdict())
+
+    # -------------------------------------------------------------------------------------
     # run loop (problem.py:368-503)
     # -------------------------------------------------------------------------------------
     def _features(self):
@@ -516,6 +620,8 @@ class Problem:
         self.max_it = self.numerics['max_it']
         if self._probe_cells is not None:           # the step count starts over: so does the series
             self._probe_steps, self._probe_times, self._probe_data = [], [], []
+        if self._integral_every is not None:
+            self._integral_steps, self._integral_times, self._integral_data = [], [], []
 
     def _absorb(self, entries):
         """Fold the per-step records of a batch into the host-side mirror of the run state."""
@@ -539,6 +645,7 @@ class Problem:
         entries = [log[i] for i in range(ran)]
         self._absorb(entries)
         self._collect_probes(entries)
+        self._collect_integrals(entries, before)
         if ran > 0:
             self._mark_device_advanced()
         failed = ran < n and log[ran].invalid != 0 if ran < n else False
@@ -675,6 +782,8 @@ class Problem:
             history_to_csv(os.path.join(self.outdir, 'history.csv'), self.history)
             if self._probe_cells is not None:
                 self._write_probes()
+            if self._integral_every is not None:
+                self._write_integrals()
             for name, m in self._gp_models.items():  # problem.py:490-503
                 history_to_csv(os.path.join(self.outdir, f'gp_{name}.csv'), m.history)
                 with open(os.path.join(self.outdir, f'gp_{name}.txt'), 'w') as f:
@@ -788,6 +897,55 @@ def _keep_probes(input_dict, ymlstring):
         input_dict['options']['probes'] = _probe_cells(opts['probes'], shape).tolist()
         if 'probes_pressure' in opts:
             input_dict['options']['probes_pressure'] = bool(opts['probes_pressure'])
+
+
+def _integral_records(base, ran, every):
+    """Records a stepping call leaves that took the step count from `base` over `ran` committed steps at stride `every`: the
+    multiples of `every` in (base, base + ran].  The slot of the step that takes the count to `expect` is
+    _integral_records(base, expect - base, every) - 1 (csrc/api_integrals.inc: integrals_count)."""
+    return (base + ran) // every - base // every if ran > 0 else 0
+
+
+def _integral_stride(every):
+    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError(f"integrals: the stride must be an integer >= 1, got {every!r}")
+    return int(every)
+
+
+def _integral_sections(sections, n, what):
+    """Interior rows / columns of the flow sections as a list of ints; None: the first and last of 1..n (one where n == 1).
+    ValueError for anything that is not 1..8 integers within 1..n.  Host only: no library call."""
+    if sections is None:
+        return [1, n] if n > 1 else [1]
+    if isinstance(sections, (str, bytes, dict)) or not hasattr(sections, '__len__'):
+        raise ValueError(f"integrals: {what} must be a list of interior indices, got {sections!r}")
+    if not 1 <= len(sections) <= _lib.INTEGRAL_MAX_SECTIONS:
+        raise ValueError(f"integrals: {what} holds {len(sections)} sections, 1 to {_lib.INTEGRAL_MAX_SECTIONS} required")
+    out = []
+    for k, v in enumerate(sections):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"integrals: {what}[{k}] must be an integer, got {v!r}")
+        if not 1 <= int(v) <= n:
+            raise ValueError(f"integrals: {what}[{k}] = {int(v)} lies outside the interior 1..{n}")
+        out.append(int(v))
+    return out
+
+
+def _keep_integrals(input_dict, ymlstring):
+    """`options.integrals: N` (the stride) and `options.integrals_sections_x / _y` are this project's own keys: read from the YAML
+    text and set beside the sanitised ones, like the probes' -- only when given, so that every other input's dictionaries stay
+    as they are.  Checked here, on the host (the sections against the grid, when the input has one)."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    if opts.get('integrals') is not None:
+        grid = input_dict.get('grid') or {}
+        input_dict['options']['integrals'] = _integral_stride(opts['integrals'])
+        for key, n in (('integrals_sections_x', 'Nx'), ('integrals_sections_y', 'Ny')):
+            if opts.get(key) is not None:
+                input_dict['options'][key] = _integral_sections(opts[key], int(grid[n]) if n in grid else 2**31 - 1, key)
 
 
 def _in_main_thread():

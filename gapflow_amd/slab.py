@@ -419,9 +419,19 @@ class SlabProblem:
         """Point probes are recorded on unsliced problems only."""
         raise NotImplementedError("probes: not available on a SlabProblem")
 
+    def set_integrals(self, *args, **kwargs):
+        """Film integrals are reduced on unsliced problems only."""
+        raise NotImplementedError("integrals: not available on a SlabProblem")
+
+    def film_integrals(self, *args, **kwargs):
+        """Film integrals are reduced on unsliced problems only."""
+        raise NotImplementedError("integrals: not available on a SlabProblem")
+
     def __init__(self, input_dict, device=0, dist=None):
         if (input_dict.get('options') or {}).get('probes') is not None:
             raise NotImplementedError("probes: not available on a SlabProblem")      # options.probes: as set_probes
+        if (input_dict.get('options') or {}).get('integrals') is not None:
+            raise NotImplementedError("integrals: not available on a SlabProblem")   # options.integrals: as set_integrals
         import torch
         if dist is None:
             import torch.distributed as dist
@@ -548,11 +558,12 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes
+        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
         _keep_probes(d, text)                       # options.probes: refused below
+        _keep_integrals(d, text)                    # options.integrals: refused below
         return cls(d, device=device, dist=dist)
 
     @classmethod

@@ -429,6 +429,55 @@ int gpf_probes_read(gpf_handle* h, double* out, int64_t capacity_steps, int64_t*
  * inside), 2 an empty kernel in k_probe_record's place -- the floor of one more launch per step (tools/probe_time.py). */
 int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- film integrals (no reference counterpart: the reference leaves load, friction and flow rates to post-processing) ---- */
+/* Whole-film integrals of the COMMITTED state, reduced on the device so that gpf_step keeps advancing whole batches.  A record
+ * is 9 + nsx + nsy doubles: the sums over the interior cells (1..Nx x 1..Ny), times dx dy, of
+ *   load                      p, the equation of state's pressure of the committed density.  Dowson-Higginson is evaluated as
+ *                             the reference writes it, rho / rho0 with IEEE divisions: near rho0 that stiff law turns the
+ *                             last bit of rho * (1 / rho0) -- the form the probes' p and the step kernels use -- into up
+ *                             to 1e-10 of p with one sign for all cells, which a sum over the film would keep.  So for
+ *                             that law `load` is NOT the sum of the probes' p / GPF_FIELD_PRESSURE in every bit: it stands
+ *                             about 1e-10 of itself beside it (csrc/closures.hpp film_pressure)
+ *   load_x, load_y            p x, p y with the cell centres x = (ix - 1/2) dx, y = (iy - 1/2) dy (centre of pressure: load_x / load)
+ *   p_hx, p_hy                p dh/dx, p dh/dy: the pressure's in-plane resultant on the profiled wall
+ *   tau_xz_bot, tau_yz_bot    the lower wall's shear stress (GPF_FIELD_WALL_LOWER components 4, 3 evaluated on the state)
+ *   tau_xz_top, tau_yz_top    the upper wall's (GPF_FIELD_WALL_UPPER components 4, 3)
+ * then flow_x[k] = sum over iy of jx h dy on interior row ix[k], then flow_y[k] = sum over ix of jy h dx on interior column
+ * iy[k] (at most 8 sections each; default: the first and last interior row / column, one where the extent is 1).  These are
+ * plain area / line integrals of the named fields: no sign convention (outward normal, which wall pushes which) is applied.
+ * Gap planes and slip-length field are the handle's, U, V and the viscosity (piezo-viscosity included) the closures'.
+ * A record is a pure function of the state: the summation order is fixed by (Nx, Ny) alone, so the same state gives the same
+ * bits whatever the batch size or stride, behind a step or from gpf_integrals_now.  Recording only reads.
+ *   gpf_integrals_set    arms recording after every committed step whose new step count is a multiple of `every` (>= 1) and
+ *                        starts with empty records.  ix / iy NULL (or nsx / nsy <= 0): the default sections.  GPF_ERR_INVALID
+ *                        with a message that names the offending section for a row outside 1..Nx, a column outside 1..Ny or
+ *                        more than 8; GPF_ERR_STATE on a slab and while a stage-wise step is open; GPF_ERR_INVALID with
+ *                        surrogate closures, shear thinning or an elastic gap (such handles step stage-wise).
+ *   gpf_integrals_clear  disarms and frees the buffers.
+ *   gpf_integrals_read   the records of the LAST gpf_step call, [record][9 + nsx + nsy], and the step count of each in
+ *                        steps_out (either may be NULL); *n_records how many the call left, min(*n_records, capacity_records)
+ *                        are copied.  A batch that stopped on the device leaves the records of the steps that ran; a step that
+ *                        was rolled back as invalid leaves none.  GPF_ERR_STATE unless armed.
+ *   gpf_integrals_now    the same record for the current committed state (armed or not: not armed, with the default
+ *                        sections), by the same two kernels; `count`: doubles `out` holds.
+ * Where they are written: k_film_partial + k_film_fold (csrc/integral_kernels.hip) behind the step's launch, told the step
+ * count the step produces if it commits and writing only if the device's run state shows that count and a valid state.  On
+ * grids small enough for k_small_steps the batch is cut at the recorded steps (bitwise the same run): with every = 1 that is
+ * one launch per step again, so choose a stride there.  gpf_close_step, gpf_step_timed and the slab calls record nothing.  The
+ * record buffer ((log_cap + 1) records) and a row scratch (Nx x 18 doubles) are allocated on first use and freed by
+ * gpf_integrals_clear / gpf_destroy once the stream is idle.  k_film_partial fetches two columns with one 16-byte load per
+ * plane where the layout and the buffers are aligned for it (always, today) and with 8-byte loads otherwise, adding in the same
+ * order.  Environment variable GPF_FILM_NARROW (any value, read when those buffers are allocated): take the 8-byte loads
+ * regardless -- a test switch; the records are the same in every bit. */
+int gpf_integrals_set(gpf_handle* h, int64_t every, int nsx, const int32_t* ix, int nsy, const int32_t* iy);
+int gpf_integrals_clear(gpf_handle* h);
+int gpf_integrals_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_integrals_now(gpf_handle* h, double* out, int64_t count);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording (armed integrals are put aside for the call), 1 recording at the armed stride (tools/integrals_time.py).
+ * Probes are put aside in both modes. */
+int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* Diagnostic: time of one pass of an elementwise kernel that reads `nin` and writes `nout` fp64 planes of
  * `doubles_per_plane` elements (16 bytes per lane, grid-stride): what THIS device streams for the byte count of a fused
  * step.  bench.py reports it beside the step kernel's HBM figure (no reference counterpart: the reference has no device). */
