@@ -12,3 +12,4 @@ __version__ = "0.1.0"
 
 from .problem import Problem  # noqa: E402,F401
 from .gp import Database  # noqa: E402,F401  (GaPFlow/__init__.py:36)
+from .ensemble import Ensemble  # noqa: E402,F401  (no reference counterpart: many small problems in one launch)

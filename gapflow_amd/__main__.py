@@ -8,6 +8,9 @@ Several GPUs of one node: start one process per GPU,
 and the problem is cut into x-slabs (gapflow_amd/slab.py); rank 0 writes the output.  GPF_SLAB_TRANSPORT=p2p selects the
 peer-to-peer mailbox transport instead of one all-gather per step.
 
+``python -m gapflow_amd -i a.yaml b.yaml c.yaml`` runs several small problems together as an ensemble, one workgroup of one
+launch each (gapflow_amd/ensemble.py); every one of them writes what it would write run alone.
+
 ``python -m gapflow_amd --restart out/checkpoint.gpf [--output DIR] [--max-it N]`` continues a run from a checkpoint."""
 import argparse
 import os
@@ -16,11 +19,18 @@ import sys
 from . import Problem
 
 
+class _InputFiles(argparse.Action):
+    """`filename` stays the (first) file, a string as ever; `filenames` holds all of them."""
+    def __call__(self, parser, namespace, values, option_string=None):
+        namespace.filename, namespace.filenames = values[0], list(values)
+
+
 def make_parser():
     cli = argparse.ArgumentParser(prog='python -m gapflow_amd',
                                   description="Advance a GaPFlow YAML problem on an MI355X.")
     src = cli.add_mutually_exclusive_group(required=True)
-    src.add_argument('-i', '--input', dest='filename', metavar='YAML', help="problem definition")
+    src.add_argument('-i', '--input', dest='filename', metavar='YAML', nargs='+', action=_InputFiles,
+                     help="problem definition; several files: run them together as an ensemble (each must fit the one-workgroup kernel)")
     src.add_argument('--restart', metavar='CHECKPOINT', help="continue the run a checkpoint file was written from (options.checkpoint_freq, "
                      "Problem.save_checkpoint); slab runs: the name without .rankNNN, on the same number of processes")
     cli.add_argument('--output', metavar='DIR', help="with --restart: a new output directory for the continued run (default: the saved run's "
@@ -53,7 +63,10 @@ def main(argv=None):
     opts = cli.parse_args(argv)
     if opts.restart is None and (opts.output or opts.max_it is not None):
         cli.error("--output and --max-it go with --restart")
+    several = len(getattr(opts, 'filenames', None) or []) > 1
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        if several:
+            cli.error("several -i files run as an ensemble on one GPU; a multi-process (slab) run takes one")
         import torch
         import torch.distributed as dist
         from .slab import SlabProblem
@@ -72,6 +85,9 @@ def main(argv=None):
     if opts.restart:
         options, numerics = restart_overrides(opts)
         Problem.from_checkpoint(opts.restart, device=opts.device, options=options, numerics=numerics).run()
+    elif several:
+        from .ensemble import Ensemble
+        Ensemble.from_yaml(opts.filenames, device=opts.device).run()
     else:
         Problem.from_yaml(opts.filename, device=opts.device).run()
     return 0

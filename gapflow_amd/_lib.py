@@ -38,6 +38,10 @@ PROFILE_GRADIENTS = 1
 PROFILE_MODES = {'both': 0, 'top': 1, 'bottom': 2, 'none': 3}
 PROBE_MAX = 256                     # gpf_probes_set: cells per handle
 INTEGRAL_MAX_SECTIONS = 8           # gpf_integrals_set: flow cross-sections per direction
+# what the host needs of the library's limits without loading it (sweeps and batch lengths are planned on the host); load()
+# compares them with gpf_ensemble_limits, so a library built with other values does not load
+SMALL_GRID_LDS_BYTES, SMALL_GRID_DOUBLES_PER_CELL = 150 * 1024, 16      # what one workgroup's LDS takes (csrc/api.hip)
+LOG_CAPACITY = 4096                 # per-step records a handle's device log holds: the longest batch
 INTEGRAL_SUMS = ('load', 'load_x', 'load_y', 'p_hx', 'p_hy', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
@@ -144,6 +148,11 @@ SIGNATURES = {
     'gpf_integrals_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_integrals_now': (C.c_int, [C.c_void_p, _DP, C.c_int64]),
     'gpf_integrals_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_ensemble_create': (C.c_int, [_VPP, C.c_int, _VPP]),
+    'gpf_ensemble_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]),
+    'gpf_ensemble_log': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfScalars), C.c_int64, C.POINTER(C.c_int64)]),
+    'gpf_ensemble_destroy': (C.c_int, [C.c_void_p]),
+    'gpf_ensemble_limits': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
 }
 
 _lib = None
@@ -231,6 +240,12 @@ def load():
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
+        lds, per_cell, steps = C.c_int64(SMALL_GRID_LDS_BYTES), C.c_int32(SMALL_GRID_DOUBLES_PER_CELL), C.c_int64(LOG_CAPACITY)
+        if 'gpf_ensemble_limits' in SIGNATURES:     # (tools/ensemble_time.py --solo-only drops the ensemble entries to time an older build)
+            lib.gpf_ensemble_limits(C.byref(lds), C.byref(per_cell), C.byref(steps))
+        if (lds.value, per_cell.value, steps.value) != (SMALL_GRID_LDS_BYTES, SMALL_GRID_DOUBLES_PER_CELL, LOG_CAPACITY):
+            raise GapflowHipError(f"{LIB_PATH} was built with other limits (LDS bytes, doubles per cell, log capacity) = "
+                                  f"{(lds.value, per_cell.value, steps.value)} than gapflow_amd/_lib.py states")
         _lib = lib
     return _lib
 

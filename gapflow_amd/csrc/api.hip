@@ -56,6 +56,8 @@ static int enter(gpf_handle* h, bool reads_only = false);
 static_assert(sizeof(LogEntry) == sizeof(gpf_scalars_t), "LogEntry must mirror gpf_scalars_t");
 // k_step2's 16-byte pair loads may reach one pair past the last column of the last row of a buffer
 static constexpr size_t PLANE_PAD_BYTES = 256;
+static constexpr long long LOG_CAPACITY = 4096;                 // per-step records a handle's device log holds: the longest batch
+static constexpr long long SMALL_GRID_LDS_BYTES = 150 * 1024;   // what k_small_steps may take of a CU's 160 KB of LDS (gpf_ensemble_limits)
 
 struct gpf_handle {
     gpf_config cfg;
@@ -312,7 +314,7 @@ extern "C" int gpf_create(const gpf_config* cfg, gpf_handle** out) {
     h->nspart = 1024;
     HIP_TRY_C(hipMalloc(&h->spart, (size_t)(h->nspart + 8) * sizeof(ScalarPartial)));
     HIP_TRY_C(hipMemset(h->spart, 0, (size_t)(h->nspart + 8) * sizeof(ScalarPartial)));
-    h->log_cap = 4096;
+    h->log_cap = LOG_CAPACITY;
     HIP_TRY_C(hipMalloc(&h->log, (size_t)h->log_cap * sizeof(LogEntry)));
 #undef HIP_TRY_C
     *out = h;
@@ -948,12 +950,20 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
 #include "api_probes.inc"
 
 // Problems that fit one workgroup's LDS advance whole batches of steps in one launch (small_kernel.hip).
-static bool small_grid_eligible(gpf_handle* h) {
+// Why not (null: it does); gpf_ensemble_create names the reason.
+static const char* small_grid_refusal(gpf_handle* h) {
     static const bool off = getenv("GPF_SMALL_GRID") && atoi(getenv("GPF_SMALL_GRID")) == 0;
     const long long nc = (long long)(h->L.Nx + 2) * (h->L.Ny + 2);
-    return !off && nc * SMALL_DOUBLES_PER_CELL * 8 <= 150 * 1024 && h->cfg.thinning == GPF_THINNING_NONE && !h->E.halo[0] && !h->E.halo[1] &&
-           !h->gp[0].set && !h->gp[1].set && !h->gp[2].set && !h->el.on;
+    if (off) return "GPF_SMALL_GRID=0 turns the one-workgroup kernel off";
+    if (nc * SMALL_DOUBLES_PER_CELL * 8 > SMALL_GRID_LDS_BYTES) return "its grid does not fit one workgroup's LDS (16 doubles per cell, ghost cells included, in 150 KB)";
+    if (h->cfg.thinning != GPF_THINNING_NONE) return "shear thinning steps stage-wise (it needs grad p)";
+    if (h->E.halo[0] || h->E.halo[1]) return "it is a slab (halo rows)";
+    if (h->gp[0].set || h->gp[1].set || h->gp[2].set) return "a surrogate model is set (it steps stage-wise)";
+    if (h->el.on) return "its gap is elastic (it steps stage-wise)";
+    return nullptr;
 }
+
+static bool small_grid_eligible(gpf_handle* h) { return small_grid_refusal(h) == nullptr; }
 
 static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long long log_base) {
     const Layout& L = h->L;
@@ -1067,3 +1077,4 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
 #include "api_slab_elastic.inc"
 #include "api_profiles.inc"
 #include "api_checkpoint.inc"
+#include "api_ensemble.inc"

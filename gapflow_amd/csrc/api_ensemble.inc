@@ -1,0 +1,183 @@
+// Ensembles (gpf_ensemble_*): many small problems advanced by one launch per kernel instantiation, one workgroup per member
+// (k_small_ensemble, small_kernel.hip).  Part of api.hip's translation unit.
+//
+// A member is a handle of its own, borrowed: everything a solo gpf_step of the same count would leave in it -- buffers, run
+// state, log, host_step / next_step, prev_state_valid, g1_ready -- is left in it here, so that it can go on alone.
+
+struct gpf_ensemble {
+    std::vector<gpf_handle*> members;
+    int device = 0;
+    // one device allocation and its pinned mirror, in launch-slot order: StepState[m] | SmallArgs[k] | Phys[k] for the k members a
+    // call launches -- the arguments adjacent, so that ONE copy per call fills them; the states come back with one
+    char* dev = nullptr;
+    char* host = nullptr;
+    std::vector<int> slot_member;           // launch slot -> member, of the last call
+    std::vector<long long> entries;         // per member: log records the last call left (0: not launched)
+    size_t args_off() const { return members.size() * sizeof(StepState); }
+    size_t bytes() const { return args_off() + members.size() * (sizeof(SmallArgs) + sizeof(Phys)); }
+};
+static_assert(sizeof(StepState) % 8 == 0 && sizeof(SmallArgs) % 8 == 0 && sizeof(Phys) % 8 == 0, "the three arrays share one allocation");
+
+// Why a member cannot be stepped in an ensemble right now; empty: it can.
+static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first) {
+    if (const char* why = small_grid_refusal(h)) return why;
+    if (h->cfg.device != first->cfg.device) return "it lives on device " + std::to_string(h->cfg.device) + ", member 0 on device " +
+                                                   std::to_string(first->cfg.device) + " (one launch needs one device)";
+    if (h->stream != first->stream) return "its stream differs from member 0's (one launch needs one stream)";
+    if (h->integ.every) return "film integrals are armed on it (they cut the batch per member; gpf_integrals_clear, or step it alone)";
+    if (h->probes.n) return "probes are armed on it (their records need per-member slots; gpf_probes_clear, or step it alone)";
+    return "";
+}
+
+extern "C" int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemble** out) {
+    if (!members || !out) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: null argument");
+    if (m < 1) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: an ensemble needs at least one member (m = " + std::to_string(m) + ")");
+    for (int i = 0; i < m; ++i) {
+        if (!members[i]) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: member " + std::to_string(i) + " is a null handle");
+        for (int j = 0; j < i; ++j)
+            if (members[j] == members[i])
+                return fail(GPF_ERR_INVALID, "gpf_ensemble_create: member " + std::to_string(i) + " is the same handle as member " +
+                                             std::to_string(j) + " (two workgroups would write the same buffers)");
+        const std::string why = ensemble_member_refusal(members[i], members[0]);
+        if (!why.empty()) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: member " + std::to_string(i) + ": " + why);
+    }
+    HIP_TRY(hipSetDevice(members[0]->cfg.device));
+    gpf_ensemble* e = new gpf_ensemble();
+    e->members.assign(members, members + m);
+    e->device = members[0]->cfg.device;
+    e->entries.assign(m, 0);
+    hipError_t err = hipMalloc(&e->dev, e->bytes());
+    if (err == hipSuccess) err = hipHostMalloc((void**)&e->host, e->bytes(), hipHostMallocDefault);
+    if (err != hipSuccess) {
+        gpf_ensemble_destroy(e);
+        return fail(GPF_ERR_HIP, std::string("gpf_ensemble_create: ") + hipGetErrorString(err));
+    }
+    *out = e;
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_destroy(gpf_ensemble* e) {
+    if (!e) return GPF_OK;
+    hipSetDevice(e->device);
+    if (e->dev) hipFree(e->dev);
+    if (e->host) hipHostFree(e->host);
+    delete e;
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_stop, int64_t* n_executed) {
+    if (!e || !n) return fail(GPF_ERR_INVALID, "gpf_ensemble_step: null argument");
+    const int m = (int)e->members.size();
+    // every refusal before anything is touched: a call that fails leaves every member as it was
+    for (int i = 0; i < m; ++i) {
+        gpf_handle* h = e->members[i];
+        const std::string who = "gpf_ensemble_step: member " + std::to_string(i) + ": ";
+        if (n[i] < 0 || n[i] > h->log_cap)
+            return fail(GPF_ERR_INVALID, who + "n = " + std::to_string((long long)n[i]) + ", 0 .. " + std::to_string(h->log_cap) + " (the log's capacity) required");
+        if (n[i] == 0) continue;
+        const std::string why = ensemble_member_refusal(h, e->members[0]);
+        if (!why.empty()) return fail(GPF_ERR_INVALID, who + why);
+        if (!h->pre_run_done) return fail(GPF_ERR_STATE, who + "call gpf_pre_run first (Problem._pre_run, problem.py:412)");
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t stream = e->members[0]->stream;
+    // launch slots: the members to advance, grouped by kernel instantiation (EOS, slip-length field or not), member order within
+    auto key = [&](int i) { return e->members[i]->cfg.eos * 2 + (e->members[i]->Ls ? 1 : 0); };
+    std::vector<int>& slots = e->slot_member;
+    slots.clear();
+    for (int i = 0; i < m; ++i) {
+        e->entries[i] = 0;
+        if (n[i] > 0) slots.push_back(i);
+    }
+    std::stable_sort(slots.begin(), slots.end(), [&](int a, int b) { return key(a) < key(b); });
+    const int nslots = (int)slots.size();
+    const size_t args_bytes = (size_t)nslots * sizeof(SmallArgs), phys_bytes = (size_t)nslots * sizeof(Phys);
+    StepState* hs = (StepState*)e->host;
+    SmallArgs* ha = (SmallArgs*)(e->host + e->args_off());
+    Phys* hp = (Phys*)(e->host + e->args_off() + args_bytes);
+    StepState* ds = (StepState*)e->dev;
+    SmallArgs* da = (SmallArgs*)(e->dev + e->args_off());
+    Phys* dp = (Phys*)(e->dev + e->args_off() + args_bytes);
+    for (int s = 0; s < nslots; ++s) {
+        gpf_handle* h = e->members[slots[s]];
+        GPF_TRY(enter(h));
+        SmallArgs& a = ha[s];
+        a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
+        a.log = h->log; a.log_base = h->host_step; a.log_cap = h->log_cap; a.L = h->L; a.E = h->E;
+        a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop; a.probe = nullptr;
+        hp[s] = h->P;
+    }
+    // Once a group has been launched its members have moved on the device, whatever happens next on the host: an error from
+    // then on does not return at once.  No further group is launched, the states of the launched slots are read back and
+    // those handles brought up to date as after a good call; then the error is returned.
+    int rc = GPF_OK, launched = 0;
+    auto hip_ok = [&](hipError_t err, const char* what) {
+        if (err != hipSuccess && rc == GPF_OK) rc = fail(GPF_ERR_HIP, std::string("gpf_ensemble_step: ") + what + ": " + hipGetErrorString(err));
+        return err == hipSuccess;
+    };
+    if (nslots > 0 && hip_ok(hipMemcpyAsync(da, ha, args_bytes + phys_bytes, hipMemcpyHostToDevice, stream), "argument copy")) {   // one copy per call
+        for (int s0 = 0; s0 < nslots && rc == GPF_OK;) {
+            int s1 = s0;
+            size_t lds = 0;
+            while (s1 < nslots && key(slots[s1]) == key(slots[s0])) {
+                const Layout& L = e->members[slots[s1]]->L;
+                lds = std::max(lds, (size_t)(L.Nx + 2) * (L.Ny + 2) * SMALL_DOUBLES_PER_CELL * 8);     // the largest member's need
+                ++s1;
+            }
+            gpf_handle* h0 = e->members[slots[s0]];
+            const dim3 grid(s1 - s0);
+            EOS_DISPATCH(h0->cfg.eos, {
+                if (h0->Ls) {
+                    if (hip_ok(hipFuncSetAttribute((const void*)k_small_ensemble<EOS_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "LDS attribute"))
+                        hipLaunchKernelGGL((k_small_ensemble<EOS_, true>), grid, dim3(512), lds, stream, da + s0, dp + s0, ds + s0);
+                } else {
+                    if (hip_ok(hipFuncSetAttribute((const void*)k_small_ensemble<EOS_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "LDS attribute"))
+                        hipLaunchKernelGGL((k_small_ensemble<EOS_, false>), grid, dim3(512), lds, stream, da + s0, dp + s0, ds + s0);
+                }
+            });
+            if (rc == GPF_OK && hip_ok(hipGetLastError(), "launch")) launched = s1;
+            s0 = s1;
+        }
+        if (launched > 0) {
+            const bool back = hip_ok(hipMemcpyAsync(hs, ds, (size_t)launched * sizeof(StepState), hipMemcpyDeviceToHost, stream), "state copy") &&
+                              hip_ok(hipStreamSynchronize(stream), "synchronise");
+            if (!back) launched = 0;            // the device no longer answers: gpf_state re-reads a member's count if it recovers
+        }
+    }
+    // what gpf_step leaves in a handle after one batch (api.hip)
+    for (int s = 0; s < launched; ++s) {
+        const int i = slots[s];
+        gpf_handle* h = e->members[i];
+        const StepState& st = hs[s];
+        const long long ran = st.step - h->host_step;
+        e->entries[i] = ran + ((st.invalid && ran < n[i]) ? 1 : 0);
+        h->host_step = st.step; h->next_step = st.step;
+        h->prev_state_valid = ran >= 1 && !st.invalid;
+        h->g1_ready = false;
+    }
+    if (n_executed)
+        for (int i = 0; i < m; ++i) n_executed[i] = e->members[i]->host_step;
+    return rc;
+}
+
+extern "C" int gpf_ensemble_limits(int64_t* lds_bytes, int32_t* doubles_per_cell, int64_t* max_steps) {
+    if (lds_bytes) *lds_bytes = SMALL_GRID_LDS_BYTES;
+    if (doubles_per_cell) *doubles_per_cell = SMALL_DOUBLES_PER_CELL;
+    if (max_steps) *max_steps = LOG_CAPACITY;
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_log(gpf_ensemble* e, int member, gpf_scalars_t* log, int64_t log_capacity, int64_t* n_entries) {
+    if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_log: null argument");
+    if (member < 0 || member >= (int)e->members.size())
+        return fail(GPF_ERR_INVALID, "gpf_ensemble_log: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    const long long have = e->entries[member];
+    if (n_entries) *n_entries = have;
+    const long long take = std::min<long long>(have, log ? log_capacity : 0);
+    if (take > 0) {
+        gpf_handle* h = e->members[member];
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipMemcpy(log, h->log, (size_t)take * sizeof(LogEntry), hipMemcpyDeviceToHost));
+    }
+    return GPF_OK;
+}

@@ -4,6 +4,7 @@
 // workgroup barriers, the scalars are reduced in the block and committed by thread 0 -- no launches, no device-scope
 // traffic between steps.  Arithmetic and order are those of the stage-wise pipeline (problem.py:509-586 line by line:
 // closures -> flux differences + source -> update -> ghost cells, twice; average; ghost cells; scalars; commit).
+// k_small_ensemble runs the same body on many such problems in one launch, one workgroup each.
 #pragma once
 
 
@@ -21,8 +22,11 @@ struct SmallArgs {
     const ProbeArgs* probe; // point probes (probe_kernels.hip), in device memory; null: none
 };
 
+// The whole batch of one problem on one workgroup of 512 threads: the body of both kernels below.  Nothing in it reaches
+// beyond `a` and `P`: the workgroup's only stores to global memory go to a.qa, a.qb, a.st, a.log (and the probe records).
+// Returns the run state the batch ended on (in LDS, written by thread 0, which alone may read it without a barrier).
 template <int EOS, bool HAS_LS>
-__global__ __launch_bounds__(512) void k_small_steps(const SmallArgs a, const Phys P) {
+__device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a, const Phys& P) {
     extern __shared__ double lds[];
     __shared__ Acc sm[16];
     __shared__ int sh_flags[2];
@@ -157,6 +161,23 @@ __global__ __launch_bounds__(512) void k_small_steps(const SmallArgs a, const Ph
         if (committed > 0 && st->invalid == 0)
             for (int c = 0; c < 3; ++c) prev[c * G.plane + o] = q[c * nc + t];
     }
+    return st;
+}
+
+template <int EOS, bool HAS_LS>
+__global__ __launch_bounds__(512) void k_small_steps(const SmallArgs a, const Phys P) {
+    small_steps_body<EOS, HAS_LS>(a, P);
+}
+
+// An ensemble: workgroup m advances problem m (api_ensemble.inc), by the body above on the arguments it finds in device
+// memory -- its own layout, edges, step count, log and stop condition.  Members share nothing: no atomics, no traffic
+// between workgroups.  The dynamic LDS of the launch is the largest member's; each workgroup lays out its own planes.
+// states_out[m]: the run state member m ended on, so that the host learns how far everyone got with one copy.
+template <int EOS, bool HAS_LS>
+__global__ __launch_bounds__(512) void k_small_ensemble(const SmallArgs* __restrict__ args, const Phys* __restrict__ phys,
+                                                        StepState* __restrict__ states_out) {
+    const StepState* st = small_steps_body<EOS, HAS_LS>(args[blockIdx.x], phys[blockIdx.x]);
+    if (threadIdx.x == 0) states_out[blockIdx.x] = *st;
 }
 
 }  // namespace gpf

@@ -1,0 +1,258 @@
+"""Ensembles: many small problems advanced together, one workgroup of one launch per member (no reference counterpart:
+the reference runs a parameter study -- three eccentricities of the Sommerfeld test, a Stribeck curve over U -- as one
+process per problem).  DESIGN.md 3.2c.
+
+    ens = Ensemble.sweep("journal1d.yaml", {'geometry.eps': [0.5, 0.7, 0.9], 'geometry.U': [0.05, 0.1]})
+    ens.run()
+    loads = [r['load'] for r in ens.film_integrals()]
+
+An ensemble HOLDS its `Problem` objects, it does not copy them: after `run()` or `step()` every member is, bit for bit, what
+the same call on it alone would have made it (`q`, `step`, `simtime`, `dt`, `residual`, `residual_buffer`, `history`, derived
+fields, output files), and it can go on alone.  Members may differ in everything -- grid, gap, edges, equation of state,
+step size, stop condition -- but each must fit the one-workgroup kernel (csrc/small_kernel.hip); what does not is refused
+when the ensemble is built, by name and with the reason.
+"""
+import ctypes as C
+import itertools
+import os
+import signal
+from datetime import datetime
+
+import numpy as np
+
+from . import _lib
+from .problem import Problem, _in_main_thread, _termination_signals
+
+
+def _refusal(p):
+    """Why Problem `p` cannot be a member, as (exception class, reason), or None.  Host only: mirrors gpf_ensemble_create."""
+    if os.environ.get('GPF_SMALL_GRID') is not None and _atoi(os.environ['GPF_SMALL_GRID']) == 0:
+        return NotImplementedError, "GPF_SMALL_GRID=0 turns the one-workgroup kernel off, and an ensemble is made of nothing else"
+    if p._gp_models or p.has_gp_model:
+        return NotImplementedError, "surrogate (GP) closures step stage-wise, with the host between the stages"
+    if p._cfg.thinning:
+        return NotImplementedError, "shear thinning steps stage-wise (it needs grad p)"
+    if p._elastic or p.topo.elastic:
+        return NotImplementedError, "an elastic gap steps stage-wise and deforms between steps"
+    cells = p._shape[0] * p._shape[1]
+    if cells * _lib.SMALL_GRID_DOUBLES_PER_CELL * 8 > _lib.SMALL_GRID_LDS_BYTES:
+        return NotImplementedError, (f"its {p.grid['Nx']} x {p.grid['Ny']} grid does not fit one workgroup's LDS "
+                                     f"({_lib.SMALL_GRID_DOUBLES_PER_CELL} doubles per cell, ghost cells included, in "
+                                     f"{_lib.SMALL_GRID_LDS_BYTES // 1024} KB)")
+    if p._integral_every is not None:
+        return NotImplementedError, "film integrals are armed on it (they cut the batch per member): clear_integrals(), or run it alone"
+    if p._probe_cells is not None:
+        return NotImplementedError, "probes are armed on it (their records need per-member slots): clear_probes(), or run it alone"
+    return None
+
+
+def _atoi(text):
+    """C's atoi, which the library applies to GPF_SMALL_GRID: leading blanks, a sign, digits; 0 where there are none."""
+    import re
+    m = re.match(r'\s*([+-]?\d+)', text)
+    return int(m.group(1)) if m else 0
+
+
+def sweep_members(base, axes):
+    """The members of a sweep over `axes` = {'section.key': [values...]} of the YAML dictionary `base`: one dictionary per
+    element of the Cartesian product, with the FIRST axis slowest and the last fastest (itertools.product over the axes in the
+    order given), and beside them the list of {dotted key: value} each one got.  KeyError for a section or key that `base`
+    does not hold (a sweep varies what the input states, it adds nothing).  Host only."""
+    import copy
+    if not axes:
+        raise ValueError("sweep: at least one 'section.key': [values] axis is required")
+    names = list(axes)
+    for name in names:
+        parts = str(name).split('.')
+        if len(parts) < 2:
+            raise KeyError(f"sweep: '{name}' is not of the form section.key")
+        node = base
+        for k, part in enumerate(parts):
+            if not isinstance(node, dict) or part not in node:
+                what = 'section' if k == 0 else 'key'
+                raise KeyError(f"sweep: the input has no {what} '{part}' (axis '{name}')")
+            node = node[part]
+        values = axes[name]
+        if isinstance(values, (str, bytes, dict)) or not hasattr(values, '__len__') or len(values) < 1:
+            raise ValueError(f"sweep: axis '{name}' needs a non-empty list of values, got {values!r}")
+    dicts, params = [], []
+    for combo in itertools.product(*[list(axes[name]) for name in names]):
+        d = copy.deepcopy(base)
+        for name, v in zip(names, combo):
+            parts = name.split('.')
+            node = d
+            for part in parts[:-1]:
+                node = node[part]
+            node[parts[-1]] = v.item() if isinstance(v, np.generic) else v
+        dicts.append(d)
+        params.append(dict(zip(names, combo)))
+    return dicts, params
+
+
+class Ensemble:
+    """`Ensemble(problems)`: the given `Problem` objects, advanced together.  See the module's text."""
+
+    def __init__(self, problems):
+        problems = list(problems)
+        if len(problems) < 1:
+            raise ValueError("Ensemble: at least one member is required (an empty list was given)")
+        for i, p in enumerate(problems):
+            if not isinstance(p, Problem):
+                raise TypeError(f"Ensemble: member {i} is a {type(p).__name__}, not a Problem")
+            for j in range(i):
+                if problems[j] is p:
+                    raise ValueError(f"Ensemble: member {i} is the same Problem as member {j} (two workgroups would write the same buffers)")
+            why = _refusal(p)
+            if why is not None:
+                raise why[0](f"Ensemble: member {i}: {why[1]}")
+            if p._cfg.device != problems[0]._cfg.device:
+                raise ValueError(f"Ensemble: member {i} lives on device {p._cfg.device}, member 0 on device {problems[0]._cfg.device} "
+                                 "(one launch needs one device)")
+        self.problems = problems
+        self.parameters = None              # sweep(): what each member got, {dotted key: value}
+        self._lib = problems[0]._lib
+        self._e = C.c_void_p()
+        handles = (C.c_void_p * len(problems))(*[p._h.value for p in problems])
+        _lib.check(self._lib.gpf_ensemble_create(handles, len(problems), C.byref(self._e)))
+
+    def __del__(self):
+        e = getattr(self, '_e', None)
+        if e is not None and e.value:
+            self._lib.gpf_ensemble_destroy(e)
+            e.value = None
+
+    def __len__(self):
+        return len(self.problems)
+
+    def __getitem__(self, i):
+        return self.problems[i]
+
+    def __iter__(self):
+        return iter(self.problems)
+
+    # -------------------------------------------------------------------------------------
+    # constructors
+    # -------------------------------------------------------------------------------------
+    @classmethod
+    def from_yaml(cls, fnames, device=0):
+        """One member per input file, in the order given."""
+        return cls([Problem.from_yaml(f, device=device) for f in fnames])
+
+    @classmethod
+    def sweep(cls, yaml_path_or_string, axes, device=0):
+        """One member per element of the Cartesian product of `axes` = {'section.key': [values...]} over the input: dotted keys
+        address the YAML sections ('geometry.eps', 'numerics.tol', 'properties.piezo.aB').  Order: itertools.product over the
+        axes as given -- the first axis varies slowest, the last fastest; `parameters[m]` holds what member m got.  A section or
+        key the input does not hold raises KeyError before any problem is built.  A non-silent input with a fixed output
+        directory would have every member write into the same one: sweep 'options.output' too, or keep `use_tstamp`."""
+        import yaml
+        text = yaml_path_or_string if isinstance(yaml_path_or_string, str) else os.fspath(yaml_path_or_string)
+        if '\n' not in text and os.path.exists(text):
+            with open(text, 'r') as f:
+                text = f.read()
+        base = yaml.full_load(text)
+        if not isinstance(base, dict):
+            raise ValueError("sweep: the input is not a YAML mapping of sections")
+        dicts, params = sweep_members(base, axes)
+        ens = cls([Problem.from_string(yaml.safe_dump(d), device=device) for d in dicts])
+        ens.parameters = params
+        return ens
+
+    # -------------------------------------------------------------------------------------
+    # stepping
+    # -------------------------------------------------------------------------------------
+    def _advance(self, counts, honor_stop):
+        """counts[m] steps for member m (0: leave it alone) in one library call; returns the per-step records per member."""
+        ps = self.problems
+        for i, (p, n) in enumerate(zip(ps, counts)):
+            if n < 0 or n > _lib.LOG_CAPACITY:
+                raise ValueError(f"Ensemble: member {i}: {n} steps, 0 .. {_lib.LOG_CAPACITY} (the device log's capacity) per call required")
+            if n == 0:
+                continue
+            if p.step is None:
+                raise RuntimeError(f"Ensemble: member {i}: call _pre_run() (or run()) before step()")
+            why = _refusal(p)
+            if why is not None:
+                raise why[0](f"Ensemble: member {i}: {why[1]}")
+        for p, n in zip(ps, counts):
+            if n:
+                p._sync_to_device()
+        arr = (C.c_int64 * len(ps))(*[int(n) for n in counts])
+        nexec = (C.c_int64 * len(ps))()
+        _lib.check(self._lib.gpf_ensemble_step(self._e, arr, int(honor_stop), nexec))
+        out = []
+        for i, (p, n) in enumerate(zip(ps, counts)):
+            if n == 0:
+                out.append([])
+                continue
+            log = (_lib.GpfScalars * n)()
+            _lib.check(self._lib.gpf_ensemble_log(self._e, i, log, n, None))
+            before = p.step
+            out.append(p._absorb_batch(log, n, int(nexec[i]) - before, before))
+        return out
+
+    def step(self, n):
+        """Advance every member by n steps -- an int, or one count per member (0 leaves a member alone) -- as `Problem.update()`
+        would, n times: no stop at convergence or max_it."""
+        counts = [int(n)] * len(self.problems) if isinstance(n, (int, np.integer)) else [int(k) for k in n]
+        if len(counts) != len(self.problems):
+            raise ValueError(f"Ensemble.step: {len(counts)} counts for {len(self.problems)} members")
+        todo = list(counts)
+        while any(todo):                # the device log holds 4096 records per member and call
+            now = [min(k, _lib.LOG_CAPACITY) for k in todo]
+            self._advance(now, honor_stop=False)
+            todo = [k - d for k, d in zip(todo, now)]
+
+    def _receive_signal(self, signum, frame):
+        if signum in _termination_signals():
+            for p in self.problems:
+                p._stop = True
+
+    def run(self, keep_open=False):
+        """For every member what `Problem.run()` does for it alone: `_pre_run` where needed, batches whose length per member
+        follows the rule of `Problem.run` (its own write_freq, max_it, checkpoint_freq; 4096), frames and checkpoints at its own
+        multiples, `_post_run` when IT ends.  A member that has converged, reached max_it or been rolled back takes no further
+        part.  A termination signal stops all members."""
+        ps = self.problems
+        cfs = [p._run_begin() for p in ps]
+        old = {s: signal.signal(s, self._receive_signal) for s in _termination_signals()} if _in_main_thread() else {}
+        tic = datetime.now()
+        for p in ps:
+            p._tic = tic
+        running = [True] * len(ps)
+
+        def retire():
+            for i, p in enumerate(ps):
+                if running[i] and not p._run_active():
+                    running[i] = False
+                    p._run_end(cfs[i], keep_open)
+
+        try:
+            retire()
+            while any(running):
+                counts = [p._run_batch_length(cf) if on else 0 for p, cf, on in zip(ps, cfs, running)]
+                self._advance(counts, honor_stop=True)
+                for p, cf, on in zip(ps, cfs, running):
+                    if on:
+                        p._run_after_batch(cf)
+                retire()
+        finally:
+            for s, hdl in old.items():
+                signal.signal(s, hdl)
+
+    # -------------------------------------------------------------------------------------
+    # views
+    # -------------------------------------------------------------------------------------
+    @property
+    def steps(self):
+        """Step count of every member (-1 before its `_pre_run`)."""
+        return np.array([-1 if p.step is None else p.step for p in self.problems], dtype=np.int64)
+
+    @property
+    def converged(self):
+        """`Problem.converged` of every member (False before its `_pre_run`)."""
+        return np.array([p.step is not None and p.converged for p in self.problems], dtype=bool)
+
+    def film_integrals(self):
+        """`Problem.film_integrals()` of every member's current state: load, friction and flow rates -- what a sweep is usually for."""
+        return [p.film_integrals() for p in self.problems]

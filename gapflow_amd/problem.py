@@ -641,7 +641,11 @@ class Problem:
         nexec = C.c_int64(0)
         before = self.step
         _lib.check(self._lib.gpf_step(self._h, n, int(honor_stop), log, n, C.byref(nexec)))
-        ran = int(nexec.value) - before
+        return self._absorb_batch(log, n, int(nexec.value) - before, before)
+
+    def _absorb_batch(self, log, n, ran, before):
+        """The host's bookkeeping behind a batch of n steps of which `ran` were committed, taking the step count on from `before`;
+        log: its n per-step records, zero where none was written (shared with Ensemble, whose members' batches run in one launch)."""
         entries = [log[i] for i in range(ran)]
         self._absorb(entries)
         self._collect_probes(entries)
@@ -719,7 +723,8 @@ class Problem:
         if signum in _termination_signals():
             self._stop = True
 
-    def run(self, keep_open=False):
+    def _run_begin(self):
+        """What run() does before its first step; returns the steps between checkpoints (0: none).  Shared with Ensemble.run."""
         if self.step is None:
             self._pre_run()
         self._stop = False
@@ -733,33 +738,45 @@ class Problem:
             print(61 * '-')
             # (a restarted run's history already ends with the row of the step it starts from)
             self.write(scalars=not (self.history['step'] and self.history['step'][-1] == self.step), params=False)
-        old = {s: signal.signal(s, self._receive_signal) for s in _termination_signals()} \
-            if _in_main_thread() else {}
-        self._tic = datetime.now()
-        wf = self.options['write_freq']
-        try:
-            while (self._gp_models or self._cfg.thinning or self._elastic) and not self.converged and self.step < self.max_it and not self._stop:
-                self.update()                   # surrogates: one host-driven step at a time
-                if self.step % wf == 0 and not silent and not self._stop:
-                    self.write()
-                if cf > 0 and self.step % cf == 0 and not self._stop and not self.converged and self.step < self.max_it:
-                    self._write_checkpoint()    # (a run that ends here writes its checkpoint once, below)
-            while not self.converged and self.step < self.max_it and not self._stop:
-                # steps until the next frame (problem.py:404) or max_it, whichever comes first; the
-                # device stops by itself at convergence, so a batch never overshoots the reference's loop
-                n = min(wf - self.step % wf, self.max_it - self.step, 4096, *([cf - self.step % cf] if cf > 0 else []))
-                self._advance(n, honor_stop=True)
-                if self.step % wf == 0 and not silent and not self._stop:
-                    self.write()
-                if cf > 0 and self.step % cf == 0 and not self._stop and not self.converged and self.step < self.max_it:
-                    self._write_checkpoint()    # (a run that ends here writes its checkpoint once, below)
-        finally:
-            for s, hdl in old.items():
-                signal.signal(s, hdl)
+        return cf
+
+    def _run_active(self):
+        return not self.converged and self.step < self.max_it and not self._stop
+
+    def _run_batch_length(self, cf):
+        return _batch_length(self.step, self.options['write_freq'], self.max_it, cf)
+
+    def _run_after_batch(self, cf):
+        """Frame and checkpoint at this problem's own multiples, after an update or a batch.  Shared with Ensemble.run."""
+        if self.step % self.options['write_freq'] == 0 and not self.options['silent'] and not self._stop:
+            self.write()
+        if cf > 0 and self.step % cf == 0 and not self._stop and not self.converged and self.step < self.max_it:
+            self._write_checkpoint()    # (a run that ends here writes its checkpoint once, in _run_end)
+
+    def _run_end(self, cf, keep_open=False):
         if not keep_open:
             self._post_run()
         if cf > 0:
             self._write_checkpoint()            # the state the run ends on, with the history _post_run completed
+
+    def run(self, keep_open=False):
+        cf = self._run_begin()
+        old = {s: signal.signal(s, self._receive_signal) for s in _termination_signals()} \
+            if _in_main_thread() else {}
+        self._tic = datetime.now()
+        try:
+            while (self._gp_models or self._cfg.thinning or self._elastic) and self._run_active():
+                self.update()                   # surrogates: one host-driven step at a time
+                self._run_after_batch(cf)
+            while self._run_active():
+                # steps until the next frame (problem.py:404) or max_it, whichever comes first; the
+                # device stops by itself at convergence, so a batch never overshoots the reference's loop
+                self._advance(self._run_batch_length(cf), honor_stop=True)
+                self._run_after_batch(cf)
+        finally:
+            for s, hdl in old.items():
+                signal.signal(s, hdl)
+        self._run_end(cf, keep_open)
 
     def _post_run(self):
         walltime = datetime.now() - self._tic
@@ -848,6 +865,13 @@ class Problem:
         if params:
             for m in self._gp_models.values():
                 m.write()
+
+
+def _batch_length(step, write_freq, max_it, checkpoint_freq=0):
+    """Steps of the next batch of a run that stands at `step`: up to the next frame (problem.py:404), to max_it, to the next
+    checkpoint (checkpoint_freq > 0), and at most what the device log holds -- whichever comes first."""
+    n = min(write_freq - step % write_freq, max_it - step, _lib.LOG_CAPACITY)
+    return min(n, checkpoint_freq - step % checkpoint_freq) if checkpoint_freq > 0 else n
 
 
 def _keep_checkpoint_freq(input_dict, ymlstring):

@@ -478,6 +478,47 @@ int gpf_integrals_now(gpf_handle* h, double* out, int64_t count);
  * Probes are put aside in both modes. */
 int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- ensembles (no reference counterpart: the reference runs a parameter study as one process per problem) ---------------- */
+/* Many small problems advanced by ONE launch per kernel instantiation: workgroup m of k_small_ensemble runs, on member m's own
+ * buffers, the very body that k_small_steps runs for a handle alone (csrc/small_kernel.hip), so a member's field, run state
+ * and per-step records are bit for bit those of a solo gpf_step of the same count.  Members differ freely in grid, gap,
+ * edges, equation of state, step size and stop condition; nothing is shared between them.
+ *   gpf_ensemble_create   BORROWS the m handles: it does not own them and they must outlive the ensemble.  GPF_ERR_INVALID, with
+ *                         a message that names the member and the reason, for: m < 1; a null handle; the same handle twice (two
+ *                         workgroups would write the same buffers); a member that the one-workgroup kernel cannot take (grid
+ *                         beyond 150 KB of LDS at 16 doubles per ghosted cell, shear thinning, slab halo, surrogate set, elastic
+ *                         gap, or GPF_SMALL_GRID=0 in the environment); members on different devices or streams (one launch
+ *                         needs one stream); film integrals or probes armed on a member.
+ *   gpf_ensemble_step     n[i] steps for member i, 0 <= n[i] <= 4096 (the log's capacity); 0 leaves the member alone: it is not
+ *                         launched and nothing of it is touched.  honor_stop as in gpf_step, for all members.  The members
+ *                         to advance are grouped by instantiation (equation of state, slip-length field present or not); each
+ *                         group is one launch on the members' stream with one workgroup per member and the dynamic LDS of its
+ *                         largest member.  The kernels' arguments travel in one host-to-device copy per call and every
+ *                         member's final run state comes back in one.  n_executed (may be NULL): m step counts afterwards.
+ *                         Afterwards every advanced handle is as gpf_step(h, n[i], honor_stop, ...) leaves it, the rollback of
+ *                         an invalid step included: it may be stepped alone, queried or checkpointed.  Checked before anything is
+ *                         launched, for members with n[i] > 0: the refusals of gpf_ensemble_create once more (a member armed or
+ *                         changed since), GPF_ERR_INVALID; gpf_pre_run not called, GPF_ERR_STATE.  A refused call changes nothing.
+ *                         A HIP error once a group has been launched (GPF_ERR_HIP) is another matter: those members have moved
+ *                         on the device.  No further group is launched, the launched members' states are read back and their
+ *                         handles brought up to date as after a good call (n_executed is filled), then the error is returned;
+ *                         only if the device no longer answers do the handles keep their old step counts (gpf_state re-reads one).
+ *   gpf_ensemble_log      the per-step records member `member` left in the LAST gpf_ensemble_step: *n_entries (may be NULL) how
+ *                         many -- the steps that ran, plus the record of an invalid step that was rolled back; 0 for a member
+ *                         that was not advanced -- and min(*n_entries, log_capacity) of them copied to log (NULL: none).  The
+ *                         records stay in the member's own device log until its next stepping call, so a caller who wants no
+ *                         history pays no copy at all, and one who does pays for the members it asks for.
+ *   gpf_ensemble_destroy  frees the ensemble's argument buffers; the members stay.
+ *   gpf_ensemble_limits   what a member may be, for hosts that refuse before calling (any pointer may be NULL): the LDS bytes
+ *                         the one-workgroup kernel may take, the doubles it keeps per ghosted cell, the most steps per member
+ *                         and call (the log's capacity).  Needs no device. */
+typedef struct gpf_ensemble gpf_ensemble;
+int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemble** out);
+int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_stop, int64_t* n_executed);
+int gpf_ensemble_log(gpf_ensemble* e, int member, gpf_scalars_t* log, int64_t log_capacity, int64_t* n_entries);
+int gpf_ensemble_destroy(gpf_ensemble* e);
+int gpf_ensemble_limits(int64_t* lds_bytes, int32_t* doubles_per_cell, int64_t* max_steps);
+
 /* Diagnostic: time of one pass of an elementwise kernel that reads `nin` and writes `nout` fp64 planes of
  * `doubles_per_plane` elements (16 bytes per lane, grid-stride): what THIS device streams for the byte count of a fused
  * step.  bench.py reports it beside the step kernel's HBM figure (no reference counterpart: the reference has no device). */
