@@ -19,6 +19,7 @@
 #include "gp_kernels.hip"
 #include "elastic_kernels.hip"
 #include "probe_kernels.hip"
+#include "extrema_kernels.hip"
 #include "small_kernel.hip"
 #include "profile_kernels.hip"
 #include "checkpoint_kernels.hip"
@@ -106,6 +107,12 @@ struct gpf_handle {
     // GPF_FILM_NARROW was set then, 8-byte loads); the records of the last stepping call and their step counts on the host
     struct { long long every = 0; int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
              double* rec = nullptr; double* part = nullptr; bool narrow = false; std::vector<double> host; std::vector<long long> steps; } integ;
+    // field extrema (api_extrema.inc): recording stride (0: not armed); the device records of the batch in flight ([log_cap + 1][7]
+    // doubles, [log_cap + 1][14] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was set then);
+    // `dev`: the ExtremaArgs of these buffers in device memory, for k_small_steps; the records of the last stepping call on the host.
+    // `pending`: an elastic handle's closed step waits for gpf_elastic_update to record it, `pending_base` the count it began at
+    struct { long long every = 0; ExtremaArgs a = {}; ExtremaArgs* dev = nullptr; bool narrow = false; bool pending = false; long long pending_base = 0;
+             std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } extr;
     double* stage = nullptr;                // contiguous staging for upload/download
     size_t stage_doubles = 0;
     // unfused pipeline scratch (lazy)
@@ -327,7 +334,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -971,6 +978,7 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
     a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
     a.log = h->log; a.log_base = log_base; a.log_cap = h->log_cap; a.L = L; a.E = h->E; a.nsteps = nsteps; a.honor_stop = honor_stop;
     a.probe = h->probes.n ? h->probes.dev : nullptr;
+    a.extrema = h->extr.every ? h->extr.dev : nullptr;
     const size_t lds = (size_t)(L.Nx + 2) * (L.Ny + 2) * SMALL_DOUBLES_PER_CELL * 8;
     EOS_DISPATCH(h->cfg.eos, {
         if (h->Ls) {
@@ -988,6 +996,7 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
 }
 
 #include "api_integrals.inc"
+#include "api_extrema.inc"
 
 extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t* log, int64_t log_capacity,
                         int64_t* n_executed) {
@@ -1002,6 +1011,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     const bool small = small_grid_eligible(h);
     GPF_TRY(probes_begin(h));
     GPF_TRY(integrals_begin(h));
+    GPF_TRY(extrema_begin(h));
     while (done < n) {
         const int64_t batch = std::min<int64_t>(n - done, h->log_cap);
         const long long base = h->host_step;
@@ -1011,12 +1021,14 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
             GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
             GPF_TRY(probes_launch(h, base + i + 1, base));      // no launch without probes
             GPF_TRY(integrals_launch(h, base + i + 1, base));   // nor without integrals, nor off their stride
+            GPF_TRY(extrema_launch(h, base + i + 1, base));     // nor without extrema, nor off theirs
         }
         StepState s;
         GPF_TRY(read_state(h, s));
         const long long ran = s.step - base;
         GPF_TRY(probes_collect(h, ran));
         GPF_TRY(integrals_collect(h, base, ran));
+        GPF_TRY(extrema_collect(h, base, ran));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);
         if (log && entries > 0) {
             const long long take = std::min<long long>(entries, log_capacity - logged);

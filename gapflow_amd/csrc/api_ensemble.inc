@@ -26,6 +26,7 @@ static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first) {
     if (h->stream != first->stream) return "its stream differs from member 0's (one launch needs one stream)";
     if (h->integ.every) return "film integrals are armed on it (they cut the batch per member; gpf_integrals_clear, or step it alone)";
     if (h->probes.n) return "probes are armed on it (their records need per-member slots; gpf_probes_clear, or step it alone)";
+    if (h->extr.every) return "extrema are armed on it (their records need per-member slots; gpf_extrema_clear, or step it alone)";
     return "";
 }
 
@@ -104,7 +105,7 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         SmallArgs& a = ha[s];
         a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
         a.log = h->log; a.log_base = h->host_step; a.log_cap = h->log_cap; a.L = h->L; a.E = h->E;
-        a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop; a.probe = nullptr;
+        a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop; a.probe = nullptr; a.extrema = nullptr;
         hp[s] = h->P;
     }
     // Once a group has been launched its members have moved on the device, whatever happens next on the host: an error from

@@ -1,0 +1,210 @@
+// Field extrema of the committed state, each with its cell (entry points in api_extrema.inc): the largest and smallest EOS
+// pressure and density, the smallest gap height, the largest |jx / rho| and |jy / rho|, over the interior cells 1..Nx x 1..Ny.
+//
+// ONE comparison, extrema_before, orders candidates (value, ix, iy) totally: the better value first, then the smaller ix, then
+// the smaller iy.  Every fold -- a thread over its cells, lanes over a wave, waves over a workgroup, rows over the grid -- keeps
+// the first of two candidates under that order.  The minimum of a total order does not depend on how the candidates are
+// bracketed, so the shape of the reduction tree is free: a record is a pure function of the state (no floating-point atomics,
+// no arrival order), and the wide and narrow loads, the row kernels and the one-workgroup kernel agree in every bit.
+// A committed state has no NaN and rho >= 0 (q_is_valid).  rho = 0 makes |j / rho| inf (NaN for j = 0, which no comparison
+// ever prefers or displaces): plain IEEE, not special-cased.
+//
+// Three writers, one record (seven doubles, fourteen int32):
+//   k_extrema_partial + k_extrema_fold   behind every launch-per-step step, guarded by the device's run state like k_probe_record
+//   extrema_record_block                 inside k_small_steps, after commit_step, from the field the workgroup holds in LDS
+//                                        (one wave per quantity)
+// k_extrema_partial runs one 256-thread workgroup per interior row; thread t owns the column pairs (1 + 2k, 2 + 2k) for
+// k = t, t + 256, ..., fetched with one 16-byte load per plane where the buffers allow it (film_wide_ok) and with 8-byte loads
+// otherwise; the ghost column an odd Ny reaches is loaded and never compared.  It reads 4 planes (rho, jx, jy, h: 32 B per
+// cell) and stores seven (value, iy) pairs per row; k_extrema_fold folds the Nx rows in one workgroup.
+#pragma once
+
+namespace gpf {
+
+constexpr int EXTREMA_NQ = 7;       // p_max p_min rho_max rho_min h_min u_max v_max
+constexpr int EXTREMA_NO_CELL = 0x7fffffff;
+
+typedef double ext_d2 __attribute__((ext_vector_type(2)));
+
+struct ExtremaArgs {
+    double* val;            // [cap + 1][7]
+    int* cell;              // [cap + 1][7][2]: ix, iy in the ghosted index space
+    double* row_val;        // [Nx][7]: k_extrema_partial's row results
+    int* row_iy;            // [Nx][7]
+    long long every, cap;   // recording stride; records a batch may leave (slot cap: gpf_extrema_now's)
+};
+
+__device__ __forceinline__ bool extrema_is_min(int k) { return k == 1 || k == 3 || k == 4; }
+
+// THE comparison: does candidate a come before candidate b?  A total order on (value, ix, iy) for values without NaN.
+__device__ __forceinline__ bool extrema_before(bool want_min, double a, int ax, int ay, double b, int bx, int by) {
+    if (a != b) return want_min ? a < b : a > b;
+    return ax != bx ? ax < bx : ay < by;
+}
+
+struct ExtAcc {
+    double v[EXTREMA_NQ];
+    int ix[EXTREMA_NQ], iy[EXTREMA_NQ];
+    // the candidate every cell comes before
+    __device__ __forceinline__ void none() {
+#pragma unroll
+        for (int k = 0; k < EXTREMA_NQ; ++k) {
+            v[k] = extrema_is_min(k) ? __builtin_huge_val() : -__builtin_huge_val();
+            ix[k] = EXTREMA_NO_CELL; iy[k] = EXTREMA_NO_CELL;
+        }
+    }
+    __device__ __forceinline__ void take(int k, double x, int cx, int cy) {
+        if (extrema_before(extrema_is_min(k), x, cx, cy, v[k], ix[k], iy[k])) { v[k] = x; ix[k] = cx; iy[k] = cy; }
+    }
+    __device__ __forceinline__ void cell(double p, double rho, double jx, double jy, double h, int cx, int cy) {
+        take(0, p, cx, cy); take(1, p, cx, cy);
+        take(2, rho, cx, cy); take(3, rho, cx, cy);
+        take(4, h, cx, cy);
+        take(5, fabs(jx / rho), cx, cy);
+        take(6, fabs(jy / rho), cx, cy);
+    }
+    __device__ __forceinline__ void merge(const ExtAcc& o) {
+#pragma unroll
+        for (int k = 0; k < EXTREMA_NQ; ++k) take(k, o.v[k], o.ix[k], o.iy[k]);
+    }
+};
+
+// The first candidate of all threads of the workgroup (blockDim.x a multiple of 64, at most 512), valid in thread 0.  Only
+// threads 0 .. nactive - 1 (nactive >= 1, block-uniform) hold candidates: the waves among them fold their lanes 32, 16, .. 1
+// apart, then thread 0 folds those waves; a wave wholly beyond nactive holds nothing and does nothing.  `sm` is written by
+// lane 0 of every such wave and read by thread 0 only: a caller that uses it again puts a barrier in between.
+__device__ __forceinline__ ExtAcc extrema_block_first(ExtAcc a, ExtAcc* sm, int nactive) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if ((w << 6) < nactive) {                           // wave-uniform
+        for (int s = 32; s >= 1; s >>= 1) {
+            ExtAcc o;
+#pragma unroll
+            for (int k = 0; k < EXTREMA_NQ; ++k) { o.v[k] = __shfl_down(a.v[k], s); o.ix[k] = __shfl_down(a.ix[k], s); o.iy[k] = __shfl_down(a.iy[k], s); }
+            a.merge(o);
+        }
+        if (lane == 0) sm[w] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int nw = (nactive + 63) >> 6;
+        for (int i = 1; i < nw; ++i) a.merge(sm[i]);
+    }
+    return a;
+}
+
+__device__ __forceinline__ void extrema_store(const ExtremaArgs& x, long long slot, const ExtAcc& r) {
+    double* v = x.val + slot * EXTREMA_NQ;
+    int* c = x.cell + slot * 2 * EXTREMA_NQ;
+#pragma unroll
+    for (int k = 0; k < EXTREMA_NQ; ++k) { v[k] = r.v[k]; c[2 * k] = r.ix[k]; c[2 * k + 1] = r.iy[k]; }
+}
+
+template <int EOS>
+__global__ __launch_bounds__(256) void k_extrema_partial(const double* qa, const double* qb, const double* topo, const StepState* st,
+                                                         const Layout L, const Phys P, const ExtremaArgs x, int wide, long long expect,
+                                                         long long slot) {
+    __shared__ ExtAcc sm[4];
+    if (st->step != expect || st->invalid != 0) return;                // uniform: the step did not run, or was rolled back
+    if (slot < 0 || slot > x.cap) return;
+    const int ix = 1 + blockIdx.x;
+    const double* q = st->parity ? qb : qa;
+    ExtAcc a;
+    a.none();
+    const int npair = (L.Ny + 1) / 2;
+    for (int k = threadIdx.x; k < npair; k += 256) {
+        const int iy = 1 + 2 * k;
+        const bool two = iy + 1 <= L.Ny;
+        const long long o = L.at(ix, iy);
+        ext_d2 in[4];
+        if (wide) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) in[p] = *reinterpret_cast<const ext_d2*>(q + p * L.plane + o);
+            in[3] = *reinterpret_cast<const ext_d2*>(topo + o);
+        } else {
+            const long long o1 = two ? o + 1 : o;
+#pragma unroll
+            for (int p = 0; p < 3; ++p) in[p] = ext_d2{q[p * L.plane + o], q[p * L.plane + o1]};
+            in[3] = ext_d2{topo[o], topo[o1]};
+        }
+        a.cell(eos_pressure<EOS>(in[0].x, P), in[0].x, in[1].x, in[2].x, in[3].x, ix, iy);
+        if (two) a.cell(eos_pressure<EOS>(in[0].y, P), in[0].y, in[1].y, in[2].y, in[3].y, ix, iy + 1);
+    }
+    const ExtAcc r = extrema_block_first(a, sm, npair < 256 ? npair : 256);
+    if (threadIdx.x == 0) {
+        double* v = x.row_val + (long long)(ix - 1) * EXTREMA_NQ;
+        int* c = x.row_iy + (long long)(ix - 1) * EXTREMA_NQ;
+#pragma unroll
+        for (int k = 0; k < EXTREMA_NQ; ++k) { v[k] = r.v[k]; c[k] = r.iy[k]; }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_extrema_fold(const StepState* st, const ExtremaArgs x, int Nx, long long expect, long long slot) {
+    __shared__ ExtAcc sm[4];
+    if (st->step != expect || st->invalid != 0) return;
+    if (slot < 0 || slot > x.cap) return;
+    ExtAcc a;
+    a.none();
+    for (int row = threadIdx.x; row < Nx; row += 256) {
+        const double* v = x.row_val + (long long)row * EXTREMA_NQ;
+        const int* c = x.row_iy + (long long)row * EXTREMA_NQ;
+#pragma unroll
+        for (int k = 0; k < EXTREMA_NQ; ++k) a.take(k, v[k], row + 1, c[k]);
+    }
+    const ExtAcc r = extrema_block_first(a, sm, Nx < 256 ? Nx : 256);
+    if (threadIdx.x == 0) extrema_store(x, slot, r);
+}
+
+// The same record from the dense LDS field of k_small_steps (q: planes of nc cells, rows of w; h: the gap plane): the whole
+// block (at least seven waves) calls it after the commit of a step whose count is a multiple of the stride, with the slot of
+// that step among the batch's recorded steps (ExtremaCursor keeps both, without a division per step).
+// Block-uniform; reads only, and needs no barrier: the committed field is not written again before the commit after next.
+// Wave k takes quantity k alone, so that a record costs a fraction of a step: its lanes evaluate the quantity of their
+// cells and keep the first, shuffles fold the lanes -- by the same comparison -- and lane 0 stores the value and the cell.
+// Which step k_small_steps records next and where: the arguments are fetched from device memory once per launch, the first
+// multiple of the stride beyond the count the launch starts at and its slot -- the rank among the multiples in (base, .] --
+// are worked out once, and each record moves both on.
+struct ExtremaCursor {
+    ExtremaArgs x;
+    long long next, slot;
+    __device__ __forceinline__ void begin(const ExtremaArgs* args, long long step, long long base) {
+        x = *args;
+        next = (step / x.every + 1) * x.every;
+        slot = next / x.every - base / x.every - 1;
+    }
+    __device__ __forceinline__ bool due(long long step) const { return step == next; }
+    __device__ __forceinline__ void advance() { next += x.every; slot += 1; }
+};
+
+template <int EOS>
+__device__ __forceinline__ void extrema_record_block(const ExtremaArgs& x, const double* q, const double* h, int Nx, int Ny, int nc, int w,
+                                                     long long slot, const Phys& P) {
+    if (slot < 0 || slot >= x.cap) return;
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (k >= EXTREMA_NQ) return;                        // wave-uniform
+    const int ncell = Nx * Ny;
+    const bool want_min = extrema_is_min(k);
+    double v = want_min ? __builtin_huge_val() : -__builtin_huge_val();
+    int bx = EXTREMA_NO_CELL, by = EXTREMA_NO_CELL;
+    for (int t = lane; t < ncell; t += 64) {
+        const int ix = 1 + t / Ny, iy = 1 + t % Ny;
+        const int c = ix * w + iy;
+        double f;
+        if (k < 2) f = eos_pressure<EOS>(q[c], P);
+        else if (k < 4) f = q[c];
+        else if (k == 4) f = h[c];
+        else f = fabs(q[(k - 4) * nc + c] / q[c]);      // k 5: jx, k 6: jy
+        if (extrema_before(want_min, f, ix, iy, v, bx, by)) { v = f; bx = ix; by = iy; }
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const double ov = __shfl_down(v, s);
+        const int ox = __shfl_down(bx, s), oy = __shfl_down(by, s);
+        if (extrema_before(want_min, ov, ox, oy, v, bx, by)) { v = ov; bx = ox; by = oy; }
+    }
+    if (lane == 0) {
+        x.val[slot * EXTREMA_NQ + k] = v;
+        x.cell[(slot * EXTREMA_NQ + k) * 2] = bx;
+        x.cell[(slot * EXTREMA_NQ + k) * 2 + 1] = by;
+    }
+}
+
+}  // namespace gpf

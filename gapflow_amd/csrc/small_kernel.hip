@@ -20,10 +20,11 @@ struct SmallArgs {
     Layout L; Edges E;
     int nsteps, honor_stop;
     const ProbeArgs* probe; // point probes (probe_kernels.hip), in device memory; null: none
+    const ExtremaArgs* extrema;     // field extrema (extrema_kernels.hip), in device memory; null: none
 };
 
 // The whole batch of one problem on one workgroup of 512 threads: the body of both kernels below.  Nothing in it reaches
-// beyond `a` and `P`: the workgroup's only stores to global memory go to a.qa, a.qb, a.st, a.log (and the probe records).
+// beyond `a` and `P`: the workgroup's only stores to global memory go to a.qa, a.qb, a.st, a.log (and the probe and extrema records).
 // Returns the run state the batch ended on (in LDS, written by thread 0, which alone may read it without a barrier).
 template <int EOS, bool HAS_LS>
 __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a, const Phys& P) {
@@ -85,6 +86,8 @@ __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a,
     };
 
     int committed = 0;                              // steps this launch has committed (block-uniform)
+    ExtremaCursor ext;
+    if (a.extrema) ext.begin(a.extrema, st->step, a.log_base);
     for (int step = 0; step < a.nsteps; ++step) {
         if (st->invalid != 0 || (a.honor_stop && (st->converged || st->step >= st->max_it))) break;     // block-uniform
         const double dt = st->dt;
@@ -148,6 +151,10 @@ __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a,
         double* tmp = q0; q0 = q; q = tmp;          // the averaged field is the current one now
         committed += 1;
         if (a.probe) probe_record_block<EOS>(*a.probe, q0, nc, w, st->step - 1 - a.log_base, a.log_cap, P);     // block-uniform; reads only
+        if (a.extrema && ext.due(st->step)) {           // likewise, at the armed stride
+            extrema_record_block<EOS>(ext.x, q0, T, D.Nx, D.Ny, nc, w, ext.slot, P);
+            ext.advance();
+        }
     }
     // the current state -> the buffer the (final) parity designates; the run state back to global memory
     __syncthreads();

@@ -43,6 +43,8 @@ def _refusal(p):
         return NotImplementedError, "film integrals are armed on it (they cut the batch per member): clear_integrals(), or run it alone"
     if p._probe_cells is not None:
         return NotImplementedError, "probes are armed on it (their records need per-member slots): clear_probes(), or run it alone"
+    if p._extrema_every is not None:
+        return NotImplementedError, "extrema are armed on it (their records need per-member slots): clear_extrema(), or run it alone"
     return None
 
 
@@ -256,3 +258,8 @@ class Ensemble:
     def film_integrals(self):
         """`Problem.film_integrals()` of every member's current state: load, friction and flow rates -- what a sweep is usually for."""
         return [p.film_integrals() for p in self.problems]
+
+    def field_extrema(self):
+        """`Problem.field_extrema()` of every member's current state: peak pressure, lowest density, smallest gap, largest
+        velocity components, each with its cell."""
+        return [p.field_extrema() for p in self.problems]

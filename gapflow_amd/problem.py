@@ -33,6 +33,8 @@ ProbeSeries = namedtuple('ProbeSeries', 'step time cells rho jx jy p')
 ProbeSeries.__doc__ = """Time series of Problem.probes: step, time (nrecords,), cells (nprobes, 2), rho, jx, jy, p (nrecords, nprobes); p None if not asked for."""
 FilmIntegrals = namedtuple('FilmIntegrals', ('step', 'time') + _lib.INTEGRAL_SUMS + ('flow_x', 'flow_y', 'sections_x', 'sections_y'))
 FilmIntegrals.__doc__ = """Time series of Problem.integrals: step, time and the nine area integrals (nrecords,), flow_x (nrecords, len(sections_x)), flow_y (nrecords, len(sections_y)), the sections' interior rows / columns."""
+FieldExtrema = namedtuple('FieldExtrema', ('step', 'time') + _lib.EXTREMA_NAMES + ('cells', 'index'))
+FieldExtrema.__doc__ = """Time series of Problem.extrema: step, time and the seven values (nrecords,), cells (nrecords, 7, 2) -- (ix, iy) of each value in the ghosted index space --, index: name -> position along the cells' second axis."""
 
 
 def _termination_signals():
@@ -115,6 +117,9 @@ class Problem:
         self._integral_every = None
         if options.get('integrals') is not None:    # options.integrals (from the YAML text, or carried by a checkpoint's dictionaries)
             self.set_integrals(options['integrals'], options.get('integrals_sections_x'), options.get('integrals_sections_y'))
+        self._extrema_every = None
+        if options.get('extrema'):                  # options.extrema (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
+            self.set_extrema(options['extrema'])
 
         if not options['silent']:
             self.outdir = create_output_directory(options['output'], options['use_tstamp'])
@@ -153,6 +158,7 @@ class Problem:
         _keep_checkpoint_freq(input_dict, ymlstring)
         _keep_probes(input_dict, ymlstring)
         _keep_integrals(input_dict, ymlstring)
+        _keep_extrema(input_dict, ymlstring)
         return cls._from_dict(input_dict, device=device)
 
     @classmethod
@@ -594,6 +600,91 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'integrals.npz'), **self.integrals._asdict())
 
     # -------------------------------------------------------------------------------------
+    # field extrema (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _extrema_refusal(self):
+        if self._gp_models.get('zz') is not None:
+            raise ValueError("extrema: p_max and p_min are the equation of state's pressure; this problem's pressure is a surrogate")
+
+    def set_extrema(self, every=1):
+        """Record where the extremes of the committed state sit after every step whose count is a multiple of `every`, on the
+        device, whichever way the steps are taken (`update()`, `run()`, batches of any length, the stage-wise pipeline of
+        shear-thinning, elastic and surrogate-shear problems).
+
+        Per record, over the interior cells 1..Nx x 1..Ny, each with its cell (ix, iy) of the ghosted index space: p_max, p_min
+        (the equation of state's pressure of the committed density: bit for bit the `p` a probe at that cell records), rho_max,
+        rho_min, h_min (the gap the device holds: deformed, for an elastic gap, as `topo.h` shows it after that step), u_max,
+        v_max (|jx / rho|, |jy / rho|).  Ties go to the smallest ix, then the smallest iy.  The same state gives the same bits
+        whatever the batch size or stride; on grids small enough for the one-workgroup kernel the records are written inside
+        the batch, which is not cut.  rho = 0 makes a velocity inf: plain IEEE, not special-cased.
+        A step that is rolled back as invalid leaves no record.  Starts a new series (see ``extrema``).  Checkpoints do not
+        carry the series: a problem restored from one whose options hold `extrema` has them armed again and its series
+        begins at the restart step.  Not available when the pressure is a surrogate."""
+        self._extrema_refusal()
+        every = _extrema_stride(every, allow_zero=False)
+        _lib.check(self._lib.gpf_extrema_set(self._h, every))
+        self._extrema_every = every
+        self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
+
+    def clear_extrema(self):
+        """Stop recording and drop the series."""
+        if self._extrema_every is not None:
+            _lib.check(self._lib.gpf_extrema_clear(self._h))
+        self._extrema_every = None
+
+    @property
+    def extrema(self):
+        """FieldExtrema(step, time, p_max, ..., v_max, cells, index) of every recorded step since set_extrema (or _pre_run),
+        across `update()` and `run()` calls; None when no extrema are armed.  cells[n, index[name]] is the (ix, iy) of `name`."""
+        if self._extrema_every is None:
+            return None
+        nq = len(_lib.EXTREMA_NAMES)
+        vals = np.concatenate(self._extrema_values) if self._extrema_values else np.empty((0, nq))
+        cells = np.concatenate(self._extrema_cells) if self._extrema_cells else np.empty((0, nq, 2), dtype=np.int32)
+        return FieldExtrema(np.array(self._extrema_steps, dtype=np.int64), np.array(self._extrema_times, dtype=np.float64),
+                            *[vals[:, k] for k in range(nq)], cells, {name: k for k, name in enumerate(_lib.EXTREMA_NAMES)})
+
+    def field_extrema(self):
+        """The same record for the current state, as a dict: the seven names of ``extrema`` and, for each, `<name>_cell` =
+        (ix, iy).  Bit for bit what a step committing this state would have recorded.  Armed or not.  Reads only."""
+        self._extrema_refusal()
+        self._sync_to_device()
+        vals = np.empty(len(_lib.EXTREMA_NAMES))
+        cells = np.zeros((len(_lib.EXTREMA_NAMES), 2), dtype=np.int32)
+        _lib.check(self._lib.gpf_extrema_now(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32))))
+        res = {}
+        for k, name in enumerate(_lib.EXTREMA_NAMES):
+            res[name] = np.float64(vals[k])
+            res[name + '_cell'] = (int(cells[k, 0]), int(cells[k, 1]))
+        return res
+
+    def _collect_extrema(self, entries, before):
+        """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
+        if self._extrema_every is None or not entries:
+            return
+        n = _integral_records(before, len(entries), self._extrema_every)
+        nq = len(_lib.EXTREMA_NAMES)
+        vals = np.empty((n, nq))
+        cells = np.zeros((n, nq, 2), dtype=np.int32)
+        steps = np.zeros(n, dtype=np.int64)
+        have = C.c_int64(0)
+        _lib.check(self._lib.gpf_extrema_read(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                              steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
+        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._extrema_every == 0]
+        if have.value != n or steps.tolist() != want:
+            raise _lib.GapflowHipError(f"extrema: {have.value} records of steps {steps.tolist()} for the committed steps "
+                                       f"{before + 1}..{before + len(entries)} at stride {self._extrema_every}")
+        self._extrema_steps.extend(want)
+        self._extrema_times.extend(entries[s - before - 1].simtime for s in want)
+        self._extrema_values.append(vals)
+        self._extrema_cells.append(cells)
+
+    def _write_extrema(self):
+        s = self.extrema._asdict()
+        index = s.pop('index')
+        np.savez(os.path.join(self.outdir, 'extrema.npz'), names=np.array(sorted(index, key=index.get)), **s)
+
+    # -------------------------------------------------------------------------------------
     # run loop (problem.py:368-503)
     # -------------------------------------------------------------------------------------
     def _features(self):
@@ -622,6 +713,8 @@ class Problem:
             self._probe_steps, self._probe_times, self._probe_data = [], [], []
         if self._integral_every is not None:
             self._integral_steps, self._integral_times, self._integral_data = [], [], []
+        if self._extrema_every is not None:
+            self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
 
     def _absorb(self, entries):
         """Fold the per-step records of a batch into the host-side mirror of the run state."""
@@ -650,6 +743,7 @@ class Problem:
         self._absorb(entries)
         self._collect_probes(entries)
         self._collect_integrals(entries, before)
+        self._collect_extrema(entries, before)
         if ran > 0:
             self._mark_device_advanced()
         failed = ran < n and log[ran].invalid != 0 if ran < n else False
@@ -696,6 +790,7 @@ class Problem:
         for m in self._gp_models.values():
             m.sync_scales()                 # the sound speed that closes the step sees the current scales too
         sc = _lib.GpfScalars()
+        before = self.step
         _lib.check(lib.gpf_close_step(h, C.byref(sc)))
         if sc.invalid:
             self._finalize(sc.invalid)
@@ -707,6 +802,7 @@ class Problem:
             self.topo.mark_stale()
         self._absorb([sc])
         self._collect_probes([sc])
+        self._collect_extrema([sc], before)     # (an elastic gap's record was taken behind gpf_elastic_update, of the deformed gap)
         self._mark_device_advanced()
         # the derived fields on the device ARE what the reference's field objects hold now: the closures of the corrector stage
         # (problem.py:531-560; neither the averaging nor Topography.update re-evaluates them)
@@ -801,6 +897,8 @@ class Problem:
                 self._write_probes()
             if self._integral_every is not None:
                 self._write_integrals()
+            if self._extrema_every is not None:
+                self._write_extrema()
             for name, m in self._gp_models.items():  # problem.py:490-503
                 history_to_csv(os.path.join(self.outdir, f'gp_{name}.csv'), m.history)
                 with open(os.path.join(self.outdir, f'gp_{name}.txt'), 'w') as f:
@@ -970,6 +1068,26 @@ def _keep_integrals(input_dict, ymlstring):
         for key, n in (('integrals_sections_x', 'Nx'), ('integrals_sections_y', 'Ny')):
             if opts.get(key) is not None:
                 input_dict['options'][key] = _integral_sections(opts[key], int(grid[n]) if n in grid else 2**31 - 1, key)
+
+
+def _extrema_stride(every, allow_zero=True):
+    low = 0 if allow_zero else 1
+    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
+        raise ValueError(f"extrema: the stride must be an integer >= {low}, got {every!r}")
+    return int(every)
+
+
+def _keep_extrema(input_dict, ymlstring):
+    """`options.extrema: N` (the stride; 0 or absent: off) is this project's own key: read from the YAML text and set beside the
+    sanitised ones, like the integrals' -- only when given, so that every other input's dictionaries stay as they are.  Checked
+    here, on the host."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    if opts.get('extrema') is not None:
+        input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
 
 
 def _in_main_thread():

@@ -427,11 +427,21 @@ class SlabProblem:
         """Film integrals are reduced on unsliced problems only."""
         raise NotImplementedError("integrals: not available on a SlabProblem")
 
+    def set_extrema(self, *args, **kwargs):
+        """Field extrema are recorded on unsliced problems only."""
+        raise NotImplementedError("extrema: not available on a SlabProblem")
+
+    def field_extrema(self, *args, **kwargs):
+        """Field extrema are taken on unsliced problems only."""
+        raise NotImplementedError("extrema: not available on a SlabProblem")
+
     def __init__(self, input_dict, device=0, dist=None):
         if (input_dict.get('options') or {}).get('probes') is not None:
             raise NotImplementedError("probes: not available on a SlabProblem")      # options.probes: as set_probes
         if (input_dict.get('options') or {}).get('integrals') is not None:
             raise NotImplementedError("integrals: not available on a SlabProblem")   # options.integrals: as set_integrals
+        if (input_dict.get('options') or {}).get('extrema'):                         # (0: off, as on a Problem)
+            raise NotImplementedError("extrema: not available on a SlabProblem")     # options.extrema: as set_extrema
         import torch
         if dist is None:
             import torch.distributed as dist
@@ -558,12 +568,13 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals
+        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
         _keep_probes(d, text)                       # options.probes: refused below
         _keep_integrals(d, text)                    # options.integrals: refused below
+        _keep_extrema(d, text)                      # options.extrema: refused below
         return cls(d, device=device, dist=dist)
 
     @classmethod

@@ -478,6 +478,50 @@ int gpf_integrals_now(gpf_handle* h, double* out, int64_t count);
  * Probes are put aside in both modes. */
 int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- field extrema (no reference counterpart: the reference's users run np.argmax on a downloaded field) ------------------ */
+/* Where the extremes of the COMMITTED state sit, found on the device so that gpf_step keeps advancing whole batches.  A record
+ * is seven values, each with its cell (ix, iy) of the ghosted index space, taken over the interior cells 1..Nx x 1..Ny:
+ *   0 p_max, 1 p_min       eos_pressure(rho) of the committed density, by the device function the probes' p uses: bit for bit
+ *                          what a probe at that cell records
+ *   2 rho_max, 3 rho_min   the density
+ *   4 h_min                the gap height, plane 0 of the handle's topography as the device holds it (deformed, for an elastic gap)
+ *   5 u_max, 6 v_max       |jx / rho|, |jy / rho| (IEEE division)
+ * Host layout: values [record][7] doubles, cells [record][7][2] int32 (ix, iy).  Candidates are ordered by ONE comparison, a
+ * total order on (value, ix, iy): the larger (smaller, for a minimum) value first, then the smaller ix, then the smaller iy.
+ * So ties go to the smallest ix, then the smallest iy, the result does not depend on the shape of the reduction, and a record
+ * is a pure function of the state: the same bits whatever the batch size, the stride or the kernel that wrote it.  No
+ * floating-point atomics, no arrival order.  A committed state has no NaN and rho >= 0; rho = 0 makes |j / rho| inf under IEEE
+ * comparison (NaN for j = 0, which is never selected): this is not special-cased.  Recording only reads: q and all scalars of
+ * a run are bitwise those of the same run without extrema, and with none armed no launch and no kernel argument but a null
+ * pointer differs.
+ *   gpf_extrema_set    arms recording after every committed step whose new step count is a multiple of `every` and starts
+ *                      with empty records.  GPF_ERR_INVALID for every < 1 and on a handle whose pressure comes from a surrogate
+ *                      (surrogate wall shear alone is fine); GPF_ERR_STATE on a slab and while a stage-wise step is open.
+ *   gpf_extrema_clear  disarms and frees the buffers.
+ *   gpf_extrema_read   the records of the LAST stepping call (gpf_step; gpf_close_step, one closed step) and the step count of
+ *                      each in steps_out (values, cells, steps_out may be NULL); *n_records how many the call left,
+ *                      min(*n_records, capacity_records) are copied.  A batch that stopped on the device leaves the records of
+ *                      the steps that ran; a step that was rolled back as invalid leaves none.  GPF_ERR_STATE unless armed.
+ *   gpf_extrema_now    the same record for the current committed state, armed or not; GPF_ERR_STATE on an invalid run state.
+ * Where they are written: k_extrema_partial (one workgroup per interior row, 4 planes read) + k_extrema_fold
+ * (csrc/extrema_kernels.hip) behind every launch-per-step step and behind gpf_close_step, told the step count the step produces
+ * if it commits and writing only if the device's run state shows that count and a valid state; inside k_small_steps after the
+ * commit, from the field the workgroup holds -- the batch is NOT cut, every = 1 keeps the whole batch in one launch.  On an
+ * elastic handle the gap deforms after the step closes: the closed step's record is written by the gpf_elastic_update that
+ * follows it, with the gap the handle then holds (no gpf_elastic_update, no record).  gpf_step_timed and the slab calls record
+ * nothing.  Record buffers ((log_cap + 1) records) and a row scratch are allocated on first use and freed by
+ * gpf_extrema_clear / gpf_destroy once the stream is idle.  Pairs of columns are fetched with one 16-byte load per plane where
+ * the buffers are aligned for it and with 8-byte loads otherwise; GPF_FILM_NARROW (read when the buffers are allocated) asks for
+ * the 8-byte loads regardless -- a test switch; the records are the same in every bit. */
+int gpf_extrema_set(gpf_handle* h, int64_t every);
+int gpf_extrema_clear(gpf_handle* h);
+int gpf_extrema_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14]);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording (armed extrema are put aside for the call), 1 recording at the armed stride (tools/extrema_time.py).
+ * Probes and film integrals are put aside in both modes. */
+int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* ---- ensembles (no reference counterpart: the reference runs a parameter study as one process per problem) ---------------- */
 /* Many small problems advanced by ONE launch per kernel instantiation: workgroup m of k_small_ensemble runs, on member m's own
  * buffers, the very body that k_small_steps runs for a handle alone (csrc/small_kernel.hip), so a member's field, run state
@@ -488,7 +532,7 @@ int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms);
  *                         workgroups would write the same buffers); a member that the one-workgroup kernel cannot take (grid
  *                         beyond 150 KB of LDS at 16 doubles per ghosted cell, shear thinning, slab halo, surrogate set, elastic
  *                         gap, or GPF_SMALL_GRID=0 in the environment); members on different devices or streams (one launch
- *                         needs one stream); film integrals or probes armed on a member.
+ *                         needs one stream); film integrals, probes or extrema armed on a member.
  *   gpf_ensemble_step     n[i] steps for member i, 0 <= n[i] <= 4096 (the log's capacity); 0 leaves the member alone: it is not
  *                         launched and nothing of it is touched.  honor_stop as in gpf_step, for all members.  The members
  *                         to advance are grouped by instantiation (equation of state, slip-length field present or not); each
