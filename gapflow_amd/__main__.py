@@ -11,7 +11,10 @@ peer-to-peer mailbox transport instead of one all-gather per step.
 ``python -m gapflow_amd -i a.yaml b.yaml c.yaml`` runs several small problems together as an ensemble, one workgroup of one
 launch each (gapflow_amd/ensemble.py); every one of them writes what it would write run alone.
 
-``python -m gapflow_amd --restart out/checkpoint.gpf [--output DIR] [--max-it N]`` continues a run from a checkpoint."""
+``python -m gapflow_amd --restart out/checkpoint.gpf [--output DIR] [--max-it N]`` continues a run from a checkpoint.
+
+``python -m gapflow_amd -i fine.yaml --init-from coarse_out/checkpoint.gpf`` starts a run from the state of a run on another grid
+of the same domain, resampled on the device (Problem.init_from; the same as `options.init_from` in the YAML file)."""
 import argparse
 import os
 import sys
@@ -37,6 +40,8 @@ def make_parser():
                      "options, with '_restart' appended when they name a fixed directory; frames go into a new sol.nc, history.csv "
                      "continues the saved history)")
     cli.add_argument('--max-it', type=int, metavar='N', help="with --restart: run until step N instead of the saved run's max_it")
+    cli.add_argument('--init-from', metavar='CHECKPOINT', help="with one -i file: start from the state of this checkpoint, written by a run on "
+                     "another grid of the same domain, resampled onto this grid (overrides options.init_from of the file)")
     cli.add_argument('--device', type=int, default=0, help="HIP device ordinal of a single-process run (default 0)")
     return cli
 
@@ -64,6 +69,8 @@ def main(argv=None):
     if opts.restart is None and (opts.output or opts.max_it is not None):
         cli.error("--output and --max-it go with --restart")
     several = len(getattr(opts, 'filenames', None) or []) > 1
+    if opts.init_from and (opts.restart or several or int(os.environ.get('WORLD_SIZE', '1')) > 1):
+        cli.error("--init-from goes with one -i file in a single-process run")
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
         if several:
             cli.error("several -i files run as an ensemble on one GPU; a multi-process (slab) run takes one")
@@ -88,6 +95,8 @@ def main(argv=None):
     elif several:
         from .ensemble import Ensemble
         Ensemble.from_yaml(opts.filenames, device=opts.device).run()
+    elif opts.init_from:
+        Problem.from_yaml(opts.filename, device=opts.device, init_from=opts.init_from).run()
     else:
         Problem.from_yaml(opts.filename, device=opts.device).run()
     return 0

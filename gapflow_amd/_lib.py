@@ -159,6 +159,8 @@ SIGNATURES = {
     'gpf_ensemble_log': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfScalars), C.c_int64, C.POINTER(C.c_int64)]),
     'gpf_ensemble_destroy': (C.c_int, [C.c_void_p]),
     'gpf_ensemble_limits': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    'gpf_resample': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'gpf_resample_time': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _DP]),
 }
 
 _lib = None

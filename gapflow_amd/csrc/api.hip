@@ -24,6 +24,7 @@
 #include "profile_kernels.hip"
 #include "checkpoint_kernels.hip"
 #include "integral_kernels.hip"
+#include "resample_kernels.hip"
 
 using namespace gpf;
 
@@ -244,6 +245,24 @@ static int ensure_stage(gpf_handle* h, size_t doubles) {
     return GPF_OK;
 }
 
+// Handles that sit in a live ensemble (gpf_ensemble_create .. gpf_ensemble_destroy), counted per handle.  Kept by address and
+// never dereferenced, so that the order in which members and their ensemble are destroyed is free.
+static std::mutex& ensemble_members_lock() { static std::mutex m; return m; }
+static std::map<const gpf_handle*, int>& ensemble_members() { static std::map<const gpf_handle*, int> m; return m; }
+static void ensemble_members_add(const gpf_handle* h) {
+    std::lock_guard<std::mutex> g(ensemble_members_lock());
+    ensemble_members()[h] += 1;
+}
+static void ensemble_members_drop(const gpf_handle* h, bool all) {
+    std::lock_guard<std::mutex> g(ensemble_members_lock());
+    auto it = ensemble_members().find(h);
+    if (it != ensemble_members().end() && (all || --it->second <= 0)) ensemble_members().erase(it);
+}
+static bool ensemble_members_has(const gpf_handle* h) {
+    std::lock_guard<std::mutex> g(ensemble_members_lock());
+    return ensemble_members().count(h) != 0;
+}
+
 #include "api_fields.inc"
 
 extern "C" int gpf_create(const gpf_config* cfg, gpf_handle** out) {
@@ -355,6 +374,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     if (h->p2p.seq) hipFree(h->p2p.seq);
     for (void* p : ptrs)
         if (p) hipFree(p);
+    ensemble_members_drop(h, true);
     delete h;
     return GPF_OK;
 }
@@ -1090,3 +1110,4 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
 #include "api_profiles.inc"
 #include "api_checkpoint.inc"
 #include "api_ensemble.inc"
+#include "api_resample.inc"

@@ -47,6 +47,7 @@ extern "C" int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemb
     e->members.assign(members, members + m);
     e->device = members[0]->cfg.device;
     e->entries.assign(m, 0);
+    for (gpf_handle* h : e->members) ensemble_members_add(h);
     hipError_t err = hipMalloc(&e->dev, e->bytes());
     if (err == hipSuccess) err = hipHostMalloc((void**)&e->host, e->bytes(), hipHostMallocDefault);
     if (err != hipSuccess) {
@@ -59,6 +60,7 @@ extern "C" int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemb
 
 extern "C" int gpf_ensemble_destroy(gpf_ensemble* e) {
     if (!e) return GPF_OK;
+    for (gpf_handle* h : e->members) ensemble_members_drop(h, false);
     hipSetDevice(e->device);
     if (e->dev) hipFree(e->dev);
     if (e->host) hipHostFree(e->host);

@@ -121,6 +121,9 @@ class Problem:
         if options.get('extrema'):                  # options.extrema (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_extrema(options['extrema'])
 
+        if options.get('init_from'):                # options.init_from (from the YAML text, or --init-from): start from another grid's state
+            self.init_from(options['init_from'])
+
         if not options['silent']:
             self.outdir = create_output_directory(options['output'], options['use_tstamp'])
             if database is not None:            # problem.py:158-164: MD datasets go below the run's output directory
@@ -146,19 +149,24 @@ class Problem:
     # constructors (problem.py:211-308)
     # -------------------------------------------------------------------------------------
     @classmethod
-    def from_yaml(cls, fname, device=0):
+    def from_yaml(cls, fname, device=0, init_from=None):
+        """init_from: a checkpoint to start from (see ``init_from``), in place of the file's own `options.init_from`; a relative
+        path in the FILE is relative to the file, one given here to the working directory."""
         print(f"Reading input file: {fname}")
         with open(fname, "r") as f:
-            return cls.from_string(f.read(), device=device)
+            return cls.from_string(f.read(), device=device, init_from=init_from, base_dir=os.path.dirname(os.path.abspath(fname)))
 
     @classmethod
-    def from_string(cls, ymlstring, device=0):
+    def from_string(cls, ymlstring, device=0, init_from=None, base_dir=None):
         with _io.StringIO(ymlstring) as f:
             input_dict = read_yaml_input(f)
         _keep_checkpoint_freq(input_dict, ymlstring)
         _keep_probes(input_dict, ymlstring)
         _keep_integrals(input_dict, ymlstring)
         _keep_extrema(input_dict, ymlstring)
+        _keep_init_from(input_dict, ymlstring, base_dir)
+        if init_from is not None:
+            input_dict['options']['init_from'] = os.path.abspath(os.fspath(init_from))
         return cls._from_dict(input_dict, device=device)
 
     @classmethod
@@ -421,6 +429,7 @@ class Problem:
         except ValueError as e:
             raise RuntimeError(str(e)) from None
         inp = meta['inputs']
+        inp['options'].pop('init_from', None)       # where the saved run started from; the blob brings the state
         for given, allowed, target in ((options, ('output', 'silent', 'use_tstamp', 'write_freq', 'checkpoint_freq'), inp['options']),
                                        (numerics, ('max_it', 'tol'), inp['numerics'])):
             for k, v in (given or {}).items():
@@ -437,6 +446,60 @@ class Problem:
 
     def _write_checkpoint(self):
         self.save_checkpoint(os.path.join(self.outdir, 'checkpoint.gpf'))
+
+    # -------------------------------------------------------------------------------------
+    # a state from another grid (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def init_from(self, source):
+        """Take the state of `source` -- a Problem on another grid of the same domain, or the path of a checkpoint.gpf of one --
+        resampled onto this problem's grid, on the device (gpf_resample): bilinear interpolation of rho and of the flow rates
+        jx h, jy h over the source's ghosted cells at this grid's cell centres, divided by this problem's own gap; the ghost
+        cells then follow this problem's boundary conditions.  A converged coarse run is a start for a fine one that saves
+        most of its steps (measured in 1-D only).  Coarsening goes through the same rule and is NOT
+        conservative.
+
+        Allowed at any time.  Before the first step the run simply begins from the new state; after steps the run starts
+        over at step 0 (`_pre_run`), as it would from a state assigned to ``q``, and the probes', integrals' and extrema
+        series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
+        which is destroyed before the call returns.
+        ValueError: the domains differ (Lx or Ly by more than 1e-12 relative), or a direction is periodic on one side only.
+        NotImplementedError: surrogate closures here, or a SlabProblem as the source."""
+        from . import resample
+        from .slab import SlabProblem
+        if self.has_gp_model or self._gp_models:
+            raise NotImplementedError("init_from: this problem's closures are surrogates (resampling does not cover them)")
+        if isinstance(source, SlabProblem):
+            raise NotImplementedError("init_from: a SlabProblem cannot be a source (gather its state into a Problem)")
+        tmp = None
+        if isinstance(source, (str, os.PathLike)):
+            from . import checkpoint
+            path = os.fspath(source)
+            try:
+                meta, _ = checkpoint.read_file(path)
+            except ValueError as e:
+                raise RuntimeError(str(e)) from None
+            if meta.get('kind') != 'problem':
+                raise NotImplementedError(f"init_from: {path} holds one rank of a slab run (kind '{meta.get('kind')}')")
+            resample.check_geometry(self.grid, meta['inputs']['grid'])
+            source = tmp = Problem.from_checkpoint(path, device=self._cfg.device, options={'silent': True})
+        elif not isinstance(source, Problem):
+            raise TypeError(f"init_from: a Problem or the path of a checkpoint is required, got {type(source).__name__}")
+        if source is self:
+            raise ValueError("init_from: a problem cannot be its own source")
+        try:
+            resample.check_geometry(self.grid, source.grid)
+            if source._cfg.device != self._cfg.device:
+                raise ValueError(f"init_from: the source lives on device {source._cfg.device}, this problem on device {self._cfg.device}")
+            resample.check_axes(self.grid, source.grid)
+            source._sync_to_device()
+            self._sync_to_device()
+            _lib.check(self._lib.gpf_resample(self._h, source._h))
+        finally:
+            if tmp is not None:
+                tmp.__del__()
+        self._mark_device_advanced()                        # q and the closures are read from the device again
+        if self.step is not None:
+            self._pre_run()
 
     # -------------------------------------------------------------------------------------
     # point probes (no reference counterpart; DESIGN.md 3.3e)
@@ -1088,6 +1151,23 @@ def _keep_extrema(input_dict, ymlstring):
         return
     if opts.get('extrema') is not None:
         input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
+
+
+def _keep_init_from(input_dict, ymlstring, base_dir=None):
+    """`options.init_from: path` (a checkpoint to start from, Problem.init_from) is this project's own key: read from the YAML
+    text and set beside the sanitised ones, like checkpoint_freq -- only when given, so that every other input's dictionaries
+    stay as they are.  A relative path is relative to the YAML file (`base_dir`; a string has none: the working directory)."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    path = opts.get('init_from')
+    if path is None:
+        return
+    if not isinstance(path, str) or not path:
+        raise ValueError(f"options.init_from: the path of a checkpoint file is required, got {path!r}")
+    input_dict['options']['init_from'] = os.path.normpath(os.path.join(base_dir or os.getcwd(), path))
 
 
 def _in_main_thread():

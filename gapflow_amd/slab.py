@@ -435,7 +435,13 @@ class SlabProblem:
         """Field extrema are taken on unsliced problems only."""
         raise NotImplementedError("extrema: not available on a SlabProblem")
 
+    def init_from(self, *args, **kwargs):
+        """States are resampled onto unsliced problems only."""
+        raise NotImplementedError("init_from: not available on a SlabProblem")
+
     def __init__(self, input_dict, device=0, dist=None):
+        if (input_dict.get('options') or {}).get('init_from'):
+            raise NotImplementedError("init_from: not available on a SlabProblem")   # options.init_from: as init_from
         if (input_dict.get('options') or {}).get('probes') is not None:
             raise NotImplementedError("probes: not available on a SlabProblem")      # options.probes: as set_probes
         if (input_dict.get('options') or {}).get('integrals') is not None:
@@ -567,20 +573,21 @@ class SlabProblem:
             h.value = None
 
     @classmethod
-    def from_string(cls, text, device=0, dist=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema
+    def from_string(cls, text, device=0, dist=None, base_dir=None):
+        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
         _keep_probes(d, text)                       # options.probes: refused below
         _keep_integrals(d, text)                    # options.integrals: refused below
         _keep_extrema(d, text)                      # options.extrema: refused below
+        _keep_init_from(d, text, base_dir)          # options.init_from: refused below
         return cls(d, device=device, dist=dist)
 
     @classmethod
     def from_yaml(cls, fname, device=0):
         with open(fname) as f:
-            return cls.from_string(f.read(), device=device)
+            return cls.from_string(f.read(), device=device, base_dir=os.path.dirname(os.path.abspath(fname)))
 
     def _upload(self, field, arr):
         a = _lib.f64c(arr)

@@ -563,6 +563,25 @@ int gpf_ensemble_log(gpf_ensemble* e, int member, gpf_scalars_t* log, int64_t lo
 int gpf_ensemble_destroy(gpf_ensemble* e);
 int gpf_ensemble_limits(int64_t* lds_bytes, int32_t* doubles_per_cell, int64_t* max_steps);
 
+/* ---- resampling a state onto another grid (no reference counterpart) ------------------------------- */
+/* dst's state from src's committed state, both covering the same domain with different (Nx, Ny): bilinear interpolation, over
+ * src's ghosted cells at dst's interior cell centres, of rho and the flow rates jx h, jy h (h: plane 0 of the gap src holds,
+ * the deformed one of an elastic handle); dst gets jx = (jx h)_interp / h_dst with its own gap, and its ghost cells from its own
+ * edge rules.  Per axis, for dst cell i = 1..N_dst: s = (i - 1/2) (d_dst / d_src) + 1/2 in ONE rounding (fma),
+ * i0 = floor(s) clamped to 0..N_src, w = s - i0, value = (1 - w) f[i0] + w f[i0 + 1]; an axis of extent 1 on both sides copies
+ * the single interior line.  Coarsening goes through the same rule and is not conservative.
+ * src is only read: its stream is synchronised first, then the kernels run on dst's stream and the call returns when they have
+ * finished.  Afterwards dst is what gpf_upload of that field into GPF_FIELD_Q leaves (run state untouched: call gpf_pre_run).
+ * Refused, with dst unchanged: a null handle, dst == src, handles on different devices, Lx or Ly differing by more than 1e-12
+ * relative, a direction periodic on one side only, a surrogate pressure on dst (GPF_ERR_INVALID); a slab or an open stage-wise
+ * step on either side, q or gap missing on either side, a source whose run state is flagged invalid, a dst that is a member
+ * of a live ensemble (GPF_ERR_STATE). */
+int gpf_resample(gpf_handle* dst, const gpf_handle* src);
+/* Diagnostic (tools/resample_time.py): `reps` (1..10000) launches on dst's stream, *ms per launch, of mode 0 what gpf_resample
+ * enqueues, 1 a kernel with the same stores of a constant and no source reads.  Both write the buffer that does NOT hold dst's
+ * state: the state and the run state stay. */
+int gpf_resample_time(gpf_handle* dst, const gpf_handle* src, int mode, int reps, double* ms);
+
 /* Diagnostic: time of one pass of an elementwise kernel that reads `nin` and writes `nout` fp64 planes of
  * `doubles_per_plane` elements (16 bytes per lane, grid-stride): what THIS device streams for the byte count of a fused
  * step.  bench.py reports it beside the step kernel's HBM figure (no reference counterpart: the reference has no device). */
