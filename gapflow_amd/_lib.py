@@ -44,6 +44,8 @@ SMALL_GRID_LDS_BYTES, SMALL_GRID_DOUBLES_PER_CELL = 150 * 1024, 16      # what o
 LOG_CAPACITY = 4096                 # per-step records a handle's device log holds: the longest batch
 EXTREMA_NAMES = ('p_max', 'p_min', 'rho_max', 'rho_min', 'h_min', 'u_max', 'v_max')     # gpf_extrema_*: the record's order
 INTEGRAL_SUMS = ('load', 'load_x', 'load_y', 'p_hx', 'p_hy', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')
+WEIGHTED_MAX_PLANES = 8             # gpf_weighted_set: weight planes per handle
+WEIGHTED_INTEGRANDS = ('p', 'h', 'rho_h', 'jx_h', 'jy_h', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')    # gpf_weighted_*: the record's order
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -149,6 +151,11 @@ SIGNATURES = {
     'gpf_integrals_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_integrals_now': (C.c_int, [C.c_void_p, _DP, C.c_int64]),
     'gpf_integrals_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_weighted_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_weighted_clear': (C.c_int, [C.c_void_p]),
+    'gpf_weighted_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_weighted_now': (C.c_int, [C.c_void_p, _DP, C.c_int64]),
+    'gpf_weighted_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_extrema_set': (C.c_int, [C.c_void_p, C.c_int64]),
     'gpf_extrema_clear': (C.c_int, [C.c_void_p]),
     'gpf_extrema_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -24,6 +24,7 @@
 #include "profile_kernels.hip"
 #include "checkpoint_kernels.hip"
 #include "integral_kernels.hip"
+#include "weighted_kernels.hip"
 #include "resample_kernels.hip"
 
 using namespace gpf;
@@ -108,6 +109,12 @@ struct gpf_handle {
     // GPF_FILM_NARROW was set then, 8-byte loads); the records of the last stepping call and their step counts on the host
     struct { long long every = 0; int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
              double* rec = nullptr; double* part = nullptr; bool narrow = false; std::vector<double> host; std::vector<long long> steps; } integ;
+    // weighted film integrals (api_weighted.inc): recording stride (0: not armed) and number of weight planes K; the planes on the
+    // device in this handle's Layout ([K] planes, pitch and offset as topo's, ghost cells zero), the row scratch ([K][Nx][9]) and the
+    // device records of the batch in flight ([log_cap + 1][K][9]), all allocated by gpf_weighted_set (`narrow`: GPF_FILM_NARROW was
+    // set then, 8-byte loads); the records of the last stepping call and their step counts on the host
+    struct { long long every = 0; int K = 0; double* w = nullptr; double* part = nullptr; double* rec = nullptr; bool narrow = false;
+             std::vector<double> host; std::vector<long long> steps; } weighted;
     // field extrema (api_extrema.inc): recording stride (0: not armed); the device records of the batch in flight ([log_cap + 1][7]
     // doubles, [log_cap + 1][14] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was set then);
     // `dev`: the ExtremaArgs of these buffers in device memory, for k_small_steps; the records of the last stepping call on the host.
@@ -353,7 +360,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -1016,6 +1023,7 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
 }
 
 #include "api_integrals.inc"
+#include "api_weighted.inc"
 #include "api_extrema.inc"
 
 extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t* log, int64_t log_capacity,
@@ -1031,16 +1039,19 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     const bool small = small_grid_eligible(h);
     GPF_TRY(probes_begin(h));
     GPF_TRY(integrals_begin(h));
+    GPF_TRY(weighted_begin(h));
     GPF_TRY(extrema_begin(h));
     while (done < n) {
         const int64_t batch = std::min<int64_t>(n - done, h->log_cap);
         const long long base = h->host_step;
-        if (small && h->integ.every) GPF_TRY(integrals_small_batch(h, batch, honor_stop, base));     // the batch, cut at the recorded steps
+        if (small && h->weighted.every) GPF_TRY(weighted_small_batch(h, batch, honor_stop, base));     // cut at the union of both series' steps
+        else if (small && h->integ.every) GPF_TRY(integrals_small_batch(h, batch, honor_stop, base));     // the batch, cut at the recorded steps
         else if (small) GPF_TRY(enqueue_small_steps(h, (int)batch, honor_stop, base));
         else for (int64_t i = 0; i < batch; ++i) {
             GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
             GPF_TRY(probes_launch(h, base + i + 1, base));      // no launch without probes
             GPF_TRY(integrals_launch(h, base + i + 1, base));   // nor without integrals, nor off their stride
+            GPF_TRY(weighted_launch(h, base + i + 1, base));    // nor without weighted integrals, nor off theirs
             GPF_TRY(extrema_launch(h, base + i + 1, base));     // nor without extrema, nor off theirs
         }
         StepState s;
@@ -1048,6 +1059,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
         const long long ran = s.step - base;
         GPF_TRY(probes_collect(h, ran));
         GPF_TRY(integrals_collect(h, base, ran));
+        GPF_TRY(weighted_collect(h, base, ran));
         GPF_TRY(extrema_collect(h, base, ran));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);
         if (log && entries > 0) {

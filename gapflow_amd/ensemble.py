@@ -41,6 +41,9 @@ def _refusal(p):
                                      f"{_lib.SMALL_GRID_LDS_BYTES // 1024} KB)")
     if p._integral_every is not None:
         return NotImplementedError, "film integrals are armed on it (they cut the batch per member): clear_integrals(), or run it alone"
+    if getattr(p, '_weighted_every', None) is not None:        # (getattr: a Problem made without __init__ has no such attribute)
+        return NotImplementedError, ("weighted integrals are armed on it (they cut the batch per member): clear_weighted_integrals(), "
+                                     "or run it alone")
     if p._probe_cells is not None:
         return NotImplementedError, "probes are armed on it (their records need per-member slots): clear_probes(), or run it alone"
     if p._extrema_every is not None:

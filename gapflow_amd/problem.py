@@ -33,6 +33,8 @@ ProbeSeries = namedtuple('ProbeSeries', 'step time cells rho jx jy p')
 ProbeSeries.__doc__ = """Time series of Problem.probes: step, time (nrecords,), cells (nprobes, 2), rho, jx, jy, p (nrecords, nprobes); p None if not asked for."""
 FilmIntegrals = namedtuple('FilmIntegrals', ('step', 'time') + _lib.INTEGRAL_SUMS + ('flow_x', 'flow_y', 'sections_x', 'sections_y'))
 FilmIntegrals.__doc__ = """Time series of Problem.integrals: step, time and the nine area integrals (nrecords,), flow_x (nrecords, len(sections_x)), flow_y (nrecords, len(sections_y)), the sections' interior rows / columns."""
+WeightedIntegrals = namedtuple('WeightedIntegrals', ('step', 'time', 'names') + _lib.WEIGHTED_INTEGRANDS)
+WeightedIntegrals.__doc__ = """Time series of Problem.weighted_integrals: step, time (nrecords,), names (the K weight planes'), and per integrand an array (nrecords, K)."""
 FieldExtrema = namedtuple('FieldExtrema', ('step', 'time') + _lib.EXTREMA_NAMES + ('cells', 'index'))
 FieldExtrema.__doc__ = """Time series of Problem.extrema: step, time and the seven values (nrecords,), cells (nrecords, 7, 2) -- (ix, iy) of each value in the ghosted index space --, index: name -> position along the cells' second axis."""
 
@@ -117,6 +119,13 @@ class Problem:
         self._integral_every = None
         if options.get('integrals') is not None:    # options.integrals (from the YAML text, or carried by a checkpoint's dictionaries)
             self.set_integrals(options['integrals'], options.get('integrals_sections_x'), options.get('integrals_sections_y'))
+        self._weighted_every = None
+        if options.get('weighted_integrals'):       # options.weighted_integrals / options.weights (from the YAML text, or a checkpoint's dictionaries); 0: off
+            from . import weights as _weights
+            if not options.get('weights'):
+                raise ValueError("options.weighted_integrals: options.weights must list the weight planes")
+            planes, names = _weights.from_entries(grid, options['weights'])
+            self.set_weighted_integrals(planes, options['weighted_integrals'], names)
         self._extrema_every = None
         if options.get('extrema'):                  # options.extrema (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_extrema(options['extrema'])
@@ -164,6 +173,7 @@ class Problem:
         _keep_probes(input_dict, ymlstring)
         _keep_integrals(input_dict, ymlstring)
         _keep_extrema(input_dict, ymlstring)
+        _keep_weighted(input_dict, ymlstring, base_dir)
         _keep_init_from(input_dict, ymlstring, base_dir)
         if init_from is not None:
             input_dict['options']['init_from'] = os.path.abspath(os.fspath(init_from))
@@ -459,8 +469,8 @@ class Problem:
         conservative.
 
         Allowed at any time.  Before the first step the run simply begins from the new state; after steps the run starts
-        over at step 0 (`_pre_run`), as it would from a state assigned to ``q``, and the probes', integrals' and extrema
-        series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
+        over at step 0 (`_pre_run`), as it would from a state assigned to ``q``, and the probes', integrals', weighted
+        integrals' and extrema series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
         which is destroyed before the call returns.
         ValueError: the domains differ (Lx or Ly by more than 1e-12 relative), or a direction is periodic on one side only.
         NotImplementedError: surrogate closures here, or a SlabProblem as the source."""
@@ -663,6 +673,94 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'integrals.npz'), **self.integrals._asdict())
 
     # -------------------------------------------------------------------------------------
+    # weighted film integrals (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _weighted_refusal(self):
+        if self.has_gp_model or self._gp_models:
+            raise NotImplementedError("weighted integrals: surrogate (GP) closures replace the pressure and wall stress the integrals evaluate")
+        if self._cfg.thinning:
+            raise NotImplementedError("weighted integrals: shear thinning needs grad p, which the reduction does not model")
+        if self._elastic or self.topo.elastic:
+            raise NotImplementedError("weighted integrals: an elastic gap steps stage-wise and deforms between steps (not supported)")
+
+    def set_weighted_integrals(self, weights, every=1, names=None):
+        """Record, for each of K <= 8 weight planes, the film's integrals with that weight in front after every step whose count
+        is a multiple of `every`, on the device, whichever way the steps are taken (`update()`, `run()`, batches of any length).
+
+        weights: array-like (K, Nx, Ny) or (Nx, Ny) over the INTERIOR cells (row ix of the ghosted field is row ix - 1); ghost
+        cells never contribute.  `gapflow_amd.weights` builds the usual ones: `box` (a pad, an asperity, a window), `mode` (one
+        Fourier mode), `load` (an .npy file).  names: one per plane, default w0, w1, ...
+        Per record and plane, summed over the interior cells and multiplied by dx dy: p (the pressure `load` of ``integrals``
+        sums: the plane's load), h, rho_h (the mass in the window), jx_h, jy_h, and tau_xz_bot, tau_yz_bot, tau_xz_top,
+        tau_yz_top (the walls' shear stresses as ``integrals`` evaluates them).  Plain integrals: NO sign convention is applied.
+        A weight of exactly 1.0 adds the cell's term bit for bit and 0.0 nothing, in the order ``integrals`` adds: a plane of
+        ones gives p and the tau_* equal to its load and tau_* in every bit, and the same state gives the same bits whatever
+        the batch size or stride.  On grids small enough for the one-workgroup kernel the batch is cut at every recorded step:
+        choose a stride there (every=1 costs one launch per step).
+        A step that is rolled back as invalid leaves no record.  Starts a new series (see ``weighted_integrals``).  Checkpoints
+        do not carry the series: a problem restored from one whose options hold `weighted_integrals` and `weights` has them
+        armed again and its series begins at the restart step; weights set from code do not survive a restore.  Not available
+        with surrogate closures, shear thinning or an elastic gap."""
+        self._weighted_refusal()
+        every = _weighted_stride(every)
+        planes, names = _weight_planes(weights, names, self.grid['Nx'], self.grid['Ny'])
+        ghosted = np.zeros((len(planes),) + self._shape)
+        ghosted[:, 1:-1, 1:-1] = planes
+        _lib.check(self._lib.gpf_weighted_set(self._h, every, len(planes), _lib.as_dp(ghosted)))
+        self._weighted_every, self._weighted_names = every, names
+        self._weighted_steps, self._weighted_times, self._weighted_data = [], [], []
+
+    def clear_weighted_integrals(self):
+        """Stop recording, drop the series and free the weight planes."""
+        if self._weighted_every is not None:
+            _lib.check(self._lib.gpf_weighted_clear(self._h))
+        self._weighted_every = None
+
+    @property
+    def weighted_integrals(self):
+        """WeightedIntegrals(step, time, names, p, h, rho_h, ...) of every recorded step since set_weighted_integrals (or
+        _pre_run), across `update()` and `run()` calls: one array (nrecords, K) per integrand; None when none are armed."""
+        if self._weighted_every is None:
+            return None
+        K, nq = len(self._weighted_names), len(_lib.WEIGHTED_INTEGRANDS)
+        data = np.concatenate(self._weighted_data) if self._weighted_data else np.empty((0, K, nq))
+        return WeightedIntegrals(np.array(self._weighted_steps, dtype=np.int64), np.array(self._weighted_times, dtype=np.float64),
+                                 tuple(self._weighted_names), *[data[:, :, k] for k in range(nq)])
+
+    def film_weighted(self):
+        """The same record for the current state, as {integrand: array(K)}: bit for bit what a step committing this state would
+        have recorded.  Needs armed weights (they live on the device).  Reads only."""
+        self._weighted_refusal()
+        if self._weighted_every is None:
+            raise RuntimeError("film_weighted: no weights are set (set_weighted_integrals)")
+        self._sync_to_device()
+        out = np.empty((len(self._weighted_names), len(_lib.WEIGHTED_INTEGRANDS)))
+        _lib.check(self._lib.gpf_weighted_now(self._h, _lib.as_dp(out), out.size))
+        return {name: out[:, k].copy() for k, name in enumerate(_lib.WEIGHTED_INTEGRANDS)}
+
+    def _collect_weighted(self, entries, before):
+        """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
+        if self._weighted_every is None or not entries:
+            return
+        n = _integral_records(before, len(entries), self._weighted_every)
+        out = np.empty((n, len(self._weighted_names), len(_lib.WEIGHTED_INTEGRANDS)))
+        steps = np.zeros(n, dtype=np.int64)
+        have = C.c_int64(0)
+        _lib.check(self._lib.gpf_weighted_read(self._h, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
+        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._weighted_every == 0]
+        if have.value != n or steps.tolist() != want:
+            raise _lib.GapflowHipError(f"weighted integrals: {have.value} records of steps {steps.tolist()} for the committed steps "
+                                       f"{before + 1}..{before + len(entries)} at stride {self._weighted_every}")
+        self._weighted_steps.extend(want)
+        self._weighted_times.extend(entries[s - before - 1].simtime for s in want)
+        self._weighted_data.append(out)
+
+    def _write_weighted(self):
+        s = self.weighted_integrals._asdict()
+        s['names'] = np.array(s['names'])
+        np.savez(os.path.join(self.outdir, 'weighted.npz'), **s)
+
+    # -------------------------------------------------------------------------------------
     # field extrema (no reference counterpart; DESIGN.md 3.3g)
     # -------------------------------------------------------------------------------------
     def _extrema_refusal(self):
@@ -776,6 +874,8 @@ class Problem:
             self._probe_steps, self._probe_times, self._probe_data = [], [], []
         if self._integral_every is not None:
             self._integral_steps, self._integral_times, self._integral_data = [], [], []
+        if self._weighted_every is not None:
+            self._weighted_steps, self._weighted_times, self._weighted_data = [], [], []
         if self._extrema_every is not None:
             self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
 
@@ -806,6 +906,7 @@ class Problem:
         self._absorb(entries)
         self._collect_probes(entries)
         self._collect_integrals(entries, before)
+        self._collect_weighted(entries, before)
         self._collect_extrema(entries, before)
         if ran > 0:
             self._mark_device_advanced()
@@ -960,6 +1061,8 @@ class Problem:
                 self._write_probes()
             if self._integral_every is not None:
                 self._write_integrals()
+            if self._weighted_every is not None:
+                self._write_weighted()
             if self._extrema_every is not None:
                 self._write_extrema()
             for name, m in self._gp_models.items():  # problem.py:490-503
@@ -1131,6 +1234,59 @@ def _keep_integrals(input_dict, ymlstring):
         for key, n in (('integrals_sections_x', 'Nx'), ('integrals_sections_y', 'Ny')):
             if opts.get(key) is not None:
                 input_dict['options'][key] = _integral_sections(opts[key], int(grid[n]) if n in grid else 2**31 - 1, key)
+
+
+def _weighted_stride(every, allow_zero=False):
+    low = 0 if allow_zero else 1
+    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
+        raise ValueError(f"weighted integrals: the stride must be an integer >= {low}, got {every!r}")
+    return int(every)
+
+
+def _weight_planes(weights, names, nx, ny):
+    """(planes (K, nx, ny) float64, names) of what set_weighted_integrals is given; ValueError for a shape other than (K, nx, ny) /
+    (nx, ny), K outside 1..8, a weight that is not finite (plane and cell named, the cell in the ghosted index space as the library
+    names it) or names that do not match.  Host only: no library call."""
+    try:
+        a = np.array(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"weighted integrals: weights must be an array of shape (K, {nx}, {ny}) or ({nx}, {ny})") from None
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[1:] != (nx, ny):
+        raise ValueError(f"weighted integrals: weights of shape {np.shape(weights)}; (K, {nx}, {ny}) or ({nx}, {ny}) required "
+                         "(interior cells; ghost cells never contribute)")
+    if not 1 <= len(a) <= _lib.WEIGHTED_MAX_PLANES:
+        raise ValueError(f"weighted integrals: {len(a)} weight planes, 1 to {_lib.WEIGHTED_MAX_PLANES} required")
+    bad = np.argwhere(~np.isfinite(a))
+    if len(bad):
+        k, i, j = (int(v) for v in bad[0])
+        raise ValueError(f"weighted integrals: weight plane {k} is not finite at cell ({i + 1}, {j + 1})")
+    if names is None:
+        names = [f'w{k}' for k in range(len(a))]
+    if isinstance(names, (str, bytes)) or not hasattr(names, '__len__') or len(names) != len(a) or \
+            not all(isinstance(n, str) and n for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"weighted integrals: names must be {len(a)} distinct non-empty strings, got {names!r}")
+    return np.ascontiguousarray(a), [str(n) for n in names]
+
+
+def _keep_weighted(input_dict, ymlstring, base_dir=None):
+    """`options.weighted_integrals: N` (the stride; 0 or absent: off) and `options.weights: [{box: ...}, {mode: ...}, {file: ...}]`
+    are this project's own keys: read from the YAML text and set beside the sanitised ones, like the integrals' -- only when
+    given, so that every other input's dictionaries stay as they are.  Checked here, on the host (gapflow_amd/weights.py:
+    parse_entries); a `file` becomes an absolute path, relative ones taken from the YAML file's directory."""
+    import yaml
+    from . import weights as _weights
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    if opts.get('weighted_integrals') is not None:
+        input_dict['options']['weighted_integrals'] = _weighted_stride(opts['weighted_integrals'], allow_zero=True)
+    if opts.get('weights') is not None:
+        input_dict['options']['weights'] = _weights.parse_entries(opts['weights'], input_dict.get('grid') or None, base_dir)
+    if input_dict['options'].get('weighted_integrals') and not input_dict['options'].get('weights'):
+        raise ValueError("options.weighted_integrals: options.weights must list the weight planes")
 
 
 def _extrema_stride(every, allow_zero=True):

@@ -427,6 +427,14 @@ class SlabProblem:
         """Film integrals are reduced on unsliced problems only."""
         raise NotImplementedError("integrals: not available on a SlabProblem")
 
+    def set_weighted_integrals(self, *args, **kwargs):
+        """Weighted film integrals are reduced on unsliced problems only."""
+        raise NotImplementedError("weighted integrals: not available on a SlabProblem")
+
+    def film_weighted(self, *args, **kwargs):
+        """Weighted film integrals are reduced on unsliced problems only."""
+        raise NotImplementedError("weighted integrals: not available on a SlabProblem")
+
     def set_extrema(self, *args, **kwargs):
         """Field extrema are recorded on unsliced problems only."""
         raise NotImplementedError("extrema: not available on a SlabProblem")
@@ -446,6 +454,8 @@ class SlabProblem:
             raise NotImplementedError("probes: not available on a SlabProblem")      # options.probes: as set_probes
         if (input_dict.get('options') or {}).get('integrals') is not None:
             raise NotImplementedError("integrals: not available on a SlabProblem")   # options.integrals: as set_integrals
+        if (input_dict.get('options') or {}).get('weighted_integrals'):              # (0: off, as on a Problem)
+            raise NotImplementedError("weighted integrals: not available on a SlabProblem")   # options.weighted_integrals: as set_weighted_integrals
         if (input_dict.get('options') or {}).get('extrema'):                         # (0: off, as on a Problem)
             raise NotImplementedError("extrema: not available on a SlabProblem")     # options.extrema: as set_extrema
         import torch
@@ -574,13 +584,14 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None, base_dir=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from
+        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
         _keep_probes(d, text)                       # options.probes: refused below
         _keep_integrals(d, text)                    # options.integrals: refused below
         _keep_extrema(d, text)                      # options.extrema: refused below
+        _keep_weighted(d, text, base_dir)           # options.weighted_integrals: refused below
         _keep_init_from(d, text, base_dir)          # options.init_from: refused below
         return cls(d, device=device, dist=dist)
 

@@ -478,6 +478,52 @@ int gpf_integrals_now(gpf_handle* h, double* out, int64_t count);
  * Probes are put aside in both modes. */
 int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- weighted film integrals (no reference counterpart: per-pad loads, windows and Fourier modes are post-processing there) -- */
+/* The film integrals' question asked per region: for each of K weight planes w_k (1 <= K <= 8) the sums over the interior cells
+ * (1..Nx x 1..Ny) of w_k(ix, iy) f(ix, iy), times dx dy, of the COMMITTED state, for the nine integrands f, in this order:
+ *   p                         the pressure `load` sums (csrc/closures.hpp film_pressure, see above)
+ *   h                         the gap height: the window's volume
+ *   rho_h                     rho h: the mass in the window
+ *   jx_h, jy_h                the mass fluxes times the gap height
+ *   tau_xz_bot, tau_yz_bot    the lower wall's shear stress, as the film integrals evaluate it
+ *   tau_xz_top, tau_yz_top    the upper wall's
+ * A record is [K][9] doubles.  No sign convention is applied and ghost cells never contribute.  A box of ones gives the load and
+ * friction of one pad, cos / sin planes the amplitude of a Fourier mode, any smooth plane a window.  A record is a pure function
+ * of the state and the planes: the summation order is k_film_partial's and k_film_fold's, fixed by (Nx, Ny) alone, and a cell
+ * enters as acc += w * f with the product rounded on its own (no fused multiply-add).  So a weight of exactly 1.0 adds f's own
+ * bits and one of exactly 0.0 a zero, and with a plane of ones p and the four tau_* equal load and the tau_* of gpf_integrals_*
+ * in every bit.  Recording only reads.
+ *   gpf_weighted_set    arms recording after every committed step whose new step count is a multiple of `every` (>= 1), with
+ *                       the K planes `weights`, host layout [K][Nx+2][Ny+2] (ghosted like every field; what the ghost entries
+ *                       hold is ignored: the device planes carry zeros there), and starts with empty records.  The planes are
+ *                       copied.  GPF_ERR_INVALID for every < 1, K outside 1..8, a weight that is not finite (the message names
+ *                       plane and cell; checked on the host before anything is uploaded), surrogate closures, shear thinning or
+ *                       an elastic gap; GPF_ERR_STATE on a slab and while a stage-wise step is open.
+ *   gpf_weighted_clear  disarms and frees the planes and the buffers.
+ *   gpf_weighted_read   the records of the LAST gpf_step call, [record][K][9], and the step count of each in steps_out (either
+ *                       may be NULL); *n_records how many the call left, min(*n_records, capacity_records) are copied.  A batch
+ *                       that stopped on the device leaves the records of the steps that ran; a step that was rolled back as
+ *                       invalid leaves none.  GPF_ERR_STATE unless armed.
+ *   gpf_weighted_now    the same record for the current committed state, by the same two kernels; `count`: doubles `out` holds
+ *                       (>= 9 K).  GPF_ERR_STATE unless armed (the weights live in the handle) and on an invalid run state.
+ * Where they are written: k_wfilm_partial (grid Nx x K: one workgroup per interior row and weight) + k_wfilm_fold (one workgroup
+ * per weight; csrc/weighted_kernels.hip) behind the step's launch, told the step count the step produces if it commits and
+ * writing only if the device's run state shows that count and a valid state.  On grids small enough for k_small_steps the batch
+ * is cut at the recorded steps -- with film integrals armed too, at the union of both series' steps -- which is bitwise the same
+ * run: choose a stride there.  gpf_close_step, gpf_step_timed and the slab calls record nothing.  The planes (K planes of the
+ * handle's layout), the row scratch (K x Nx x 9 doubles) and the record buffer ((log_cap + 1) records) are allocated by
+ * gpf_weighted_set and freed by gpf_weighted_clear / gpf_destroy once the stream is idle.  Pairs of columns are fetched with one
+ * 16-byte load per plane where the buffers, the weight planes among them, are aligned for it and with 8-byte loads otherwise;
+ * GPF_FILM_NARROW (any value, read by gpf_weighted_set) asks for the 8-byte loads regardless -- a test switch; same bits. */
+int gpf_weighted_set(gpf_handle* h, int64_t every, int K, const double* weights /* [K][Nx+2][Ny+2] */);
+int gpf_weighted_clear(gpf_handle* h);
+int gpf_weighted_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_weighted_now(gpf_handle* h, double* out, int64_t count);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording (armed weighted integrals are put aside for the call), 1 recording at the armed stride
+ * (tools/weighted_time.py).  Probes, film integrals and extrema are put aside in both modes. */
+int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* ---- field extrema (no reference counterpart: the reference's users run np.argmax on a downloaded field) ------------------ */
 /* Where the extremes of the COMMITTED state sit, found on the device so that gpf_step keeps advancing whole batches.  A record
  * is seven values, each with its cell (ix, iy) of the ghosted index space, taken over the interior cells 1..Nx x 1..Ny:
