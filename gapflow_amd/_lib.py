@@ -46,6 +46,8 @@ EXTREMA_NAMES = ('p_max', 'p_min', 'rho_max', 'rho_min', 'h_min', 'u_max', 'v_ma
 INTEGRAL_SUMS = ('load', 'load_x', 'load_y', 'p_hx', 'p_hy', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')
 WEIGHTED_MAX_PLANES = 8             # gpf_weighted_set: weight planes per handle
 WEIGHTED_INTEGRANDS = ('p', 'h', 'rho_h', 'jx_h', 'jy_h', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')    # gpf_weighted_*: the record's order
+STATS_FIELDS = ('p', 'rho', 'jx', 'jy')         # gpf_stats_*: field index, bit of the field mask
+STATS_QUANTITIES = ('mean', 'm2', 'min', 'max')     # gpf_stats_read: quantity index
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -161,6 +163,11 @@ SIGNATURES = {
     'gpf_extrema_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_extrema_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32)]),
     'gpf_extrema_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_stats_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    'gpf_stats_clear': (C.c_int, [C.c_void_p]),
+    'gpf_stats_info': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP, _DP]),
+    'gpf_stats_read': (C.c_int, [C.c_void_p, C.c_int, C.c_int, _DP, C.c_size_t]),
+    'gpf_stats_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_ensemble_create': (C.c_int, [_VPP, C.c_int, _VPP]),
     'gpf_ensemble_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]),
     'gpf_ensemble_log': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfScalars), C.c_int64, C.POINTER(C.c_int64)]),

@@ -25,6 +25,7 @@
 #include "checkpoint_kernels.hip"
 #include "integral_kernels.hip"
 #include "weighted_kernels.hip"
+#include "stats_kernels.hip"
 #include "resample_kernels.hip"
 
 using namespace gpf;
@@ -121,6 +122,12 @@ struct gpf_handle {
     // `pending`: an elastic handle's closed step waits for gpf_elastic_update to record it, `pending_base` the count it began at
     struct { long long every = 0; ExtremaArgs a = {}; ExtremaArgs* dev = nullptr; bool narrow = false; bool pending = false; long long pending_base = 0;
              std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } extr;
+    // running field statistics (api_stats.inc): recording stride (0: not armed), the step count records are taken above, the
+    // requested fields (bit 0 p, 1 rho, 2 jx, 3 jy) and the step count at which the window began; the accumulator planes
+    // ([requested fields][mean m2 min max] planes of this handle's Layout) and the device's record of the window, both allocated by
+    // gpf_stats_set (`narrow`: GPF_FILM_NARROW was set then, 8-byte accesses); that record as the last stepping call left it
+    struct { long long every = 0, after = 0, arm_step = 0; int mask = 0; double* acc = nullptr; StatsRecord* rec = nullptr; bool narrow = false;
+             StatsRecord host = {}; } stats;
     double* stage = nullptr;                // contiguous staging for upload/download
     size_t stage_doubles = 0;
     // unfused pipeline scratch (lazy)
@@ -360,7 +367,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -570,6 +577,7 @@ static FieldPtrs field_ptrs(gpf_handle* h) {
 
 static int gp_launch_mean(gpf_handle* h, int which, const double* q, bool with_grad, double* c2_out);
 static int read_state(gpf_handle* h, StepState& s);
+static int stats_restart(gpf_handle* h, long long step);
 
 // thinning on a slab: the beyond rows that belong to field q (the working field of an open step, or the state)
 static const double* beyond_rows(gpf_handle* h, const double* q) {
@@ -756,7 +764,7 @@ extern "C" int gpf_pre_run(gpf_handle* h) {
     h->prev_state_valid = false;
     h->fields_step = -1;
     h->host_step = 0; h->next_step = 0;
-    return GPF_OK;
+    return stats_restart(h, 0);         // the step count starts over: so does the statistics' window
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1022,9 +1030,12 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
     return GPF_OK;
 }
 
+static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base);
+
 #include "api_integrals.inc"
 #include "api_weighted.inc"
 #include "api_extrema.inc"
+#include "api_stats.inc"
 
 extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t* log, int64_t log_capacity,
                         int64_t* n_executed) {
@@ -1041,18 +1052,18 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     GPF_TRY(integrals_begin(h));
     GPF_TRY(weighted_begin(h));
     GPF_TRY(extrema_begin(h));
+    GPF_TRY(stats_begin(h));
     while (done < n) {
         const int64_t batch = std::min<int64_t>(n - done, h->log_cap);
         const long long base = h->host_step;
-        if (small && h->weighted.every) GPF_TRY(weighted_small_batch(h, batch, honor_stop, base));     // cut at the union of both series' steps
-        else if (small && h->integ.every) GPF_TRY(integrals_small_batch(h, batch, honor_stop, base));     // the batch, cut at the recorded steps
-        else if (small) GPF_TRY(enqueue_small_steps(h, (int)batch, honor_stop, base));
+        if (small) GPF_TRY(small_batch_cut(h, batch, honor_stop, base));       // the batch, cut at the union of the armed series' steps
         else for (int64_t i = 0; i < batch; ++i) {
             GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
             GPF_TRY(probes_launch(h, base + i + 1, base));      // no launch without probes
             GPF_TRY(integrals_launch(h, base + i + 1, base));   // nor without integrals, nor off their stride
             GPF_TRY(weighted_launch(h, base + i + 1, base));    // nor without weighted integrals, nor off theirs
             GPF_TRY(extrema_launch(h, base + i + 1, base));     // nor without extrema, nor off theirs
+            GPF_TRY(stats_launch(h, base + i + 1));             // nor without statistics, nor off theirs
         }
         StepState s;
         GPF_TRY(read_state(h, s));
@@ -1061,6 +1072,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
         GPF_TRY(integrals_collect(h, base, ran));
         GPF_TRY(weighted_collect(h, base, ran));
         GPF_TRY(extrema_collect(h, base, ran));
+        GPF_TRY(stats_collect(h, s.step));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);
         if (log && entries > 0) {
             const long long take = std::min<long long>(entries, log_capacity - logged);
@@ -1105,6 +1117,7 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
     GPF_TRY(read_state(h, s));
     h->prev_state_valid = s.step > h->host_step && !s.invalid;
     h->host_step = s.step; h->next_step = s.step;
+    GPF_TRY(stats_restart(h, s.step));      // steps went by unrecorded: armed statistics begin a new window
     return rc;
 }
 

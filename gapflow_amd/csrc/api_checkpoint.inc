@@ -331,7 +331,7 @@ extern "C" int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes
     h->gp_state_mean_valid = false;
     h->fields_step = (B.flags & CKPT_DERIVED) ? s.step : -1;
     h->fields_restored = (B.flags & CKPT_DERIVED) != 0;       // otherwise the derived fields are stale: gpf_update_closures forms them again
-    return GPF_OK;
+    return stats_restart(h, s.step);        // accumulators are not part of a checkpoint: armed statistics begin a new window here
 }
 
 // Diagnostic: one pass of k_ckpt_pack over the three planes of the current q, chunked through the scratch as gpf_checkpoint_save

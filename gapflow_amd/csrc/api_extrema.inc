@@ -182,7 +182,7 @@ extern "C" int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14
 
 // Diagnostic (tools/extrema_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed extrema are put aside
 // for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes and film
-// integrals are put aside in both modes.
+// integrals are put aside in both modes; armed statistics begin a new window after the call.
 extern "C" int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_extrema_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_extrema_time: call gpf_pre_run first");
@@ -230,6 +230,7 @@ extern "C" int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms) 
     int rcol = GPF_OK;
     if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = extrema_collect(h, base, s.step - base);
     h->extr.every = keep_every; h->integ.every = keep_integ; h->probes.n = keep_probes;
+    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
     GPF_TRY(rc);
     if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_extrema_time: ") + hipGetErrorString(e));
     GPF_TRY(rs);

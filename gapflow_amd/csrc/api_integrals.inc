@@ -83,19 +83,6 @@ static int integrals_launch(gpf_handle* h, long long expect, long long base) {
     return integrals_enqueue(h, expect, integrals_count(base, expect - base, every) - 1);
 }
 
-// A batch of the small-grid kernel, cut at the steps to record: k_small_steps itself knows nothing of the integrals, and a
-// batch in pieces is bitwise the batch in one (every piece starts from the state and the run state the piece before left).
-static int integrals_small_batch(gpf_handle* h, long long batch, int honor_stop, long long base) {
-    const long long every = h->integ.every, end = base + batch;
-    for (long long at = base; at < end;) {
-        const long long next = std::min(end, (at / every + 1) * every);
-        GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
-        GPF_TRY(integrals_launch(h, next, base));
-        at = next;
-    }
-    return GPF_OK;
-}
-
 // After the batch's state has been read (the stream is idle): a batch that stopped on the device ran a prefix of its steps,
 // so the records written are those of the multiples of the stride in (base, base + ran]
 static int integrals_collect(gpf_handle* h, long long base, long long ran) {
@@ -181,8 +168,8 @@ extern "C" int gpf_integrals_now(gpf_handle* h, double* out, int64_t count) {
 }
 
 // Diagnostic (tools/integrals_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed integrals are put
-// aside for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes are put
-// aside in both modes.
+// aside for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes, weighted
+// integrals and statistics are put aside in both modes (armed statistics begin a new window after the call).
 extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_integrals_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_integrals_time: call gpf_pre_run first");
@@ -194,9 +181,9 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
     GPF_TRY(enter(h));
     h->integ.host.clear(); h->integ.steps.clear();
     h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->integ.every;
+    const long long keep_every = h->integ.every, keep_weighted = h->weighted.every, keep_stats = h->stats.every;
     const int keep_probes = h->probes.n;
-    h->probes.n = 0;
+    h->probes.n = 0; h->weighted.every = 0; h->stats.every = 0;
     if (mode != 1) h->integ.every = 0;
     int rc = integrals_begin(h);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -206,7 +193,7 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
     float t = 0.f;
     if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
     if (rc == GPF_OK && e == hipSuccess) {
-        if (small) rc = h->integ.every ? integrals_small_batch(h, n, 0, base) : enqueue_small_steps(h, (int)n, 0, base);
+        if (small) rc = small_batch_cut(h, n, 0, base);
         for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
             rc = enqueue_step(h, 0, base, nullptr);
             if (rc == GPF_OK) rc = integrals_launch(h, base + i + 1, base);
@@ -227,7 +214,8 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
     }
     int rcol = GPF_OK;
     if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = integrals_collect(h, base, s.step - base);
-    h->integ.every = keep_every; h->probes.n = keep_probes;
+    h->integ.every = keep_every; h->weighted.every = keep_weighted; h->stats.every = keep_stats; h->probes.n = keep_probes;
+    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
     GPF_TRY(rc);
     if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_integrals_time: ") + hipGetErrorString(e));
     GPF_TRY(rs);

@@ -87,7 +87,7 @@ extern "C" int gpf_resample(gpf_handle* dst, const gpf_handle* src) {
     dst->g1_ready = false;
     dst->prev_state_valid = false;
     dst->fields_step = -1;
-    return GPF_OK;
+    return stats_restart(dst, dst->host_step);      // another state: armed statistics begin a new window
 }
 
 // Diagnostic (tools/resample_time.py): `reps` launches on dst's stream of, `mode` 0, what gpf_resample enqueues, written into the

@@ -58,29 +58,6 @@ static int weighted_launch(gpf_handle* h, long long expect, long long base) {
     return weighted_enqueue(h, expect, integrals_count(base, expect - base, every) - 1);
 }
 
-// The step count at which a small-grid batch standing at `at` is cut next: the next multiple of either armed stride (film
-// integrals, weighted integrals), or `end`
-static long long weighted_next_cut(long long at, long long end, long long every_a, long long every_b) {
-    long long next = end;
-    if (every_a) next = std::min(next, (at / every_a + 1) * every_a);
-    if (every_b) next = std::min(next, (at / every_b + 1) * every_b);
-    return next;
-}
-
-// A batch of the small-grid kernel, cut at the union of the steps the film integrals and the weighted integrals record (see
-// integrals_small_batch: a batch in pieces is bitwise the batch in one)
-static int weighted_small_batch(gpf_handle* h, long long batch, int honor_stop, long long base) {
-    const long long end = base + batch;
-    for (long long at = base; at < end;) {
-        const long long next = weighted_next_cut(at, end, h->integ.every, h->weighted.every);
-        GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
-        GPF_TRY(integrals_launch(h, next, base));
-        GPF_TRY(weighted_launch(h, next, base));
-        at = next;
-    }
-    return GPF_OK;
-}
-
 // After the batch's state has been read (the stream is idle): the records written are those of the multiples of the stride in
 // (base, base + ran]
 static int weighted_collect(gpf_handle* h, long long base, long long ran) {
@@ -194,7 +171,7 @@ extern "C" int gpf_weighted_now(gpf_handle* h, double* out, int64_t count) {
 
 // Diagnostic (tools/weighted_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed weighted integrals are
 // put aside for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes, film
-// integrals and extrema are put aside in both modes.
+// integrals, extrema and statistics are put aside in both modes (armed statistics begin a new window after the call).
 extern "C" int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_weighted_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_weighted_time: call gpf_pre_run first");
@@ -207,9 +184,9 @@ extern "C" int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms)
     h->integ.host.clear(); h->integ.steps.clear();
     h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
     h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->weighted.every, keep_integ = h->integ.every, keep_extr = h->extr.every;
+    const long long keep_every = h->weighted.every, keep_integ = h->integ.every, keep_extr = h->extr.every, keep_stats = h->stats.every;
     const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0; h->extr.every = 0;
+    h->probes.n = 0; h->integ.every = 0; h->extr.every = 0; h->stats.every = 0;
     if (mode != 1) h->weighted.every = 0;
     int rc = weighted_begin(h);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -219,7 +196,7 @@ extern "C" int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms)
     float t = 0.f;
     if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
     if (rc == GPF_OK && e == hipSuccess) {
-        if (small) rc = h->weighted.every ? weighted_small_batch(h, n, 0, base) : enqueue_small_steps(h, (int)n, 0, base);
+        if (small) rc = small_batch_cut(h, n, 0, base);
         for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
             rc = enqueue_step(h, 0, base, nullptr);
             if (rc == GPF_OK) rc = weighted_launch(h, base + i + 1, base);
@@ -240,7 +217,8 @@ extern "C" int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms)
     }
     int rcol = GPF_OK;
     if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = weighted_collect(h, base, s.step - base);
-    h->weighted.every = keep_every; h->integ.every = keep_integ; h->extr.every = keep_extr; h->probes.n = keep_probes;
+    h->weighted.every = keep_every; h->integ.every = keep_integ; h->extr.every = keep_extr; h->stats.every = keep_stats; h->probes.n = keep_probes;
+    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
     GPF_TRY(rc);
     if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_weighted_time: ") + hipGetErrorString(e));
     GPF_TRY(rs);

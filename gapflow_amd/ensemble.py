@@ -44,6 +44,8 @@ def _refusal(p):
     if getattr(p, '_weighted_every', None) is not None:        # (getattr: a Problem made without __init__ has no such attribute)
         return NotImplementedError, ("weighted integrals are armed on it (they cut the batch per member): clear_weighted_integrals(), "
                                      "or run it alone")
+    if getattr(p, '_stats_every', None) is not None:
+        return NotImplementedError, "statistics are armed on it (they cut the batch per member): clear_statistics(), or run it alone"
     if p._probe_cells is not None:
         return NotImplementedError, "probes are armed on it (their records need per-member slots): clear_probes(), or run it alone"
     if p._extrema_every is not None:

@@ -129,6 +129,9 @@ class Problem:
         self._extrema_every = None
         if options.get('extrema'):                  # options.extrema (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_extrema(options['extrema'])
+        self._stats_every = None
+        if options.get('statistics'):               # options.statistics (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
+            self.set_statistics(options['statistics'], options.get('statistics_fields', _lib.STATS_FIELDS), options.get('statistics_after', 0))
 
         if options.get('init_from'):                # options.init_from (from the YAML text, or --init-from): start from another grid's state
             self.init_from(options['init_from'])
@@ -174,6 +177,7 @@ class Problem:
         _keep_integrals(input_dict, ymlstring)
         _keep_extrema(input_dict, ymlstring)
         _keep_weighted(input_dict, ymlstring, base_dir)
+        _keep_statistics(input_dict, ymlstring)
         _keep_init_from(input_dict, ymlstring, base_dir)
         if init_from is not None:
             input_dict['options']['init_from'] = os.path.abspath(os.fspath(init_from))
@@ -846,6 +850,65 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'extrema.npz'), names=np.array(sorted(index, key=index.get)), **s)
 
     # -------------------------------------------------------------------------------------
+    # running field statistics (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def set_statistics(self, every=1, fields=_lib.STATS_FIELDS, after=0):
+        """Keep, on the device, per cell of the ghosted grid the mean, the variance, the smallest and the largest value of `fields`
+        -- any of 'p', 'rho', 'jx', 'jy' -- over the committed steps whose count is a multiple of `every` and greater than
+        `after`, from now on and whichever way the steps are taken (`update()`, `run()`, batches of any length): the peak-pressure
+        map of a start-up, the lowest density every cell reached, the time-mean and fluctuation of an oscillating run, without
+        downloading ``q`` after every step.
+
+        'p' is eos_pressure(rho), the equation of state applied to the COMMITTED density by the device function a probe's p uses
+        -- not the corrector-stage pressure the ``pressure`` member holds; it is not available with a pressure surrogate
+        ('rho', 'jx', 'jy' are).  The statistics are those of the recorded SAMPLE (Welford's update, every operation rounded on
+        its own: restating it on downloaded states gives the same bits); nothing is weighted by dt.  A step that is rolled back
+        as invalid is not recorded.  A record reads and writes four planes per field: on a large grid choose a stride.
+        Starts a new window, as do `_pre_run`, `init_from` and a restored checkpoint (checkpoints do not carry the
+        accumulators: a problem restored from one whose options hold `statistics` is armed again and its window begins at the
+        restart step)."""
+        every, after = _statistics_stride(every, 'statistics', low=1), _statistics_stride(after, 'statistics_after', low=0)
+        fields = _statistics_fields(fields)
+        if 'p' in fields and self._gp_models.get('zz') is not None:
+            raise ValueError("statistics: 'p' is the equation of state's pressure; this problem's pressure is a surrogate")
+        mask = sum(1 << _lib.STATS_FIELDS.index(f) for f in fields)
+        self._sync_to_device()
+        _lib.check(self._lib.gpf_stats_set(self._h, every, after, mask))
+        self._stats_every, self._stats_fields, self._stats_after = every, fields, after
+
+    def clear_statistics(self):
+        """Stop recording and free the accumulators."""
+        if self._stats_every is not None:
+            _lib.check(self._lib.gpf_stats_clear(self._h))
+        self._stats_every = None
+
+    @property
+    def statistics(self):
+        """The window since set_statistics (or `_pre_run`), fetched from the device on access: a dict of `count`, `first_step`,
+        `last_step`, `t_first`, `t_last` and, per field f, `f_mean`, `f_var` (m2 / count, the population form; zeros at
+        count == 1), `f_m2`, `f_min`, `f_max`, each of shape (Nx+2, Ny+2).  None while nothing is armed or recorded."""
+        if self._stats_every is None:
+            return None
+        cnt, first, last = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        t0, t1 = C.c_double(0.), C.c_double(0.)
+        _lib.check(self._lib.gpf_stats_info(self._h, C.byref(cnt), C.byref(first), C.byref(last), C.byref(t0), C.byref(t1)))
+        if cnt.value == 0:
+            return None
+        out = {'count': int(cnt.value), 'first_step': int(first.value), 'last_step': int(last.value), 't_first': t0.value, 't_last': t1.value}
+        for f in self._stats_fields:
+            for k, name in enumerate(_lib.STATS_QUANTITIES):
+                a = np.empty(self._shape)
+                _lib.check(self._lib.gpf_stats_read(self._h, _lib.STATS_FIELDS.index(f), k, _lib.as_dp(a), a.size))
+                out[f'{f}_{name}'] = a
+            out[f'{f}_var'] = out[f'{f}_m2'] / out['count']
+        return out
+
+    def _write_statistics(self):
+        s = self.statistics
+        if s is not None:
+            np.savez(os.path.join(self.outdir, 'statistics.npz'), fields=np.array(self._stats_fields), **s)
+
+    # -------------------------------------------------------------------------------------
     # run loop (problem.py:368-503)
     # -------------------------------------------------------------------------------------
     def _features(self):
@@ -1065,6 +1128,8 @@ class Problem:
                 self._write_weighted()
             if self._extrema_every is not None:
                 self._write_extrema()
+            if self._stats_every is not None:
+                self._write_statistics()
             for name, m in self._gp_models.items():  # problem.py:490-503
                 history_to_csv(os.path.join(self.outdir, f'gp_{name}.csv'), m.history)
                 with open(os.path.join(self.outdir, f'gp_{name}.txt'), 'w') as f:
@@ -1307,6 +1372,38 @@ def _keep_extrema(input_dict, ymlstring):
         return
     if opts.get('extrema') is not None:
         input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
+
+
+def _statistics_stride(v, key, low):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < low:
+        raise ValueError(f"statistics: {key} must be an integer >= {low}, got {v!r}")
+    return int(v)
+
+
+def _statistics_fields(fields):
+    """The requested fields as a tuple in the library's order; ValueError for anything but a non-empty list of distinct names
+    out of p, rho, jx, jy.  Host only: no library call."""
+    if isinstance(fields, (str, bytes, dict)) or not hasattr(fields, '__len__') or len(fields) < 1 or \
+            not all(isinstance(f, str) and f in _lib.STATS_FIELDS for f in fields) or len(set(fields)) != len(fields):
+        raise ValueError(f"statistics: statistics_fields must be a non-empty list of distinct names out of {list(_lib.STATS_FIELDS)}, got {fields!r}")
+    return tuple(f for f in _lib.STATS_FIELDS if f in fields)
+
+
+def _keep_statistics(input_dict, ymlstring):
+    """`options.statistics: N` (the stride; 0 or absent: off), `options.statistics_fields: [p, rho]` and `options.statistics_after: M`
+    are this project's own keys: read from the YAML text and set beside the sanitised ones, like the integrals' -- only when
+    given, so that every other input's dictionaries stay as they are.  Checked here, on the host."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    if opts.get('statistics') is not None:
+        input_dict['options']['statistics'] = _statistics_stride(opts['statistics'], 'statistics', low=0)
+    if opts.get('statistics_fields') is not None:
+        input_dict['options']['statistics_fields'] = list(_statistics_fields(opts['statistics_fields']))
+    if opts.get('statistics_after') is not None:
+        input_dict['options']['statistics_after'] = _statistics_stride(opts['statistics_after'], 'statistics_after', low=0)
 
 
 def _keep_init_from(input_dict, ymlstring, base_dir=None):

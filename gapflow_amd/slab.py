@@ -443,6 +443,15 @@ class SlabProblem:
         """Field extrema are taken on unsliced problems only."""
         raise NotImplementedError("extrema: not available on a SlabProblem")
 
+    def set_statistics(self, *args, **kwargs):
+        """Running field statistics are kept on unsliced problems only."""
+        raise NotImplementedError("statistics: not available on a SlabProblem")
+
+    @property
+    def statistics(self):
+        """Running field statistics are kept on unsliced problems only."""
+        raise NotImplementedError("statistics: not available on a SlabProblem")
+
     def init_from(self, *args, **kwargs):
         """States are resampled onto unsliced problems only."""
         raise NotImplementedError("init_from: not available on a SlabProblem")
@@ -458,6 +467,8 @@ class SlabProblem:
             raise NotImplementedError("weighted integrals: not available on a SlabProblem")   # options.weighted_integrals: as set_weighted_integrals
         if (input_dict.get('options') or {}).get('extrema'):                         # (0: off, as on a Problem)
             raise NotImplementedError("extrema: not available on a SlabProblem")     # options.extrema: as set_extrema
+        if (input_dict.get('options') or {}).get('statistics'):                      # (0: off, as on a Problem)
+            raise NotImplementedError("statistics: not available on a SlabProblem")  # options.statistics: as set_statistics
         import torch
         if dist is None:
             import torch.distributed as dist
@@ -584,7 +595,7 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None, base_dir=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted
+        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted, _keep_statistics
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
@@ -592,6 +603,7 @@ class SlabProblem:
         _keep_integrals(d, text)                    # options.integrals: refused below
         _keep_extrema(d, text)                      # options.extrema: refused below
         _keep_weighted(d, text, base_dir)           # options.weighted_integrals: refused below
+        _keep_statistics(d, text)                   # options.statistics: refused below
         _keep_init_from(d, text, base_dir)          # options.init_from: refused below
         return cls(d, device=device, dist=dist)
 

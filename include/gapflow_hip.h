@@ -568,6 +568,53 @@ int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14]);
  * Probes and film integrals are put aside in both modes. */
 int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- running field statistics (no reference counterpart: its users download q after every step and average on the host) ---- */
+/* WHERE on the film something happened over a run: per cell of the GHOSTED grid (Nx+2) x (Ny+2) -- the shape q has -- and per
+ * requested field, the mean, the sum of squared deviations m2, the smallest and the largest value over the recorded steps, kept
+ * in accumulator planes on the device.  Fields (bits of `field_mask`, index `field`): 0 p = eos_pressure(rho) of the committed
+ * density, by the device function the probes' p uses (bit for bit a probe's p); 1 rho, 2 jx, 3 jy of the committed state.
+ * Quantities (index `quantity`): 0 mean, 1 m2, 2 min, 3 max.  The variance of the recorded sample is m2 / count.
+ * A record is folded in behind every committed step whose new step count is a multiple of `every`, greater than `after`, and
+ * reached after arming.  The n-th record of a window does, per cell, every operation rounded on its own (Welford's update):
+ *     n == 1:  mean = x;  m2 = 0;  min = x;  max = x        (the accumulators are not read)
+ *     n  > 1:  d = x - mean;  mean = mean + d / n;  m2 = m2 + d * (x - mean);  min = x < min ? x : min;  max = x > max ? x : max
+ * with an IEEE division by (double)n and no fused multiply-add.  The planes are therefore a pure function of the sequence of
+ * recorded states -- the same bits whatever the batch size and whichever kernel stepped -- and restating the recurrences on the
+ * host over downloaded states reproduces them in every bit.  These are SAMPLE statistics of the recorded steps: nothing is
+ * weighted by dt; t_first and t_last tell how long the window was.  Recording only reads q.
+ *   gpf_stats_set    arms, or arms again from scratch (count 0).  GPF_ERR_INVALID for every < 1, after < 0, an empty mask or bits
+ *                    beyond 15, and for p on a handle whose pressure comes from a surrogate (rho, jx, jy alone are fine there;
+ *                    surrogate wall shear is fine with all four); GPF_ERR_STATE on a slab and while a stage-wise step is open.
+ *   gpf_stats_clear  disarms and frees the planes.
+ *   gpf_stats_info   the window as the last stepping call left it: records folded in, step count and simulation time of the
+ *                    first and of the last (any pointer may be NULL).  GPF_ERR_STATE unless armed.
+ *   gpf_stats_read   one plane, host layout [Nx+2][Ny+2] like every field; n_doubles must be (Nx+2)(Ny+2).  GPF_ERR_INVALID for a
+ *                    field that is not armed or a quantity outside 0..3; GPF_ERR_STATE unless armed and while count == 0.
+ * Where they are written: k_stats_update (csrc/stats_kernels.hip), one launch behind the step's launch -- gpf_step's
+ * launch-per-step path and gpf_close_step (an elastic handle needs no deferral: the gap is not read) --, told the step count
+ * the step produces if it commits and the record's rank n, and touching nothing unless the device's run state shows that count
+ * and a valid state: a step that did not run or was rolled back leaves the planes and the count as they were.  n is host
+ * arithmetic, n = expect / every - a / every with a = max(step count at arming, after); the kernel also keeps {count,
+ * first_step, t_first, last_step, t_last} on the device, and every stepping call checks that count against its own
+ * (GPF_ERR_STATE if they differ).  On grids small enough for k_small_steps the batch is cut at the union of the steps that film
+ * integrals, weighted integrals and statistics record, which is bitwise the same run: choose a stride there.
+ * gpf_pre_run, gpf_resample and gpf_checkpoint_load begin a new window (count 0) and keep stride, `after` and fields; so do
+ * the diagnostic calls that step without recording (gpf_step_timed, gpf_*_time).  Checkpoints do not carry accumulators.
+ * Four planes of the handle's layout per requested field are allocated by gpf_stats_set and freed by gpf_stats_clear /
+ * gpf_destroy once the stream is idle.  A record reads and writes them once (72 bytes per field and cell): several steps' worth
+ * of traffic for all four fields, so a stride is the sensible setting on large grids.  Column pairs go through one 16-byte
+ * access per plane where the buffers are aligned for it, single cells through 8-byte ones; GPF_FILM_NARROW (any value, read by
+ * gpf_stats_set) asks for 8-byte accesses throughout -- a test switch; same bits. */
+int gpf_stats_set(gpf_handle* h, int64_t every, int64_t after, int field_mask);
+int gpf_stats_clear(gpf_handle* h);
+int gpf_stats_info(gpf_handle* h, int64_t* count, int64_t* first_step, int64_t* last_step, double* t_first, double* t_last);
+int gpf_stats_read(gpf_handle* h, int field, int quantity, double* out, size_t n_doubles);
+/* Diagnostic (tools/stats_time.py): *ms from the first launch to the last on the handle's stream of, mode 0, n steps (1..4096)
+ * enqueued as gpf_step does with nothing recorded (armed statistics are put aside for the call); 1, the same recording at the
+ * armed stride; 2, n launches of an elementwise kernel that moves one record's bytes over the same planes, and no step.
+ * Probes, film integrals, weighted integrals and extrema are put aside in every mode; modes 0 and 2 begin a new window. */
+int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* ---- ensembles (no reference counterpart: the reference runs a parameter study as one process per problem) ---------------- */
 /* Many small problems advanced by ONE launch per kernel instantiation: workgroup m of k_small_ensemble runs, on member m's own
  * buffers, the very body that k_small_steps runs for a handle alone (csrc/small_kernel.hip), so a member's field, run state
