@@ -48,6 +48,9 @@ WEIGHTED_MAX_PLANES = 8             # gpf_weighted_set: weight planes per handle
 WEIGHTED_INTEGRANDS = ('p', 'h', 'rho_h', 'jx_h', 'jy_h', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')    # gpf_weighted_*: the record's order
 STATS_FIELDS = ('p', 'rho', 'jx', 'jy')         # gpf_stats_*: field index, bit of the field mask
 STATS_QUANTITIES = ('mean', 'm2', 'min', 'max')     # gpf_stats_read: quantity index
+REGION_MAX = 8                      # gpf_regions_set: regions per handle
+REGION_FIELDS = ('p', 'rho', 'h', 'jx', 'jy')       # gpf_region.field: GPF_REGION_*
+REGION_INTS = ('cells', 'ix_min', 'ix_max', 'iy_min', 'iy_max')     # gpf_regions_*: the record's int64 part; its doubles: WEIGHTED_INTEGRANDS
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -62,6 +65,11 @@ class GpfConfig(C.Structure):
                 ('adaptive', C.c_int32), ('CFL', C.c_double), ('dt_fixed', C.c_double), ('tol', C.c_double),
                 ('max_it', C.c_int64), ('mc_order', C.c_int32), ('device', C.c_int32),
                 ('thinning', C.c_int32), ('thinning_par', C.c_double * 4)]
+
+
+class GpfRegion(C.Structure):
+    """gpf_region of include/gapflow_hip.h"""
+    _fields_ = [('field', C.c_int32), ('box', C.c_int32 * 4), ('lo', C.c_double), ('hi', C.c_double)]
 
 
 class GpfScalars(C.Structure):
@@ -168,6 +176,11 @@ SIGNATURES = {
     'gpf_stats_info': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP, _DP]),
     'gpf_stats_read': (C.c_int, [C.c_void_p, C.c_int, C.c_int, _DP, C.c_size_t]),
     'gpf_stats_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_regions_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(GpfRegion)]),
+    'gpf_regions_clear': (C.c_int, [C.c_void_p]),
+    'gpf_regions_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_regions_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int64), C.c_int64]),
+    'gpf_regions_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_ensemble_create': (C.c_int, [_VPP, C.c_int, _VPP]),
     'gpf_ensemble_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]),
     'gpf_ensemble_log': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfScalars), C.c_int64, C.POINTER(C.c_int64)]),

@@ -26,6 +26,7 @@
 #include "integral_kernels.hip"
 #include "weighted_kernels.hip"
 #include "stats_kernels.hip"
+#include "region_kernels.hip"
 #include "resample_kernels.hip"
 
 using namespace gpf;
@@ -116,6 +117,12 @@ struct gpf_handle {
     // set then, 8-byte loads); the records of the last stepping call and their step counts on the host
     struct { long long every = 0; int K = 0; double* w = nullptr; double* part = nullptr; double* rec = nullptr; bool narrow = false;
              std::vector<double> host; std::vector<long long> steps; } weighted;
+    // region series (api_regions.inc): recording stride (0: not armed) and number of regions K; the region list on the device
+    // ([K] Region), the row scratch ([K][Nx][9] doubles, [K][Nx][3] int32) and the device records of the batch in flight
+    // ([log_cap + 1][K][9] doubles, [log_cap + 1][K][5] int64), all allocated by gpf_regions_set (`narrow`: GPF_FILM_NARROW was set
+    // then, 8-byte loads); the records of the last stepping call and their step counts on the host
+    struct { long long every = 0; int K = 0; Region* defs = nullptr; double* part = nullptr; int* ipart = nullptr; double* rec = nullptr;
+             long long* irec = nullptr; bool narrow = false; std::vector<double> host; std::vector<long long> ihost, steps; } regions;
     // field extrema (api_extrema.inc): recording stride (0: not armed); the device records of the batch in flight ([log_cap + 1][7]
     // doubles, [log_cap + 1][14] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was set then);
     // `dev`: the ExtremaArgs of these buffers in device memory, for k_small_steps; the records of the last stepping call on the host.
@@ -367,7 +374,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -1035,6 +1042,7 @@ static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long 
 #include "api_integrals.inc"
 #include "api_weighted.inc"
 #include "api_extrema.inc"
+#include "api_regions.inc"
 #include "api_stats.inc"
 
 extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t* log, int64_t log_capacity,
@@ -1051,6 +1059,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     GPF_TRY(probes_begin(h));
     GPF_TRY(integrals_begin(h));
     GPF_TRY(weighted_begin(h));
+    GPF_TRY(regions_begin(h));
     GPF_TRY(extrema_begin(h));
     GPF_TRY(stats_begin(h));
     while (done < n) {
@@ -1062,6 +1071,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
             GPF_TRY(probes_launch(h, base + i + 1, base));      // no launch without probes
             GPF_TRY(integrals_launch(h, base + i + 1, base));   // nor without integrals, nor off their stride
             GPF_TRY(weighted_launch(h, base + i + 1, base));    // nor without weighted integrals, nor off theirs
+            GPF_TRY(regions_launch(h, base + i + 1, base));     // nor without regions, nor off theirs
             GPF_TRY(extrema_launch(h, base + i + 1, base));     // nor without extrema, nor off theirs
             GPF_TRY(stats_launch(h, base + i + 1));             // nor without statistics, nor off theirs
         }
@@ -1071,6 +1081,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
         GPF_TRY(probes_collect(h, ran));
         GPF_TRY(integrals_collect(h, base, ran));
         GPF_TRY(weighted_collect(h, base, ran));
+        GPF_TRY(regions_collect(h, base, ran));
         GPF_TRY(extrema_collect(h, base, ran));
         GPF_TRY(stats_collect(h, s.step));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);

@@ -1,0 +1,237 @@
+// Part of api.hip (included there, not compiled on its own): region series -- the weighted film integrals' nine sums over zones
+// the state itself defines (a field inside [lo, hi), inside a box), with the zone's exact cell count and bounding box -- reduced on
+// the device behind the committed steps whose count is a multiple of the armed stride, and handed out once per call.
+// Kernels: region_kernels.hip; the predicate: regions.hpp.
+
+// The cases the reduction does not cover: the weighted integrals' (weighted_refusal), with their error classes
+static int regions_refusal(const gpf_handle* h, const std::string& who) {
+    if (h->E.halo[0] || h->E.halo[1]) return fail(GPF_ERR_STATE, who + ": this handle is a slab; regions are not available on slabs");
+    if (h->step_open) return fail(GPF_ERR_STATE, who + ": a stage-wise step is open; close it first");
+    if (h->gp[0].set || h->gp[1].set || h->gp[2].set)
+        return fail(GPF_ERR_INVALID, who + ": surrogate closures: the regions evaluate the analytic pressure and wall stress, which this handle replaces");
+    if (h->cfg.thinning != GPF_THINNING_NONE) return fail(GPF_ERR_INVALID, who + ": shear thinning needs grad p (not supported)");
+    if (h->el.on || h->els.on) return fail(GPF_ERR_INVALID, who + ": an elastic handle steps stage-wise and deforms its gap between steps (not supported)");
+    return GPF_OK;
+}
+
+static size_t regions_nsum(const gpf_handle* h) { return (size_t)h->regions.K * WFILM_NQ; }
+static size_t regions_nint(const gpf_handle* h) { return (size_t)h->regions.K * REGION_NI; }
+
+// 16-byte pair loads of k_region_partial: film_wide_ok's conditions on the planes it reads (GPF_FILM_NARROW, read by
+// gpf_regions_set, asks for the 8-byte loads regardless)
+static bool regions_wide_ok(const gpf_handle* h) {
+    const Layout& L = h->L;
+    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    return ((L.off + 1) & 1) == 0 && (L.pitch & 1) == 0 && (L.plane & 1) == 0 && a16(h->q[0]) && a16(h->q[1]) && a16(h->topo) &&
+           (!h->Ls || a16(h->Ls)) && !h->regions.narrow;
+}
+
+// A stepping call begins: its records replace those of the call before
+static int regions_begin(gpf_handle* h) {
+    if (!h->regions.every) return GPF_OK;
+    GPF_TRY(regions_refusal(h, "gpf_step with regions armed"));
+    h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
+    return GPF_OK;
+}
+
+// The two launches on the handle's stream: the record of the committed state into `slot` if the step count is `expect`
+static int regions_enqueue(gpf_handle* h, long long expect, long long slot) {
+    RegionArgs f;
+    f.qa = h->q[0]; f.qb = h->q[1]; f.topo = h->topo; f.Ls = h->Ls; f.regions = h->regions.defs; f.st = h->st;
+    f.part = h->regions.part; f.ipart = h->regions.ipart; f.rec = h->regions.rec; f.irec = h->regions.irec;
+    f.L = h->L; f.dx = h->cfg.dx; f.dy = h->cfg.dy;
+    f.K = h->regions.K; f.wide = regions_wide_ok(h) ? 1 : 0;
+    f.slot = slot; f.cap = h->log_cap;
+    const dim3 grid(h->L.Nx, f.K);
+    EOS_DISPATCH(h->cfg.eos, {
+        if (h->Ls) hipLaunchKernelGGL((k_region_partial<EOS_, true>), grid, dim3(256), 0, h->stream, f, h->P, expect);
+        else hipLaunchKernelGGL((k_region_partial<EOS_, false>), grid, dim3(256), 0, h->stream, f, h->P, expect);
+    });
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_region_fold, dim3(f.K), dim3(256), 0, h->stream, f, expect);
+    HIP_TRY(hipGetLastError());
+    return GPF_OK;
+}
+
+// Behind the launches of one step of a batch that began at step count `base`: record it if it takes the count to a multiple
+// of the stride.  No launch otherwise, and none without regions armed.
+static int regions_launch(gpf_handle* h, long long expect, long long base) {
+    const long long every = h->regions.every;
+    if (!every || expect % every != 0) return GPF_OK;
+    return regions_enqueue(h, expect, integrals_count(base, expect - base, every) - 1);
+}
+
+// After the batch's state has been read (the stream is idle): the records written are those of the multiples of the stride in
+// (base, base + ran]
+static int regions_collect(gpf_handle* h, long long base, long long ran) {
+    const long long every = h->regions.every;
+    if (!every) return GPF_OK;
+    const long long cnt = integrals_count(base, ran, every);
+    if (cnt <= 0) return GPF_OK;
+    const size_t ns = regions_nsum(h), ni = regions_nint(h), at = h->regions.host.size(), iat = h->regions.ihost.size();
+    h->regions.host.resize(at + (size_t)cnt * ns);
+    h->regions.ihost.resize(iat + (size_t)cnt * ni);
+    HIP_TRY(hipMemcpy(h->regions.host.data() + at, h->regions.rec, (size_t)cnt * ns * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h->regions.ihost.data() + iat, h->regions.irec, (size_t)cnt * ni * sizeof(long long), hipMemcpyDeviceToHost));
+    for (long long k = 1; k <= cnt; ++k) h->regions.steps.push_back((base / every + k) * every);
+    return GPF_OK;
+}
+
+static int regions_release(gpf_handle* h) {
+    HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
+    for (void** p : {(void**)&h->regions.defs, (void**)&h->regions.part, (void**)&h->regions.ipart, (void**)&h->regions.rec, (void**)&h->regions.irec}) {
+        if (*p) HIP_TRY(hipFree(*p));
+        *p = nullptr;
+    }
+    h->regions.every = 0; h->regions.K = 0;
+    h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
+    return GPF_OK;
+}
+
+extern "C" int gpf_regions_set(gpf_handle* h, int64_t every, int K, const gpf_region* regions) {
+    static const char* const field_names = "0 (p), 1 (rho), 2 (h), 3 (jx), 4 (jy)";
+    if (!h) return fail(GPF_ERR_INVALID, "null handle");
+    GPF_TRY(regions_refusal(h, "gpf_regions_set"));
+    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_regions_set: every >= 1 required (gpf_regions_clear disarms), got " + std::to_string(every));
+    if (K < 1 || K > REGION_MAX_K)
+        return fail(GPF_ERR_INVALID, "gpf_regions_set: 1 to " + std::to_string(REGION_MAX_K) + " regions required, got " + std::to_string(K));
+    if (!regions) return fail(GPF_ERR_INVALID, "gpf_regions_set: null regions");
+    const Layout& L = h->L;
+    Region defs[REGION_MAX_K];
+    for (int k = 0; k < K; ++k) {
+        const gpf_region& g = regions[k];
+        Region& r = defs[k];
+        r.lo = g.lo; r.hi = g.hi; r.field = g.field; r.pad_ = 0;
+        const bool whole = !g.box[0] && !g.box[1] && !g.box[2] && !g.box[3];       // all zeros: the whole interior
+        r.ix0 = whole ? 1 : g.box[0]; r.ix1 = whole ? L.Nx : g.box[1]; r.iy0 = whole ? 1 : g.box[2]; r.iy1 = whole ? L.Ny : g.box[3];
+        const std::string who = "gpf_regions_set: region " + std::to_string(k);
+        switch (region_check(r.field, r.lo, r.hi, r.ix0, r.ix1, r.iy0, r.iy1, L.Nx, L.Ny)) {
+            case 0: break;
+            case 1: return fail(GPF_ERR_INVALID, who + ": unknown field " + std::to_string(g.field) + "; one of " + field_names + " required");
+            case 2: return fail(GPF_ERR_INVALID, who + ": lo < hi required, neither a NaN (lo inclusive, hi exclusive; -inf / +inf leave a side open), got lo = " +
+                                                 std::to_string(g.lo) + ", hi = " + std::to_string(g.hi));
+            default: return fail(GPF_ERR_INVALID, who + ": box (" + std::to_string(g.box[0]) + ", " + std::to_string(g.box[1]) + ", " + std::to_string(g.box[2]) + ", " +
+                                                  std::to_string(g.box[3]) + ") must be ix0 <= ix1 within 1.." + std::to_string(L.Nx) + " and iy0 <= iy1 within 1.." +
+                                                  std::to_string(L.Ny) + " (inclusive interior indices; all zeros: the whole interior)");
+        }
+    }
+    GPF_TRY(enter(h, true));
+    GPF_TRY(regions_release(h));
+    auto undo = [&](int code) { (void)regions_release(h); return code; };
+#define HIP_TRY_R(expr)                                                                                 \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) return undo(fail(GPF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)));      \
+    } while (0)
+    const size_t slots = (size_t)(h->log_cap + 1) * K;
+    HIP_TRY_R(hipMalloc(&h->regions.defs, (size_t)K * sizeof(Region)));
+    HIP_TRY_R(hipMalloc(&h->regions.part, (size_t)K * L.Nx * WFILM_NQ * sizeof(double)));
+    HIP_TRY_R(hipMalloc(&h->regions.ipart, (size_t)K * L.Nx * REGION_NROW * sizeof(int)));
+    HIP_TRY_R(hipMalloc(&h->regions.rec, slots * WFILM_NQ * sizeof(double)));
+    HIP_TRY_R(hipMalloc(&h->regions.irec, slots * REGION_NI * sizeof(long long)));
+    HIP_TRY_R(hipMemcpyAsync(h->regions.defs, defs, (size_t)K * sizeof(Region), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY_R(hipStreamSynchronize(h->stream));         // `defs` is on this call's stack
+#undef HIP_TRY_R
+    h->regions.narrow = std::getenv("GPF_FILM_NARROW") != nullptr;
+    h->regions.K = K;
+    h->regions.every = every;
+    return GPF_OK;
+}
+
+extern "C" int gpf_regions_clear(gpf_handle* h) {
+    if (!h) return fail(GPF_ERR_INVALID, "null handle");
+    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_regions_clear: a stage-wise step is open; close it first");
+    GPF_TRY(enter(h, true));
+    return regions_release(h);
+}
+
+extern "C" int gpf_regions_read(gpf_handle* h, double* sums, int64_t* ints, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
+    if (!h) return fail(GPF_ERR_INVALID, "null handle");
+    if (!h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_read: no regions are armed (gpf_regions_set)");
+    const size_t ns = regions_nsum(h), ni = regions_nint(h);
+    const int64_t have = (int64_t)h->regions.steps.size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
+    if (n_records) *n_records = have;
+    if (sums && take > 0) std::memcpy(sums, h->regions.host.data(), (size_t)take * ns * sizeof(double));
+    if (ints && take > 0) std::memcpy(ints, h->regions.ihost.data(), (size_t)take * ni * sizeof(int64_t));
+    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = h->regions.steps[(size_t)k];
+    return GPF_OK;
+}
+
+extern "C" int gpf_regions_now(gpf_handle* h, double* sums, int64_t* ints, int64_t count) {
+    if (!h || !sums || !ints) return fail(GPF_ERR_INVALID, "gpf_regions_now: null argument");
+    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_regions_now: upload q and topography first");
+    GPF_TRY(regions_refusal(h, "gpf_regions_now"));
+    if (!h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_now: no regions are armed (gpf_regions_set holds the region list)");
+    GPF_TRY(enter(h, true));
+    if (count < h->regions.K) return fail(GPF_ERR_INVALID, "gpf_regions_now: room for " + std::to_string(h->regions.K) + " regions required, " + std::to_string(count) + " given");
+    StepState s;
+    GPF_TRY(read_state(h, s));
+    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_regions_now: the run state is flagged invalid (the last step was rolled back)");
+    const size_t ns = regions_nsum(h), ni = regions_nint(h);
+    GPF_TRY(regions_enqueue(h, s.step, h->log_cap));            // the slot behind a batch's
+    HIP_TRY(hipMemcpyAsync(sums, h->regions.rec + (size_t)h->log_cap * ns, ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(ints, h->regions.irec + (size_t)h->log_cap * ni, ni * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return GPF_OK;
+}
+
+// Diagnostic (tools/regions_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed regions are put aside for
+// the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes, film integrals, weighted
+// integrals, extrema and statistics are put aside in both modes (armed statistics begin a new window after the call).
+extern "C" int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms) {
+    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_regions_time: null argument");
+    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_regions_time: call gpf_pre_run first");
+    GPF_TRY(regions_refusal(h, "gpf_regions_time"));
+    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
+        return fail(GPF_ERR_INVALID, "gpf_regions_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
+    if (mode == 1 && !h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_time: mode 1 needs armed regions (gpf_regions_set)");
+    const bool small = small_grid_eligible(h);
+    GPF_TRY(enter(h));
+    h->integ.host.clear(); h->integ.steps.clear();
+    h->weighted.host.clear(); h->weighted.steps.clear();
+    h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
+    h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
+    const long long keep_every = h->regions.every, keep_integ = h->integ.every, keep_weighted = h->weighted.every, keep_extr = h->extr.every,
+                    keep_stats = h->stats.every;
+    const int keep_probes = h->probes.n;
+    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->extr.every = 0; h->stats.every = 0;
+    if (mode != 1) h->regions.every = 0;
+    int rc = regions_begin(h);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    const long long base = h->host_step;
+    float t = 0.f;
+    if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
+    if (rc == GPF_OK && e == hipSuccess) {
+        if (small) rc = small_batch_cut(h, n, 0, base);
+        for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
+            rc = enqueue_step(h, 0, base, nullptr);
+            if (rc == GPF_OK) rc = regions_launch(h, base + i + 1, base);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    // steps may have been queued whatever went wrong after them: the host's counters follow the device's
+    StepState s;
+    const int rs = read_state(h, s);
+    if (rs == GPF_OK) {
+        h->prev_state_valid = s.step > base && !s.invalid;
+        h->host_step = s.step; h->next_step = s.step;
+    }
+    int rcol = GPF_OK;
+    if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = regions_collect(h, base, s.step - base);
+    h->regions.every = keep_every; h->integ.every = keep_integ; h->weighted.every = keep_weighted; h->extr.every = keep_extr; h->stats.every = keep_stats;
+    h->probes.n = keep_probes;
+    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
+    GPF_TRY(rc);
+    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_regions_time: ") + hipGetErrorString(e));
+    GPF_TRY(rs);
+    GPF_TRY(rcol);
+    *ms = t;
+    return GPF_OK;
+}

@@ -35,6 +35,8 @@ FilmIntegrals = namedtuple('FilmIntegrals', ('step', 'time') + _lib.INTEGRAL_SUM
 FilmIntegrals.__doc__ = """Time series of Problem.integrals: step, time and the nine area integrals (nrecords,), flow_x (nrecords, len(sections_x)), flow_y (nrecords, len(sections_y)), the sections' interior rows / columns."""
 WeightedIntegrals = namedtuple('WeightedIntegrals', ('step', 'time', 'names') + _lib.WEIGHTED_INTEGRANDS)
 WeightedIntegrals.__doc__ = """Time series of Problem.weighted_integrals: step, time (nrecords,), names (the K weight planes'), and per integrand an array (nrecords, K)."""
+RegionSeries = namedtuple('RegionSeries', ('step', 'time', 'names') + _lib.WEIGHTED_INTEGRANDS + ('cells', 'area', 'bbox'))
+RegionSeries.__doc__ = """Time series of Problem.regions: step, time (nrecords,), names (the K regions'), per integrand an array (nrecords, K), cells (nrecords, K) int64, area = cells dx dy, bbox (nrecords, K, 4) = (ix_min, ix_max, iy_min, iy_max), -1 for an empty region."""
 FieldExtrema = namedtuple('FieldExtrema', ('step', 'time') + _lib.EXTREMA_NAMES + ('cells', 'index'))
 FieldExtrema.__doc__ = """Time series of Problem.extrema: step, time and the seven values (nrecords,), cells (nrecords, 7, 2) -- (ix, iy) of each value in the ghosted index space --, index: name -> position along the cells' second axis."""
 
@@ -126,6 +128,11 @@ class Problem:
                 raise ValueError("options.weighted_integrals: options.weights must list the weight planes")
             planes, names = _weights.from_entries(grid, options['weights'])
             self.set_weighted_integrals(planes, options['weighted_integrals'], names)
+        self._regions_every = None
+        if options.get('regions'):                  # options.regions / options.region_list (from the YAML text, or a checkpoint's dictionaries); 0: off
+            if not options.get('region_list'):
+                raise ValueError("options.regions: options.region_list must list the regions")
+            self.set_regions(options['region_list'], options['regions'])
         self._extrema_every = None
         if options.get('extrema'):                  # options.extrema (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_extrema(options['extrema'])
@@ -178,6 +185,7 @@ class Problem:
         _keep_extrema(input_dict, ymlstring)
         _keep_weighted(input_dict, ymlstring, base_dir)
         _keep_statistics(input_dict, ymlstring)
+        _keep_regions(input_dict, ymlstring)
         _keep_init_from(input_dict, ymlstring, base_dir)
         if init_from is not None:
             input_dict['options']['init_from'] = os.path.abspath(os.fspath(init_from))
@@ -474,7 +482,7 @@ class Problem:
 
         Allowed at any time.  Before the first step the run simply begins from the new state; after steps the run starts
         over at step 0 (`_pre_run`), as it would from a state assigned to ``q``, and the probes', integrals', weighted
-        integrals' and extrema series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
+        integrals', regions' and extrema series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
         which is destroyed before the call returns.
         ValueError: the domains differ (Lx or Ly by more than 1e-12 relative), or a direction is periodic on one side only.
         NotImplementedError: surrogate closures here, or a SlabProblem as the source."""
@@ -765,6 +773,112 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'weighted.npz'), **s)
 
     # -------------------------------------------------------------------------------------
+    # region series (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _regions_refusal(self):
+        if self.has_gp_model or self._gp_models:
+            raise NotImplementedError("regions: surrogate (GP) closures replace the pressure and wall stress the regions evaluate")
+        if self._cfg.thinning:
+            raise NotImplementedError("regions: shear thinning needs grad p, which the reduction does not model")
+        if self._elastic or self.topo.elastic:
+            raise NotImplementedError("regions: an elastic gap steps stage-wise and deforms between steps (not supported)")
+
+    def set_regions(self, regions, every=1):
+        """Record, for each of K <= 8 regions, what the part of the film in a given state carries after every step whose count
+        is a multiple of `every`, on the device, whichever way the steps are taken (`update()`, `run()`, batches of any length).
+
+        regions: a list of dicts {field, above=-inf, below=+inf, box=None, name=None}.  field: 'p' (the equation of state's
+        pressure of the committed density: a probe's p, the extrema's), 'rho', 'h', 'jx' or 'jy'.  An interior cell belongs iff
+        above <= f < below for its value f -- `above` is inclusive, `below` exclusive, a NaN never belongs -- and it lies in
+        box = (ix0, ix1, iy0, iy1), inclusive 1-based interior indices (None: the whole interior).  The zone follows the state
+        of each step: {field: 'rho', below: rho_cav} is the cavitated zone, {field: 'h', below: c} the thin film.  names
+        default to r0, r1, ...
+        Per record and region: the nine sums of ``weighted_integrals`` (p, h, rho_h, jx_h, jy_h, tau_xz_bot, tau_yz_bot,
+        tau_xz_top, tau_yz_top) over the region's cells times dx dy -- on a finite state bit for bit what
+        `set_weighted_integrals` gives for the 0 / 1 plane of the same predicate --, `cells`, the exact number of member
+        cells, `area` = cells dx dy, and `bbox` = (ix_min, ix_max, iy_min, iy_max) over them: (-1, -1, -1, -1) for an empty
+        region, whose sums are +0.0.  A zone that wraps a periodic seam reports the full extent along that axis.
+        On grids small enough for the one-workgroup kernel the batch is cut at every recorded step: choose a stride there.
+        A step that is rolled back as invalid leaves no record.  Starts a new series (see ``regions``).  Checkpoints do not
+        carry the series: a problem restored from one whose options hold `regions` and `region_list` has them armed again and
+        its series begins at the restart step; regions set from code do not survive a restore.  Not available with surrogate
+        closures, shear thinning or an elastic gap."""
+        self._regions_refusal()
+        every = _regions_stride(every)
+        entries = _region_entries(regions, self.grid['Nx'], self.grid['Ny'])
+        arr = (_lib.GpfRegion * len(entries))()
+        for r, e in zip(arr, entries):
+            r.field, r.lo, r.hi = _lib.REGION_FIELDS.index(e['field']), e['above'], e['below']
+            r.box[:] = e['box'] if e['box'] is not None else (1, self.grid['Nx'], 1, self.grid['Ny'])
+        _lib.check(self._lib.gpf_regions_set(self._h, every, len(entries), arr))
+        self._regions_every, self._regions_names = every, [e['name'] for e in entries]
+        self._regions_steps, self._regions_times, self._regions_sums, self._regions_ints = [], [], [], []
+
+    def clear_regions(self):
+        """Stop recording, drop the series and free the device buffers."""
+        if self._regions_every is not None:
+            _lib.check(self._lib.gpf_regions_clear(self._h))
+        self._regions_every = None
+
+    def _region_record(self, steps, times, sums, ints):
+        nq = len(_lib.WEIGHTED_INTEGRANDS)
+        cells = ints[:, :, 0].copy()
+        return RegionSeries(steps, times, tuple(self._regions_names), *[sums[:, :, k] for k in range(nq)], cells,
+                            cells * (self.grid['dx'] * self.grid['dy']), ints[:, :, 1:].copy())
+
+    @property
+    def regions(self):
+        """RegionSeries(step, time, names, p, h, rho_h, ..., cells, area, bbox) of every recorded step since set_regions (or
+        _pre_run), across `update()` and `run()` calls: one array (nrecords, K) per integrand, cells and area (nrecords, K),
+        bbox (nrecords, K, 4); None when none are armed."""
+        if self._regions_every is None:
+            return None
+        K = len(self._regions_names)
+        sums = np.concatenate(self._regions_sums) if self._regions_sums else np.empty((0, K, len(_lib.WEIGHTED_INTEGRANDS)))
+        ints = np.concatenate(self._regions_ints) if self._regions_ints else np.empty((0, K, len(_lib.REGION_INTS)), dtype=np.int64)
+        return self._region_record(np.array(self._regions_steps, dtype=np.int64), np.array(self._regions_times, dtype=np.float64), sums, ints)
+
+    def film_regions(self):
+        """The same record for the current state, as {name: array(K)} for the nine integrands, `cells` and `area`, and
+        `bbox` (K, 4): bit for bit what a step committing this state would have recorded.  Needs armed regions.  Reads only."""
+        self._regions_refusal()
+        if self._regions_every is None:
+            raise RuntimeError("film_regions: no regions are set (set_regions)")
+        self._sync_to_device()
+        K = len(self._regions_names)
+        sums = np.empty((1, K, len(_lib.WEIGHTED_INTEGRANDS)))
+        ints = np.zeros((1, K, len(_lib.REGION_INTS)), dtype=np.int64)
+        _lib.check(self._lib.gpf_regions_now(self._h, _lib.as_dp(sums), ints.ctypes.data_as(C.POINTER(C.c_int64)), K))
+        rec = self._region_record(None, None, sums, ints)._asdict()
+        return {k: v[0].copy() for k, v in rec.items() if k not in ('step', 'time', 'names')}
+
+    def _collect_regions(self, entries, before):
+        """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
+        if self._regions_every is None or not entries:
+            return
+        n = _integral_records(before, len(entries), self._regions_every)
+        K = len(self._regions_names)
+        sums = np.empty((n, K, len(_lib.WEIGHTED_INTEGRANDS)))
+        ints = np.zeros((n, K, len(_lib.REGION_INTS)), dtype=np.int64)
+        steps = np.zeros(n, dtype=np.int64)
+        have = C.c_int64(0)
+        i64p = C.POINTER(C.c_int64)
+        _lib.check(self._lib.gpf_regions_read(self._h, _lib.as_dp(sums), ints.ctypes.data_as(i64p), n, steps.ctypes.data_as(i64p), C.byref(have)))
+        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._regions_every == 0]
+        if have.value != n or steps.tolist() != want:
+            raise _lib.GapflowHipError(f"regions: {have.value} records of steps {steps.tolist()} for the committed steps "
+                                       f"{before + 1}..{before + len(entries)} at stride {self._regions_every}")
+        self._regions_steps.extend(want)
+        self._regions_times.extend(entries[s - before - 1].simtime for s in want)
+        self._regions_sums.append(sums)
+        self._regions_ints.append(ints)
+
+    def _write_regions(self):
+        s = self.regions._asdict()
+        s['names'] = np.array(s['names'])
+        np.savez(os.path.join(self.outdir, 'regions.npz'), **s)
+
+    # -------------------------------------------------------------------------------------
     # field extrema (no reference counterpart; DESIGN.md 3.3g)
     # -------------------------------------------------------------------------------------
     def _extrema_refusal(self):
@@ -939,6 +1053,8 @@ class Problem:
             self._integral_steps, self._integral_times, self._integral_data = [], [], []
         if self._weighted_every is not None:
             self._weighted_steps, self._weighted_times, self._weighted_data = [], [], []
+        if self._regions_every is not None:
+            self._regions_steps, self._regions_times, self._regions_sums, self._regions_ints = [], [], [], []
         if self._extrema_every is not None:
             self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
 
@@ -970,6 +1086,7 @@ class Problem:
         self._collect_probes(entries)
         self._collect_integrals(entries, before)
         self._collect_weighted(entries, before)
+        self._collect_regions(entries, before)
         self._collect_extrema(entries, before)
         if ran > 0:
             self._mark_device_advanced()
@@ -1126,6 +1243,8 @@ class Problem:
                 self._write_integrals()
             if self._weighted_every is not None:
                 self._write_weighted()
+            if self._regions_every is not None:
+                self._write_regions()
             if self._extrema_every is not None:
                 self._write_extrema()
             if self._stats_every is not None:
@@ -1352,6 +1471,75 @@ def _keep_weighted(input_dict, ymlstring, base_dir=None):
         input_dict['options']['weights'] = _weights.parse_entries(opts['weights'], input_dict.get('grid') or None, base_dir)
     if input_dict['options'].get('weighted_integrals') and not input_dict['options'].get('weights'):
         raise ValueError("options.weighted_integrals: options.weights must list the weight planes")
+
+
+def _regions_stride(every, allow_zero=False):
+    low = 0 if allow_zero else 1
+    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
+        raise ValueError(f"regions: the stride must be an integer >= {low}, got {every!r}")
+    return int(every)
+
+
+def _region_entries(regions, nx=None, ny=None, where='regions'):
+    """What set_regions / options.region_list is given, checked and completed: a list of 1 to 8 dicts {field, above, below, box,
+    name} with above / below as floats (-inf / +inf when absent), box a list of four ints or None (the whole interior) and the
+    names distinct (r0, r1, ... when absent).  ValueError, naming the entry, for an unknown key or field, bounds that are no
+    numbers, a NaN among them or above >= below, a box that is not four integers ix0 <= ix1, iy0 <= iy1 inside the interior
+    (checked against nx, ny where given), a name that is no non-empty string or is used twice.  Host only: no library call."""
+    if isinstance(regions, (str, bytes, dict)) or not hasattr(regions, '__len__') or not 1 <= len(regions) <= _lib.REGION_MAX:
+        raise ValueError(f"{where}: a list of 1 to {_lib.REGION_MAX} regions {{field, above, below, box, name}} is required, got {regions!r}")
+    out = []
+    for k, e in enumerate(regions):
+        def bad(msg):
+            return ValueError(f"{where}: entry {k}: {msg}, got {e!r}")
+        if not isinstance(e, dict) or set(e) - {'field', 'above', 'below', 'box', 'name'}:
+            raise bad("a dict with the keys field, above, below, box, name is required")
+        if e.get('field') not in _lib.REGION_FIELDS:
+            raise bad(f"field must be one of {list(_lib.REGION_FIELDS)}")
+        bounds = []
+        for key, default in (('above', -np.inf), ('below', np.inf)):
+            v = e.get(key)
+            v = default if v is None else v
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or np.isnan(v):
+                raise bad(f"{key} must be a number (inf allowed, NaN not)")
+            bounds.append(float(v))
+        if not bounds[0] < bounds[1]:
+            raise bad("above < below is required (above is inclusive, below exclusive)")
+        box = e.get('box')
+        if box is not None:
+            if isinstance(box, (str, bytes, dict)) or not hasattr(box, '__len__') or len(box) != 4 or \
+                    any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in box):
+                raise bad("box must be four integers [ix0, ix1, iy0, iy1]")
+            box = [int(v) for v in box]
+            if not (1 <= box[0] <= box[1] and 1 <= box[2] <= box[3]) or (nx is not None and box[1] > nx) or (ny is not None and box[3] > ny):
+                raise bad("box must be ix0 <= ix1 and iy0 <= iy1 inside the interior (inclusive, 1-based)")
+        name = e.get('name')
+        name = f'r{k}' if name is None else name
+        if not isinstance(name, str) or not name:
+            raise bad("name must be a non-empty string")
+        if name in [o['name'] for o in out]:
+            raise bad(f"the name {name!r} is used twice")
+        out.append({'field': e['field'], 'above': bounds[0], 'below': bounds[1], 'box': box, 'name': name})
+    return out
+
+
+def _keep_regions(input_dict, ymlstring):
+    """`options.regions: N` (the stride; 0 or absent: off) and `options.region_list: [{field: rho, below: 850.0, name: cavitated},
+    ...]` are this project's own keys: read from the YAML text and set beside the sanitised ones, like the weighted integrals'
+    -- only when given, so that every other input's dictionaries stay as they are.  Checked here, on the host (_region_entries)."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    grid = input_dict.get('grid') or {}
+    if opts.get('regions') is not None:
+        input_dict['options']['regions'] = _regions_stride(opts['regions'], allow_zero=True)
+    if opts.get('region_list') is not None:
+        input_dict['options']['region_list'] = _region_entries(opts['region_list'], int(grid['Nx']) if 'Nx' in grid else None,
+                                                               int(grid['Ny']) if 'Ny' in grid else None, where='options.region_list')
+    if input_dict['options'].get('regions') and not input_dict['options'].get('region_list'):
+        raise ValueError("options.regions: options.region_list must list the regions")
 
 
 def _extrema_stride(every, allow_zero=True):

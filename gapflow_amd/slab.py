@@ -435,6 +435,14 @@ class SlabProblem:
         """Weighted film integrals are reduced on unsliced problems only."""
         raise NotImplementedError("weighted integrals: not available on a SlabProblem")
 
+    def set_regions(self, *args, **kwargs):
+        """Regions are reduced on unsliced problems only."""
+        raise NotImplementedError("regions: not available on a SlabProblem")
+
+    def film_regions(self, *args, **kwargs):
+        """Regions are reduced on unsliced problems only."""
+        raise NotImplementedError("regions: not available on a SlabProblem")
+
     def set_extrema(self, *args, **kwargs):
         """Field extrema are recorded on unsliced problems only."""
         raise NotImplementedError("extrema: not available on a SlabProblem")
@@ -465,6 +473,8 @@ class SlabProblem:
             raise NotImplementedError("integrals: not available on a SlabProblem")   # options.integrals: as set_integrals
         if (input_dict.get('options') or {}).get('weighted_integrals'):              # (0: off, as on a Problem)
             raise NotImplementedError("weighted integrals: not available on a SlabProblem")   # options.weighted_integrals: as set_weighted_integrals
+        if (input_dict.get('options') or {}).get('regions'):                         # (0: off, as on a Problem)
+            raise NotImplementedError("regions: not available on a SlabProblem")     # options.regions: as set_regions
         if (input_dict.get('options') or {}).get('extrema'):                         # (0: off, as on a Problem)
             raise NotImplementedError("extrema: not available on a SlabProblem")     # options.extrema: as set_extrema
         if (input_dict.get('options') or {}).get('statistics'):                      # (0: off, as on a Problem)
@@ -595,7 +605,7 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None, base_dir=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted, _keep_statistics
+        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted, _keep_statistics, _keep_regions
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
@@ -604,6 +614,7 @@ class SlabProblem:
         _keep_extrema(d, text)                      # options.extrema: refused below
         _keep_weighted(d, text, base_dir)           # options.weighted_integrals: refused below
         _keep_statistics(d, text)                   # options.statistics: refused below
+        _keep_regions(d, text)                      # options.regions: refused below
         _keep_init_from(d, text, base_dir)          # options.init_from: refused below
         return cls(d, device=device, dist=dist)
 

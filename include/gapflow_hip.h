@@ -615,6 +615,69 @@ int gpf_stats_read(gpf_handle* h, int field, int quantity, double* out, size_t n
  * Probes, film integrals, weighted integrals and extrema are put aside in every mode; modes 0 and 2 begin a new window. */
 int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- region series (no reference counterpart: its users download q and mask it on the host) -------------------------------- */
+/* How much of the film is in a given state, and what that part carries: the cavitated zone (rho below a threshold), the zone that
+ * bears the load, the thin-film zone (h below a clearance), the area above a pressure limit.  A region is {field, lo, hi, box}:
+ * interior cell (ix, iy) of the COMMITTED state belongs to it iff lo <= f && f < hi for its value f of `field` and
+ * box[0] <= ix <= box[1], box[2] <= iy <= box[3] (inclusive, 1-based interior indices: the ghosted index space's 1..Nx, 1..Ny; a
+ * box of four zeros is the whole interior).  field: GPF_REGION_P, the equation of state's pressure of the committed density
+ * (csrc/closures.hpp eos_pressure: the p of the probes, the extrema and the statistics, so that p >= p_max of the extrema record
+ * holds that record's cell); GPF_REGION_RHO, _JX, _JY, the planes of the state; GPF_REGION_H, plane 0 of the gap as the device
+ * holds it.  lo and hi are doubles with lo < hi; -inf / +inf leave a side open; the comparisons are IEEE's, so -0.0 equals 0.0 and
+ * a NaN value never belongs.  Ghost cells never belong.  Up to 8 regions per handle.
+ * Per region a record holds
+ *   nine doubles   the weighted film integrals' sums, in their order (p h rho_h jx_h jy_h tau_xz_bot tau_yz_bot tau_xz_top
+ *                  tau_yz_top), over the region's cells, times dx dy.  The summation order is k_wfilm_partial's and
+ *                  k_wfilm_fold's and a cell enters as acc += w * f with w exactly 1.0 (member) or 0.0 and the product rounded
+ *                  on its own: on a finite state the nine values equal, in every bit, what gpf_weighted_* returns for the 0 / 1
+ *                  plane of the same predicate on the same state.  +0.0 for an empty region.
+ *   five int64     cells, the exact number of member cells (area = cells dx dy), and their bounding box ix_min, ix_max, iy_min,
+ *                  iy_max; (-1, -1, -1, -1) behind cells = 0.  The box is taken over the indices as they are: a zone that
+ *                  wraps a periodic seam reports the full extent along that axis (1 .. Nx or 1 .. Ny).
+ * so a record is [K][9] doubles and [K][5] int64.  It is a pure function of the state and the region list: integer folds, a
+ * fixed summation tree, no floating-point atomics, no arrival order.  Recording only reads.
+ *   gpf_regions_set     arms recording after every committed step whose new step count is a multiple of `every` (>= 1) with the
+ *                       K regions (copied), and starts with empty records.  GPF_ERR_INVALID for every < 1, K outside 1..8, an
+ *                       unknown field, lo >= hi or a NaN bound, a box outside the interior or empty (the message names the
+ *                       region), surrogate closures, shear thinning or an elastic gap; GPF_ERR_STATE on a slab and while a
+ *                       stage-wise step is open.
+ *   gpf_regions_clear   disarms and frees the buffers.
+ *   gpf_regions_read    the records of the LAST gpf_step call, sums [record][K][9] and ints [record][K][5], and the step count
+ *                       of each in steps_out (any may be NULL); *n_records how many the call left, min(*n_records,
+ *                       capacity_records) are copied.  A batch that stopped on the device leaves the records of the steps that
+ *                       ran; a step that was rolled back as invalid leaves none.  GPF_ERR_STATE unless armed.
+ *   gpf_regions_now     the same record for the current committed state, by the same two kernels; `count`: the regions `sums`
+ *                       ([count][9]) and `ints` ([count][5]) have room for (>= K).  GPF_ERR_STATE unless armed and on an
+ *                       invalid run state.
+ * Where they are written: k_region_partial (grid Nx x K: one workgroup per interior row and region) + k_region_fold (one
+ * workgroup per region; csrc/region_kernels.hip, the predicate in csrc/regions.hpp) behind the step's launch, told the step count
+ * the step produces if it commits and writing only if the device's run state shows that count and a valid state.  On grids small
+ * enough for k_small_steps the batch is cut at the recorded steps -- at the union of the steps of every armed series that cuts
+ * it -- which is bitwise the same run: choose a stride there.  gpf_close_step, gpf_step_timed and the slab calls record nothing.
+ * The buffers (row scratch K x Nx x (9 doubles + 3 int32), (log_cap + 1) records) are allocated by gpf_regions_set and freed by
+ * gpf_regions_clear / gpf_destroy once the stream is idle.  There is no plane per region: nothing is uploaded or stored per
+ * cell.  Pairs of columns are fetched with one 16-byte load per plane where the buffers are aligned for it and with 8-byte loads
+ * otherwise; GPF_FILM_NARROW (any value, read by gpf_regions_set) asks for the 8-byte loads regardless -- a test switch; same
+ * bits. */
+#define GPF_REGION_P   0
+#define GPF_REGION_RHO 1
+#define GPF_REGION_H   2
+#define GPF_REGION_JX  3
+#define GPF_REGION_JY  4
+typedef struct {
+    int32_t field;             /* GPF_REGION_*                                                      */
+    int32_t box[4];            /* ix0, ix1, iy0, iy1, inclusive; all zeros: the whole interior      */
+    double  lo, hi;            /* lo <= f < hi                                                      */
+} gpf_region;
+int gpf_regions_set(gpf_handle* h, int64_t every, int K, const gpf_region* regions /* [K] */);
+int gpf_regions_clear(gpf_handle* h);
+int gpf_regions_read(gpf_handle* h, double* sums, int64_t* ints, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_regions_now(gpf_handle* h, double* sums, int64_t* ints, int64_t count);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording (armed regions are put aside for the call), 1 recording at the armed stride (tools/regions_time.py).
+ * Probes, film integrals, weighted integrals, extrema and statistics are put aside in both modes. */
+int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* ---- ensembles (no reference counterpart: the reference runs a parameter study as one process per problem) ---------------- */
 /* Many small problems advanced by ONE launch per kernel instantiation: workgroup m of k_small_ensemble runs, on member m's own
  * buffers, the very body that k_small_steps runs for a handle alone (csrc/small_kernel.hip), so a member's field, run state
