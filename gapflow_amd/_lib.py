@@ -42,6 +42,11 @@ INTEGRAL_MAX_SECTIONS = 8           # gpf_integrals_set: flow cross-sections per
 # compares them with gpf_ensemble_limits, so a library built with other values does not load
 SMALL_GRID_LDS_BYTES, SMALL_GRID_DOUBLES_PER_CELL = 150 * 1024, 16      # what one workgroup's LDS takes (csrc/api.hip)
 LOG_CAPACITY = 4096                 # per-step records a handle's device log holds: the longest batch
+# the ensembles' workspace tier (csrc/mid_layout.hpp; load() compares them with gpf_ensemble_limits2): the most cells of a member,
+# ghost cells included, and the doubles its workspace in device memory holds per cell
+MID_GRID_MAX_CELLS, MID_GRID_DOUBLES_PER_CELL = 16384, 19
+ENSEMBLE_FORCE_WORKSPACE = 1        # gpf_ensemble_create2: flags
+ENSEMBLE_TIERS = ('lds', 'workspace')       # gpf_ensemble_member_info: tier
 EXTREMA_NAMES = ('p_max', 'p_min', 'rho_max', 'rho_min', 'h_min', 'u_max', 'v_max')     # gpf_extrema_*: the record's order
 INTEGRAL_SUMS = ('load', 'load_x', 'load_y', 'p_hx', 'p_hy', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')
 WEIGHTED_MAX_PLANES = 8             # gpf_weighted_set: weight planes per handle
@@ -186,6 +191,9 @@ SIGNATURES = {
     'gpf_ensemble_log': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfScalars), C.c_int64, C.POINTER(C.c_int64)]),
     'gpf_ensemble_destroy': (C.c_int, [C.c_void_p]),
     'gpf_ensemble_limits': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    'gpf_ensemble_create2': (C.c_int, [_VPP, C.c_int, C.c_int, _VPP]),
+    'gpf_ensemble_limits2': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    'gpf_ensemble_member_info': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     'gpf_resample': (C.c_int, [C.c_void_p, C.c_void_p]),
     'gpf_resample_time': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _DP]),
 }
@@ -281,6 +289,12 @@ def load():
         if (lds.value, per_cell.value, steps.value) != (SMALL_GRID_LDS_BYTES, SMALL_GRID_DOUBLES_PER_CELL, LOG_CAPACITY):
             raise GapflowHipError(f"{LIB_PATH} was built with other limits (LDS bytes, doubles per cell, log capacity) = "
                                   f"{(lds.value, per_cell.value, steps.value)} than gapflow_amd/_lib.py states")
+        mid_cells, mid_per_cell = C.c_int64(MID_GRID_MAX_CELLS), C.c_int32(MID_GRID_DOUBLES_PER_CELL)
+        if 'gpf_ensemble_limits2' in SIGNATURES:
+            lib.gpf_ensemble_limits2(C.byref(mid_cells), C.byref(mid_per_cell))
+        if (mid_cells.value, mid_per_cell.value) != (MID_GRID_MAX_CELLS, MID_GRID_DOUBLES_PER_CELL):
+            raise GapflowHipError(f"{LIB_PATH} was built with other workspace-tier limits (cells, doubles per cell) = "
+                                  f"{(mid_cells.value, mid_per_cell.value)} than gapflow_amd/_lib.py states")
         _lib = lib
     return _lib
 

@@ -21,6 +21,7 @@
 #include "probe_kernels.hip"
 #include "extrema_kernels.hip"
 #include "small_kernel.hip"
+#include "mid_kernel.hip"
 #include "profile_kernels.hip"
 #include "checkpoint_kernels.hip"
 #include "integral_kernels.hip"
@@ -999,16 +1000,25 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
 #include "api_probes.inc"
 
 // Problems that fit one workgroup's LDS advance whole batches of steps in one launch (small_kernel.hip).
-// Why not (null: it does); gpf_ensemble_create names the reason.
-static const char* small_grid_refusal(gpf_handle* h) {
+// Why not (null: it does); gpf_ensemble_create names the reason.  one_workgroup_refusal: every reason but the grid's size, which
+// are also the reasons against the ensembles' workspace tier (mid_kernel.hip).
+static const char* one_workgroup_refusal(gpf_handle* h) {
     static const bool off = getenv("GPF_SMALL_GRID") && atoi(getenv("GPF_SMALL_GRID")) == 0;
-    const long long nc = (long long)(h->L.Nx + 2) * (h->L.Ny + 2);
     if (off) return "GPF_SMALL_GRID=0 turns the one-workgroup kernel off";
-    if (nc * SMALL_DOUBLES_PER_CELL * 8 > SMALL_GRID_LDS_BYTES) return "its grid does not fit one workgroup's LDS (16 doubles per cell, ghost cells included, in 150 KB)";
     if (h->cfg.thinning != GPF_THINNING_NONE) return "shear thinning steps stage-wise (it needs grad p)";
     if (h->E.halo[0] || h->E.halo[1]) return "it is a slab (halo rows)";
     if (h->gp[0].set || h->gp[1].set || h->gp[2].set) return "a surrogate model is set (it steps stage-wise)";
     if (h->el.on) return "its gap is elastic (it steps stage-wise)";
+    return nullptr;
+}
+
+static bool small_grid_fits_lds(const gpf_handle* h) {
+    return mid_cells(h->L.Nx, h->L.Ny) * SMALL_DOUBLES_PER_CELL * 8 <= SMALL_GRID_LDS_BYTES;
+}
+
+static const char* small_grid_refusal(gpf_handle* h) {
+    if (const char* why = one_workgroup_refusal(h)) return why;
+    if (!small_grid_fits_lds(h)) return "its grid does not fit one workgroup's LDS (16 doubles per cell, ghost cells included, in 150 KB)";
     return nullptr;
 }
 

@@ -1,5 +1,7 @@
-// Ensembles (gpf_ensemble_*): many small problems advanced by one launch per kernel instantiation, one workgroup per member
-// (k_small_ensemble, small_kernel.hip).  Part of api.hip's translation unit.
+// Ensembles (gpf_ensemble_*): many small problems advanced by one launch per kernel instantiation, one workgroup per member.
+// Two tiers: a member that fits one workgroup's LDS runs k_small_ensemble (small_kernel.hip); one of up to MID_GRID_MAX_CELLS
+// cells runs k_mid_ensemble (mid_kernel.hip) on a workspace in device memory that the ensemble owns.  Part of api.hip's
+// translation unit.
 //
 // A member is a handle of its own, borrowed: everything a solo gpf_step of the same count would leave in it -- buffers, run
 // state, log, host_step / next_step, prev_state_valid, g1_ready -- is left in it here, so that it can go on alone.
@@ -11,16 +13,32 @@ struct gpf_ensemble {
     // call launches -- the arguments adjacent, so that ONE copy per call fills them; the states come back with one
     char* dev = nullptr;
     char* host = nullptr;
+    // ... and behind them double*[k], the launched members' workspaces (null for a member of the LDS tier)
     std::vector<int> slot_member;           // launch slot -> member, of the last call
     std::vector<long long> entries;         // per member: log records the last call left (0: not launched)
+    int flags = 0;                          // of gpf_ensemble_create2
+    std::vector<int> tier;                  // per member: GPF_ENSEMBLE_TIER_LDS / _WORKSPACE, fixed at create
+    std::vector<long long> ws_off;          // per member of the workspace tier: where its workspace starts in `ws`, in bytes
+    char* ws = nullptr;                     // one device allocation for all workspaces (mid_layout.hpp)
     size_t args_off() const { return members.size() * sizeof(StepState); }
-    size_t bytes() const { return args_off() + members.size() * (sizeof(SmallArgs) + sizeof(Phys)); }
+    size_t bytes() const { return args_off() + members.size() * (sizeof(SmallArgs) + sizeof(Phys) + sizeof(double*)); }
 };
-static_assert(sizeof(StepState) % 8 == 0 && sizeof(SmallArgs) % 8 == 0 && sizeof(Phys) % 8 == 0, "the three arrays share one allocation");
+static_assert(sizeof(StepState) % 8 == 0 && sizeof(SmallArgs) % 8 == 0 && sizeof(Phys) % 8 == 0, "the four arrays share one allocation");
+
+// The tier a member gets in an ensemble made with `flags`; -1, and the reason in *why, for one that no tier takes.
+static int ensemble_member_tier(gpf_handle* h, int flags, std::string* why) {
+    if (const char* no = one_workgroup_refusal(h)) { *why = no; return -1; }
+    if (!(flags & GPF_ENSEMBLE_FORCE_WORKSPACE) && small_grid_fits_lds(h)) return GPF_ENSEMBLE_TIER_LDS;
+    if (mid_cells(h->L.Nx, h->L.Ny) <= MID_GRID_MAX_CELLS) return GPF_ENSEMBLE_TIER_WORKSPACE;
+    *why = "its grid does not fit one workgroup's LDS (16 doubles per cell, ghost cells included, in 150 KB) nor the workspace tier (at most " +
+           std::to_string(MID_GRID_MAX_CELLS) + " cells, ghost cells included)";
+    return -1;
+}
 
 // Why a member cannot be stepped in an ensemble right now; empty: it can.
-static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first) {
-    if (const char* why = small_grid_refusal(h)) return why;
+static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first, int flags) {
+    std::string why;
+    if (ensemble_member_tier(h, flags, &why) < 0) return why;
     if (h->cfg.device != first->cfg.device) return "it lives on device " + std::to_string(h->cfg.device) + ", member 0 on device " +
                                                    std::to_string(first->cfg.device) + " (one launch needs one device)";
     if (h->stream != first->stream) return "its stream differs from member 0's (one launch needs one stream)";
@@ -34,7 +52,12 @@ static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first) {
 }
 
 extern "C" int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemble** out) {
+    return gpf_ensemble_create2(members, m, 0, out);
+}
+
+extern "C" int gpf_ensemble_create2(gpf_handle* const* members, int m, int flags, gpf_ensemble** out) {
     if (!members || !out) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: null argument");
+    if (flags & ~GPF_ENSEMBLE_FORCE_WORKSPACE) return fail(GPF_ERR_INVALID, "gpf_ensemble_create2: flags = " + std::to_string(flags) + ", 0 or GPF_ENSEMBLE_FORCE_WORKSPACE required");
     if (m < 1) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: an ensemble needs at least one member (m = " + std::to_string(m) + ")");
     for (int i = 0; i < m; ++i) {
         if (!members[i]) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: member " + std::to_string(i) + " is a null handle");
@@ -42,7 +65,7 @@ extern "C" int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemb
             if (members[j] == members[i])
                 return fail(GPF_ERR_INVALID, "gpf_ensemble_create: member " + std::to_string(i) + " is the same handle as member " +
                                              std::to_string(j) + " (two workgroups would write the same buffers)");
-        const std::string why = ensemble_member_refusal(members[i], members[0]);
+        const std::string why = ensemble_member_refusal(members[i], members[0], flags);
         if (!why.empty()) return fail(GPF_ERR_INVALID, "gpf_ensemble_create: member " + std::to_string(i) + ": " + why);
     }
     HIP_TRY(hipSetDevice(members[0]->cfg.device));
@@ -50,8 +73,20 @@ extern "C" int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemb
     e->members.assign(members, members + m);
     e->device = members[0]->cfg.device;
     e->entries.assign(m, 0);
+    e->flags = flags;
+    e->tier.assign(m, GPF_ENSEMBLE_TIER_LDS);
+    e->ws_off.assign(m, 0);
+    long long ws_bytes = 0;                 // every workspace a multiple of 256 bytes: each starts 256-byte aligned
+    for (int i = 0; i < m; ++i) {
+        std::string unused;
+        e->tier[i] = ensemble_member_tier(members[i], flags, &unused);
+        if (e->tier[i] != GPF_ENSEMBLE_TIER_WORKSPACE) continue;
+        e->ws_off[i] = ws_bytes;
+        ws_bytes += mid_workspace_bytes(mid_cells(members[i]->L.Nx, members[i]->L.Ny));
+    }
     for (gpf_handle* h : e->members) ensemble_members_add(h);
     hipError_t err = hipMalloc(&e->dev, e->bytes());
+    if (err == hipSuccess && ws_bytes > 0) err = hipMalloc(&e->ws, (size_t)ws_bytes);
     if (err == hipSuccess) err = hipHostMalloc((void**)&e->host, e->bytes(), hipHostMallocDefault);
     if (err != hipSuccess) {
         gpf_ensemble_destroy(e);
@@ -66,6 +101,7 @@ extern "C" int gpf_ensemble_destroy(gpf_ensemble* e) {
     for (gpf_handle* h : e->members) ensemble_members_drop(h, false);
     hipSetDevice(e->device);
     if (e->dev) hipFree(e->dev);
+    if (e->ws) hipFree(e->ws);
     if (e->host) hipHostFree(e->host);
     delete e;
     return GPF_OK;
@@ -81,14 +117,15 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         if (n[i] < 0 || n[i] > h->log_cap)
             return fail(GPF_ERR_INVALID, who + "n = " + std::to_string((long long)n[i]) + ", 0 .. " + std::to_string(h->log_cap) + " (the log's capacity) required");
         if (n[i] == 0) continue;
-        const std::string why = ensemble_member_refusal(h, e->members[0]);
+        const std::string why = ensemble_member_refusal(h, e->members[0], e->flags);
         if (!why.empty()) return fail(GPF_ERR_INVALID, who + why);
         if (!h->pre_run_done) return fail(GPF_ERR_STATE, who + "call gpf_pre_run first (Problem._pre_run, problem.py:412)");
     }
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t stream = e->members[0]->stream;
-    // launch slots: the members to advance, grouped by kernel instantiation (EOS, slip-length field or not), member order within
-    auto key = [&](int i) { return e->members[i]->cfg.eos * 2 + (e->members[i]->Ls ? 1 : 0); };
+    // launch slots: the members to advance, grouped by kernel (tier) and instantiation (EOS, slip-length field or not), member
+    // order within
+    auto key = [&](int i) { return (e->tier[i] * 64 + e->members[i]->cfg.eos) * 2 + (e->members[i]->Ls ? 1 : 0); };
     std::vector<int>& slots = e->slot_member;
     slots.clear();
     for (int i = 0; i < m; ++i) {
@@ -97,13 +134,15 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
     }
     std::stable_sort(slots.begin(), slots.end(), [&](int a, int b) { return key(a) < key(b); });
     const int nslots = (int)slots.size();
-    const size_t args_bytes = (size_t)nslots * sizeof(SmallArgs), phys_bytes = (size_t)nslots * sizeof(Phys);
+    const size_t args_bytes = (size_t)nslots * sizeof(SmallArgs), phys_bytes = (size_t)nslots * sizeof(Phys), ws_bytes = (size_t)nslots * sizeof(double*);
     StepState* hs = (StepState*)e->host;
     SmallArgs* ha = (SmallArgs*)(e->host + e->args_off());
     Phys* hp = (Phys*)(e->host + e->args_off() + args_bytes);
+    double** hw = (double**)(e->host + e->args_off() + args_bytes + phys_bytes);
     StepState* ds = (StepState*)e->dev;
     SmallArgs* da = (SmallArgs*)(e->dev + e->args_off());
     Phys* dp = (Phys*)(e->dev + e->args_off() + args_bytes);
+    double** dw = (double**)(e->dev + e->args_off() + args_bytes + phys_bytes);
     for (int s = 0; s < nslots; ++s) {
         gpf_handle* h = e->members[slots[s]];
         GPF_TRY(enter(h));
@@ -112,6 +151,7 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         a.log = h->log; a.log_base = h->host_step; a.log_cap = h->log_cap; a.L = h->L; a.E = h->E;
         a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop; a.probe = nullptr; a.extrema = nullptr;
         hp[s] = h->P;
+        hw[s] = e->tier[slots[s]] == GPF_ENSEMBLE_TIER_WORKSPACE ? (double*)(e->ws + e->ws_off[slots[s]]) : nullptr;
     }
     // Once a group has been launched its members have moved on the device, whatever happens next on the host: an error from
     // then on does not return at once.  No further group is launched, the states of the launched slots are read back and
@@ -121,7 +161,7 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         if (err != hipSuccess && rc == GPF_OK) rc = fail(GPF_ERR_HIP, std::string("gpf_ensemble_step: ") + what + ": " + hipGetErrorString(err));
         return err == hipSuccess;
     };
-    if (nslots > 0 && hip_ok(hipMemcpyAsync(da, ha, args_bytes + phys_bytes, hipMemcpyHostToDevice, stream), "argument copy")) {   // one copy per call
+    if (nslots > 0 && hip_ok(hipMemcpyAsync(da, ha, args_bytes + phys_bytes + ws_bytes, hipMemcpyHostToDevice, stream), "argument copy")) {   // one copy per call
         for (int s0 = 0; s0 < nslots && rc == GPF_OK;) {
             int s1 = s0;
             size_t lds = 0;
@@ -132,15 +172,22 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
             }
             gpf_handle* h0 = e->members[slots[s0]];
             const dim3 grid(s1 - s0);
-            EOS_DISPATCH(h0->cfg.eos, {
-                if (h0->Ls) {
-                    if (hip_ok(hipFuncSetAttribute((const void*)k_small_ensemble<EOS_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "LDS attribute"))
-                        hipLaunchKernelGGL((k_small_ensemble<EOS_, true>), grid, dim3(512), lds, stream, da + s0, dp + s0, ds + s0);
-                } else {
-                    if (hip_ok(hipFuncSetAttribute((const void*)k_small_ensemble<EOS_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "LDS attribute"))
-                        hipLaunchKernelGGL((k_small_ensemble<EOS_, false>), grid, dim3(512), lds, stream, da + s0, dp + s0, ds + s0);
-                }
-            });
+            if (e->tier[slots[s0]] == GPF_ENSEMBLE_TIER_WORKSPACE) {
+                EOS_DISPATCH(h0->cfg.eos, {
+                    if (h0->Ls) hipLaunchKernelGGL((k_mid_ensemble<EOS_, true>), grid, dim3(MID_THREADS), 0, stream, da + s0, dp + s0, dw + s0, ds + s0);
+                    else hipLaunchKernelGGL((k_mid_ensemble<EOS_, false>), grid, dim3(MID_THREADS), 0, stream, da + s0, dp + s0, dw + s0, ds + s0);
+                });
+            } else {
+                EOS_DISPATCH(h0->cfg.eos, {
+                    if (h0->Ls) {
+                        if (hip_ok(hipFuncSetAttribute((const void*)k_small_ensemble<EOS_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "LDS attribute"))
+                            hipLaunchKernelGGL((k_small_ensemble<EOS_, true>), grid, dim3(512), lds, stream, da + s0, dp + s0, ds + s0);
+                    } else {
+                        if (hip_ok(hipFuncSetAttribute((const void*)k_small_ensemble<EOS_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "LDS attribute"))
+                            hipLaunchKernelGGL((k_small_ensemble<EOS_, false>), grid, dim3(512), lds, stream, da + s0, dp + s0, ds + s0);
+                    }
+                });
+            }
             if (rc == GPF_OK && hip_ok(hipGetLastError(), "launch")) launched = s1;
             s0 = s1;
         }
@@ -170,6 +217,22 @@ extern "C" int gpf_ensemble_limits(int64_t* lds_bytes, int32_t* doubles_per_cell
     if (lds_bytes) *lds_bytes = SMALL_GRID_LDS_BYTES;
     if (doubles_per_cell) *doubles_per_cell = SMALL_DOUBLES_PER_CELL;
     if (max_steps) *max_steps = LOG_CAPACITY;
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_limits2(int64_t* mid_max_cells, int32_t* mid_doubles_per_cell) {
+    if (mid_max_cells) *mid_max_cells = MID_GRID_MAX_CELLS;
+    if (mid_doubles_per_cell) *mid_doubles_per_cell = MID_DOUBLES_PER_CELL;
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_member_info(gpf_ensemble* e, int member, int32_t* tier, int64_t* workspace_bytes) {
+    if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_member_info: null argument");
+    if (member < 0 || member >= (int)e->members.size())
+        return fail(GPF_ERR_INVALID, "gpf_ensemble_member_info: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    const bool ws = e->tier[member] == GPF_ENSEMBLE_TIER_WORKSPACE;
+    if (tier) *tier = e->tier[member];
+    if (workspace_bytes) *workspace_bytes = ws ? mid_workspace_bytes(mid_cells(e->members[member]->L.Nx, e->members[member]->L.Ny)) : 0;
     return GPF_OK;
 }
 

@@ -9,8 +9,14 @@ process per problem).  DESIGN.md 3.2c.
 An ensemble HOLDS its `Problem` objects, it does not copy them: after `run()` or `step()` every member is, bit for bit, what
 the same call on it alone would have made it (`q`, `step`, `simtime`, `dt`, `residual`, `residual_buffer`, `history`, derived
 fields, output files), and it can go on alone.  Members may differ in everything -- grid, gap, edges, equation of state,
-step size, stop condition -- but each must fit the one-workgroup kernel (csrc/small_kernel.hip); what does not is refused
-when the ensemble is built, by name and with the reason.
+step size, stop condition -- but each must fit one of the two one-workgroup kernels; what does not is refused when the
+ensemble is built, by name and with the reason.
+
+Two tiers (`Ensemble.tiers`, `member_tier`): 'lds' -- up to 1200 cells, ghost cells included, the planes in LDS
+(csrc/small_kernel.hip); such a member is bit for bit its solo run.  'workspace' -- up to 16384 cells (126 x 126 interior
+cells: the reference's 2-D set-ups), the planes in a workspace in device memory that the ensemble owns (csrc/mid_kernel.hip);
+such a member is bit for bit the same whoever else is in the ensemble and however its steps are split into calls, and agrees
+with its solo run (another kernel) to rounding.
 """
 import ctypes as C
 import itertools
@@ -24,6 +30,21 @@ from . import _lib
 from .problem import Problem, _in_main_thread, _termination_signals
 
 
+def member_tier(nx, ny):
+    """The tier an Nx x Ny member gets: 'lds', 'workspace', or None for a grid no tier takes.  Host only."""
+    cells = (int(nx) + 2) * (int(ny) + 2)
+    if cells * _lib.SMALL_GRID_DOUBLES_PER_CELL * 8 <= _lib.SMALL_GRID_LDS_BYTES:
+        return 'lds'
+    return 'workspace' if cells <= _lib.MID_GRID_MAX_CELLS else None
+
+
+def workspace_bytes(nx, ny):
+    """Bytes of device memory an Nx x Ny member's workspace takes: MID_GRID_DOUBLES_PER_CELL doubles per cell, ghost cells
+    included, rounded up to 256 (csrc/mid_layout.hpp).  Host only."""
+    raw = (int(nx) + 2) * (int(ny) + 2) * _lib.MID_GRID_DOUBLES_PER_CELL * 8
+    return (raw + 255) // 256 * 256
+
+
 def _refusal(p):
     """Why Problem `p` cannot be a member, as (exception class, reason), or None.  Host only: mirrors gpf_ensemble_create."""
     if os.environ.get('GPF_SMALL_GRID') is not None and _atoi(os.environ['GPF_SMALL_GRID']) == 0:
@@ -34,11 +55,11 @@ def _refusal(p):
         return NotImplementedError, "shear thinning steps stage-wise (it needs grad p)"
     if p._elastic or p.topo.elastic:
         return NotImplementedError, "an elastic gap steps stage-wise and deforms between steps"
-    cells = p._shape[0] * p._shape[1]
-    if cells * _lib.SMALL_GRID_DOUBLES_PER_CELL * 8 > _lib.SMALL_GRID_LDS_BYTES:
+    if member_tier(p._shape[0] - 2, p._shape[1] - 2) is None:
         return NotImplementedError, (f"its {p.grid['Nx']} x {p.grid['Ny']} grid does not fit one workgroup's LDS "
                                      f"({_lib.SMALL_GRID_DOUBLES_PER_CELL} doubles per cell, ghost cells included, in "
-                                     f"{_lib.SMALL_GRID_LDS_BYTES // 1024} KB)")
+                                     f"{_lib.SMALL_GRID_LDS_BYTES // 1024} KB) nor the workspace tier (at most "
+                                     f"{_lib.MID_GRID_MAX_CELLS} cells, ghost cells included)")
     if p._integral_every is not None:
         return NotImplementedError, "film integrals are armed on it (they cut the batch per member): clear_integrals(), or run it alone"
     if getattr(p, '_weighted_every', None) is not None:        # (getattr: a Problem made without __init__ has no such attribute)
@@ -99,9 +120,12 @@ def sweep_members(base, axes):
 
 
 class Ensemble:
-    """`Ensemble(problems)`: the given `Problem` objects, advanced together.  See the module's text."""
+    """`Ensemble(problems, tier='auto')`: the given `Problem` objects, advanced together.  tier='workspace' gives every member
+    the workspace tier, those that fit LDS too.  See the module's text."""
 
-    def __init__(self, problems):
+    def __init__(self, problems, tier='auto'):
+        if tier not in ('auto', 'workspace'):
+            raise ValueError(f"Ensemble: tier = {tier!r}, 'auto' or 'workspace' required")
         problems = list(problems)
         if len(problems) < 1:
             raise ValueError("Ensemble: at least one member is required (an empty list was given)")
@@ -122,7 +146,8 @@ class Ensemble:
         self._lib = problems[0]._lib
         self._e = C.c_void_p()
         handles = (C.c_void_p * len(problems))(*[p._h.value for p in problems])
-        _lib.check(self._lib.gpf_ensemble_create(handles, len(problems), C.byref(self._e)))
+        flags = _lib.ENSEMBLE_FORCE_WORKSPACE if tier == 'workspace' else 0
+        _lib.check(self._lib.gpf_ensemble_create2(handles, len(problems), flags, C.byref(self._e)))
 
     def __del__(self):
         e = getattr(self, '_e', None)
@@ -252,6 +277,16 @@ class Ensemble:
     # -------------------------------------------------------------------------------------
     # views
     # -------------------------------------------------------------------------------------
+    @property
+    def tiers(self):
+        """The tier of every member as the library assigned it: 'lds' or 'workspace'."""
+        out = []
+        for i in range(len(self.problems)):
+            t = C.c_int32(0)
+            _lib.check(self._lib.gpf_ensemble_member_info(self._e, i, C.byref(t), None))
+            out.append(_lib.ENSEMBLE_TIERS[t.value])
+        return out
+
     @property
     def steps(self):
         """Step count of every member (-1 before its `_pre_run`)."""

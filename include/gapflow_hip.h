@@ -683,17 +683,25 @@ int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms);
  * buffers, the very body that k_small_steps runs for a handle alone (csrc/small_kernel.hip), so a member's field, run state
  * and per-step records are bit for bit those of a solo gpf_step of the same count.  Members differ freely in grid, gap,
  * edges, equation of state, step size and stop condition; nothing is shared between them.
+ * Two tiers.  LDS: a member of at most 1200 cells, ghost cells included (150 KB at 16 doubles per cell), as above.  WORKSPACE: a
+ * larger member of at most 16384 cells (up to 126 x 126 interior cells) runs k_mid_ensemble (csrc/mid_kernel.hip): the same
+ * phases and per-cell arithmetic on one workgroup, its 19 planes per cell in a workspace in device memory that the ensemble
+ * allocates at create and frees at destroy.  Such a member's results do not depend on who else is in the ensemble nor on how
+ * its steps are split into calls; they agree with its solo gpf_step (another kernel, k_step2) to rounding, not bit for bit.
  *   gpf_ensemble_create   BORROWS the m handles: it does not own them and they must outlive the ensemble.  GPF_ERR_INVALID, with
  *                         a message that names the member and the reason, for: m < 1; a null handle; the same handle twice (two
  *                         workgroups would write the same buffers); a member that the one-workgroup kernel cannot take (grid
- *                         beyond 150 KB of LDS at 16 doubles per ghosted cell, shear thinning, slab halo, surrogate set, elastic
+ *                         beyond 150 KB of LDS at 16 doubles per ghosted cell AND beyond 16384 ghosted cells, shear thinning, slab halo, surrogate set, elastic
  *                         gap, or GPF_SMALL_GRID=0 in the environment); members on different devices or streams (one launch
  *                         needs one stream); film integrals, probes or extrema armed on a member.
+ *                         GPF_ERR_HIP, with nothing left allocated, if the argument buffers or the workspaces cannot be had.
+ *   gpf_ensemble_create2  the same with flags: 0, or GPF_ENSEMBLE_FORCE_WORKSPACE: every member gets the workspace tier, those
+ *                         that fit LDS too (a cross-check of the two tiers on one problem).  gpf_ensemble_create is flags = 0.
  *   gpf_ensemble_step     n[i] steps for member i, 0 <= n[i] <= 4096 (the log's capacity); 0 leaves the member alone: it is not
  *                         launched and nothing of it is touched.  honor_stop as in gpf_step, for all members.  The members
- *                         to advance are grouped by instantiation (equation of state, slip-length field present or not); each
- *                         group is one launch on the members' stream with one workgroup per member and the dynamic LDS of its
- *                         largest member.  The kernels' arguments travel in one host-to-device copy per call and every
+ *                         to advance are grouped by tier and instantiation (equation of state, slip-length field present or not);
+ *                         each group is one launch on the members' stream with one workgroup per member (LDS tier: with the
+ *                         dynamic LDS of its largest member).  The kernels' arguments travel in one host-to-device copy per call and every
  *                         member's final run state comes back in one.  n_executed (may be NULL): m step counts afterwards.
  *                         Afterwards every advanced handle is as gpf_step(h, n[i], honor_stop, ...) leaves it, the rollback of
  *                         an invalid step included: it may be stepped alone, queried or checkpointed.  Checked before anything is
@@ -711,13 +719,22 @@ int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms);
  *   gpf_ensemble_destroy  frees the ensemble's argument buffers; the members stay.
  *   gpf_ensemble_limits   what a member may be, for hosts that refuse before calling (any pointer may be NULL): the LDS bytes
  *                         the one-workgroup kernel may take, the doubles it keeps per ghosted cell, the most steps per member
- *                         and call (the log's capacity).  Needs no device. */
+ *                         and call (the log's capacity).  Needs no device.
+ *   gpf_ensemble_limits2  likewise for the workspace tier: the most cells, ghost cells included, and the doubles per cell of a
+ *                         workspace (which is that many doubles per cell, rounded up to 256 bytes).
+ *   gpf_ensemble_member_info  the tier member `member` got (GPF_ENSEMBLE_TIER_*) and the bytes of its workspace (0 in the LDS
+ *                         tier); either pointer may be NULL. */
+#define GPF_ENSEMBLE_FORCE_WORKSPACE 1
+enum { GPF_ENSEMBLE_TIER_LDS = 0, GPF_ENSEMBLE_TIER_WORKSPACE = 1 };
 typedef struct gpf_ensemble gpf_ensemble;
 int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemble** out);
 int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_stop, int64_t* n_executed);
 int gpf_ensemble_log(gpf_ensemble* e, int member, gpf_scalars_t* log, int64_t log_capacity, int64_t* n_entries);
 int gpf_ensemble_destroy(gpf_ensemble* e);
 int gpf_ensemble_limits(int64_t* lds_bytes, int32_t* doubles_per_cell, int64_t* max_steps);
+int gpf_ensemble_create2(gpf_handle* const* members, int m, int flags, gpf_ensemble** out);
+int gpf_ensemble_limits2(int64_t* mid_max_cells, int32_t* mid_doubles_per_cell);
+int gpf_ensemble_member_info(gpf_ensemble* e, int member, int32_t* tier, int64_t* workspace_bytes);
 
 /* ---- resampling a state onto another grid (no reference counterpart) ------------------------------- */
 /* dst's state from src's committed state, both covering the same domain with different (Nx, Ny): bilinear interpolation, over
