@@ -56,6 +56,9 @@ STATS_QUANTITIES = ('mean', 'm2', 'min', 'max')     # gpf_stats_read: quantity i
 REGION_MAX = 8                      # gpf_regions_set: regions per handle
 REGION_FIELDS = ('p', 'rho', 'h', 'jx', 'jy')       # gpf_region.field: GPF_REGION_*
 REGION_INTS = ('cells', 'ix_min', 'ix_max', 'iy_min', 'iy_max')     # gpf_regions_*: the record's int64 part; its doubles: WEIGHTED_INTEGRANDS
+LINE_MAX = 8                        # gpf_lines_set: lines per handle
+LINE_FIELDS = ('rho', 'jx', 'jy', 'p', 'h', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')       # gpf_lines_*: a point's nine values, in the record's order
+LINE_AXES = ('x', 'y')              # gpf_line.along: GPF_LINE_X, GPF_LINE_Y
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -75,6 +78,11 @@ class GpfConfig(C.Structure):
 class GpfRegion(C.Structure):
     """gpf_region of include/gapflow_hip.h"""
     _fields_ = [('field', C.c_int32), ('box', C.c_int32 * 4), ('lo', C.c_double), ('hi', C.c_double)]
+
+
+class GpfLine(C.Structure):
+    """gpf_line of include/gapflow_hip.h"""
+    _fields_ = [('along', C.c_int32), ('i0', C.c_int32), ('i1', C.c_int32)]
 
 
 class GpfScalars(C.Structure):
@@ -186,6 +194,11 @@ SIGNATURES = {
     'gpf_regions_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_regions_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int64), C.c_int64]),
     'gpf_regions_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_lines_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(GpfLine), C.c_int64]),
+    'gpf_lines_clear': (C.c_int, [C.c_void_p]),
+    'gpf_lines_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_lines_now': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfLine), _DP, C.c_int64]),
+    'gpf_lines_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_ensemble_create': (C.c_int, [_VPP, C.c_int, _VPP]),
     'gpf_ensemble_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]),
     'gpf_ensemble_log': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfScalars), C.c_int64, C.POINTER(C.c_int64)]),

@@ -28,6 +28,7 @@
 #include "weighted_kernels.hip"
 #include "stats_kernels.hip"
 #include "region_kernels.hip"
+#include "line_kernels.hip"
 #include "resample_kernels.hip"
 
 using namespace gpf;
@@ -124,6 +125,12 @@ struct gpf_handle {
     // then, 8-byte loads); the records of the last stepping call and their step counts on the host
     struct { long long every = 0; int K = 0; Region* defs = nullptr; double* part = nullptr; int* ipart = nullptr; double* rec = nullptr;
              long long* irec = nullptr; bool narrow = false; std::vector<double> host; std::vector<long long> ihost, steps; } regions;
+    // line profiles (api_lines.inc): recording stride (0: not armed), number of lines K and the lines as the kernels read them;
+    // doubles per record and records the device buffer holds (a batch never leaves more: lines_batch); the device records of the
+    // batch in flight ([capacity + 1][rec_doubles]) and the chunk sums of the bands along y, both allocated by gpf_lines_set; the
+    // records of the last stepping call and their step counts on the host
+    struct { long long every = 0; int K = 0; Line defs[LINE_MAX_K] = {}; long long rec_doubles = 0, capacity = 0; double* rec = nullptr;
+             double* scratch = nullptr; std::vector<double> host; std::vector<long long> steps; } lines;
     // field extrema (api_extrema.inc): recording stride (0: not armed); the device records of the batch in flight ([log_cap + 1][7]
     // doubles, [log_cap + 1][14] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was set then);
     // `dev`: the ExtremaArgs of these buffers in device memory, for k_small_steps; the records of the last stepping call on the host.
@@ -375,7 +382,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -1053,6 +1060,7 @@ static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long 
 #include "api_weighted.inc"
 #include "api_extrema.inc"
 #include "api_regions.inc"
+#include "api_lines.inc"
 #include "api_stats.inc"
 
 extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t* log, int64_t log_capacity,
@@ -1070,11 +1078,12 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     GPF_TRY(integrals_begin(h));
     GPF_TRY(weighted_begin(h));
     GPF_TRY(regions_begin(h));
+    GPF_TRY(lines_begin(h));
     GPF_TRY(extrema_begin(h));
     GPF_TRY(stats_begin(h));
     while (done < n) {
-        const int64_t batch = std::min<int64_t>(n - done, h->log_cap);
         const long long base = h->host_step;
+        const int64_t batch = lines_batch(h, std::min<int64_t>(n - done, h->log_cap), base);        // (lines: no more records than their buffer holds)
         if (small) GPF_TRY(small_batch_cut(h, batch, honor_stop, base));       // the batch, cut at the union of the armed series' steps
         else for (int64_t i = 0; i < batch; ++i) {
             GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
@@ -1082,6 +1091,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
             GPF_TRY(integrals_launch(h, base + i + 1, base));   // nor without integrals, nor off their stride
             GPF_TRY(weighted_launch(h, base + i + 1, base));    // nor without weighted integrals, nor off theirs
             GPF_TRY(regions_launch(h, base + i + 1, base));     // nor without regions, nor off theirs
+            GPF_TRY(lines_launch(h, base + i + 1, base));       // nor without lines, nor off theirs
             GPF_TRY(extrema_launch(h, base + i + 1, base));     // nor without extrema, nor off theirs
             GPF_TRY(stats_launch(h, base + i + 1));             // nor without statistics, nor off theirs
         }
@@ -1092,6 +1102,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
         GPF_TRY(integrals_collect(h, base, ran));
         GPF_TRY(weighted_collect(h, base, ran));
         GPF_TRY(regions_collect(h, base, ran));
+        GPF_TRY(lines_collect(h, base, ran));
         GPF_TRY(extrema_collect(h, base, ran));
         GPF_TRY(stats_collect(h, s.step));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);

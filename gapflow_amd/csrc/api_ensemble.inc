@@ -46,6 +46,7 @@ static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first, int
     if (h->weighted.every) return "weighted integrals are armed on it (they cut the batch per member; gpf_weighted_clear, or step it alone)";
     if (h->stats.every) return "statistics are armed on it (they cut the batch per member; gpf_stats_clear, or step it alone)";
     if (h->regions.every) return "regions are armed on it (they cut the batch per member; gpf_regions_clear, or step it alone)";
+    if (h->lines.every) return "lines are armed on it (they cut the batch per member; gpf_lines_clear, or step it alone)";
     if (h->probes.n) return "probes are armed on it (their records need per-member slots; gpf_probes_clear, or step it alone)";
     if (h->extr.every) return "extrema are armed on it (their records need per-member slots; gpf_extrema_clear, or step it alone)";
     return "";

@@ -181,9 +181,10 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
     GPF_TRY(enter(h));
     h->integ.host.clear(); h->integ.steps.clear();
     h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->integ.every, keep_weighted = h->weighted.every, keep_stats = h->stats.every, keep_regions = h->regions.every;
+    const long long keep_every = h->integ.every, keep_weighted = h->weighted.every, keep_stats = h->stats.every, keep_regions = h->regions.every,
+                    keep_lines = h->lines.every;
     const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->weighted.every = 0; h->stats.every = 0; h->regions.every = 0;
+    h->probes.n = 0; h->weighted.every = 0; h->stats.every = 0; h->regions.every = 0; h->lines.every = 0;
     if (mode != 1) h->integ.every = 0;
     int rc = integrals_begin(h);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -214,7 +215,7 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
     }
     int rcol = GPF_OK;
     if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = integrals_collect(h, base, s.step - base);
-    h->integ.every = keep_every; h->weighted.every = keep_weighted; h->stats.every = keep_stats; h->regions.every = keep_regions; h->probes.n = keep_probes;
+    h->integ.every = keep_every; h->weighted.every = keep_weighted; h->stats.every = keep_stats; h->regions.every = keep_regions; h->lines.every = keep_lines; h->probes.n = keep_probes;
     if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
     GPF_TRY(rc);
     if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_integrals_time: ") + hipGetErrorString(e));

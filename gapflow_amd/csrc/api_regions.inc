@@ -192,9 +192,9 @@ extern "C" int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms) 
     h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
     h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
     const long long keep_every = h->regions.every, keep_integ = h->integ.every, keep_weighted = h->weighted.every, keep_extr = h->extr.every,
-                    keep_stats = h->stats.every;
+                    keep_stats = h->stats.every, keep_lines = h->lines.every;
     const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->extr.every = 0; h->stats.every = 0;
+    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->extr.every = 0; h->stats.every = 0; h->lines.every = 0;
     if (mode != 1) h->regions.every = 0;
     int rc = regions_begin(h);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -226,7 +226,7 @@ extern "C" int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms) 
     int rcol = GPF_OK;
     if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = regions_collect(h, base, s.step - base);
     h->regions.every = keep_every; h->integ.every = keep_integ; h->weighted.every = keep_weighted; h->extr.every = keep_extr; h->stats.every = keep_stats;
-    h->probes.n = keep_probes;
+    h->lines.every = keep_lines; h->probes.n = keep_probes;
     if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
     GPF_TRY(rc);
     if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_regions_time: ") + hipGetErrorString(e));

@@ -103,20 +103,21 @@ static int stats_release(gpf_handle* h) {
 }
 
 // A batch of the small-grid kernel, cut at the union of the steps that the series which cut it record (film integrals, weighted
-// integrals, regions, statistics), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
+// integrals, regions, lines, statistics), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
 // batch in pieces is bitwise the batch in one: every piece starts from the state and the run state the piece before left.
 // With none of them armed this is the one launch.
 static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base) {
     const long long end = base + batch;
     for (long long at = base; at < end;) {
         long long next = end;
-        for (long long every : {h->integ.every, h->weighted.every, h->regions.every})
+        for (long long every : {h->integ.every, h->weighted.every, h->regions.every, h->lines.every})
             if (every) next = std::min(next, (at / every + 1) * every);
         if (h->stats.every) next = std::min(next, (std::max(at, stats_floor(h)) / h->stats.every + 1) * h->stats.every);
         GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
         GPF_TRY(integrals_launch(h, next, base));
         GPF_TRY(weighted_launch(h, next, base));
         GPF_TRY(regions_launch(h, next, base));
+        GPF_TRY(lines_launch(h, next, base));
         GPF_TRY(stats_launch(h, next));
         at = next;
     }
@@ -207,9 +208,10 @@ extern "C" int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     h->weighted.host.clear(); h->weighted.steps.clear();
     h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
     h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->stats.every, keep_integ = h->integ.every, keep_weighted = h->weighted.every, keep_extr = h->extr.every, keep_regions = h->regions.every;
+    const long long keep_every = h->stats.every, keep_integ = h->integ.every, keep_weighted = h->weighted.every, keep_extr = h->extr.every, keep_regions = h->regions.every,
+                    keep_lines = h->lines.every;
     const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->extr.every = 0; h->regions.every = 0;
+    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->extr.every = 0; h->regions.every = 0; h->lines.every = 0;
     if (mode != 1) h->stats.every = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipEventCreate(&e0);
@@ -248,7 +250,7 @@ extern "C" int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms) {
         h->prev_state_valid = s.step > base && !s.invalid;
         h->host_step = s.step; h->next_step = s.step;
     }
-    h->stats.every = keep_every; h->integ.every = keep_integ; h->weighted.every = keep_weighted; h->extr.every = keep_extr; h->regions.every = keep_regions; h->probes.n = keep_probes;
+    h->stats.every = keep_every; h->integ.every = keep_integ; h->weighted.every = keep_weighted; h->extr.every = keep_extr; h->regions.every = keep_regions; h->lines.every = keep_lines; h->probes.n = keep_probes;
     int rcol = GPF_OK;
     if (rs == GPF_OK) rcol = mode == 1 ? stats_collect(h, s.step) : stats_restart(h, s.step);      // steps went by unrecorded: a new window
     GPF_TRY(rc);

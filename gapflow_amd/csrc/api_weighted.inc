@@ -184,9 +184,10 @@ extern "C" int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms)
     h->integ.host.clear(); h->integ.steps.clear();
     h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
     h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->weighted.every, keep_integ = h->integ.every, keep_extr = h->extr.every, keep_stats = h->stats.every, keep_regions = h->regions.every;
+    const long long keep_every = h->weighted.every, keep_integ = h->integ.every, keep_extr = h->extr.every, keep_stats = h->stats.every, keep_regions = h->regions.every,
+                    keep_lines = h->lines.every;
     const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0; h->extr.every = 0; h->stats.every = 0; h->regions.every = 0;
+    h->probes.n = 0; h->integ.every = 0; h->extr.every = 0; h->stats.every = 0; h->regions.every = 0; h->lines.every = 0;
     if (mode != 1) h->weighted.every = 0;
     int rc = weighted_begin(h);
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -217,7 +218,7 @@ extern "C" int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms)
     }
     int rcol = GPF_OK;
     if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = weighted_collect(h, base, s.step - base);
-    h->weighted.every = keep_every; h->integ.every = keep_integ; h->extr.every = keep_extr; h->stats.every = keep_stats; h->regions.every = keep_regions; h->probes.n = keep_probes;
+    h->weighted.every = keep_every; h->integ.every = keep_integ; h->extr.every = keep_extr; h->stats.every = keep_stats; h->regions.every = keep_regions; h->lines.every = keep_lines; h->probes.n = keep_probes;
     if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
     GPF_TRY(rc);
     if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_weighted_time: ") + hipGetErrorString(e));

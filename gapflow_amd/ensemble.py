@@ -69,6 +69,8 @@ def _refusal(p):
         return NotImplementedError, "statistics are armed on it (they cut the batch per member): clear_statistics(), or run it alone"
     if getattr(p, '_regions_every', None) is not None:
         return NotImplementedError, "regions are armed on it (they cut the batch per member): clear_regions(), or run it alone"
+    if getattr(p, '_lines_every', None) is not None:
+        return NotImplementedError, "lines are armed on it (they cut the batch per member): clear_lines(), or run it alone"
     if p._probe_cells is not None:
         return NotImplementedError, "probes are armed on it (their records need per-member slots): clear_probes(), or run it alone"
     if p._extrema_every is not None:

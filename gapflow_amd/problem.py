@@ -133,6 +133,11 @@ class Problem:
             if not options.get('region_list'):
                 raise ValueError("options.regions: options.region_list must list the regions")
             self.set_regions(options['region_list'], options['regions'])
+        self._lines_every = None
+        if options.get('lines'):                    # options.lines / options.line_list (from the YAML text, or a checkpoint's dictionaries); 0: off
+            if not options.get('line_list'):
+                raise ValueError("options.lines: options.line_list must list the lines")
+            self.set_lines(options['line_list'], options['lines'])
         self._extrema_every = None
         if options.get('extrema'):                  # options.extrema (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_extrema(options['extrema'])
@@ -186,6 +191,7 @@ class Problem:
         _keep_weighted(input_dict, ymlstring, base_dir)
         _keep_statistics(input_dict, ymlstring)
         _keep_regions(input_dict, ymlstring)
+        _keep_lines(input_dict, ymlstring)
         _keep_init_from(input_dict, ymlstring, base_dir)
         if init_from is not None:
             input_dict['options']['init_from'] = os.path.abspath(os.fspath(init_from))
@@ -482,7 +488,7 @@ class Problem:
 
         Allowed at any time.  Before the first step the run simply begins from the new state; after steps the run starts
         over at step 0 (`_pre_run`), as it would from a state assigned to ``q``, and the probes', integrals', weighted
-        integrals', regions' and extrema series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
+        integrals', regions', lines' and extrema series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
         which is destroyed before the call returns.
         ValueError: the domains differ (Lx or Ly by more than 1e-12 relative), or a direction is periodic on one side only.
         NotImplementedError: surrogate closures here, or a SlabProblem as the source."""
@@ -879,6 +885,132 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'regions.npz'), **s)
 
     # -------------------------------------------------------------------------------------
+    # line profiles (viz/plotting.py:51-60, viz/animations.py:200-242 draw them from written frames)
+    # -------------------------------------------------------------------------------------
+    def _lines_refusal(self):
+        if self.has_gp_model or self._gp_models:
+            raise NotImplementedError("lines: surrogate (GP) closures replace the pressure and wall stress the lines evaluate")
+        if self._cfg.thinning:
+            raise NotImplementedError("lines: shear thinning needs grad p, which the recording does not model")
+        if self._elastic or self.topo.elastic:
+            raise NotImplementedError("lines: an elastic gap steps stage-wise and deforms between steps (not supported)")
+
+    def _line_structs(self, entries):
+        arr = (_lib.GpfLine * len(entries))()
+        for l, e in zip(arr, entries):
+            l.along = _lib.LINE_AXES.index(e['along'])
+            l.i0, l.i1 = _line_span(e, self.grid['Nx'], self.grid['Ny'])
+        return arr
+
+    def _line_lengths(self, entries):
+        return [self.grid['Nx'] if e['along'] == 'x' else self.grid['Ny'] for e in entries]
+
+    def _line_split(self, data, entries):
+        """{name: {field: array(n, length)}} of records (n, doubles of a record) in the library's layout: per line, nine fields,
+        each `length` doubles."""
+        out, at, nf = {}, 0, len(_lib.LINE_FIELDS)
+        for e, length in zip(entries, self._line_lengths(entries)):
+            block = data[:, at:at + nf * length].reshape(len(data), nf, length)
+            out[e['name']] = {f: block[:, k].copy() for k, f in enumerate(_lib.LINE_FIELDS)}
+            at += nf * length
+        return out
+
+    def set_lines(self, lines, every=1, capacity=None):
+        """Record profiles of the committed state along grid lines after every step whose count is a multiple of `every`, on the
+        device, whichever way the steps are taken (`update()`, `run()`, batches of any length): the centre lines that the
+        reference's `plot_frame(dim=1)` and animations draw from written frames, or any other row / column, or the mean over a
+        band of them -- a journal bearing's circumferential pressure profile at mid-width, or averaged over the width.
+
+        lines: a list of 1 to 8 dicts {along, at=None, name=None}.  along 'x': a profile over the interior rows ix = 1..Nx
+        (length Nx), at column `at` (an int iy), or the arithmetic mean over the columns iy0..iy1 inclusive for at = (iy0, iy1);
+        1-based interior indices as in the `box` of regions, 1 <= iy0 <= iy1 <= Ny.  at=None is the reference's centre line,
+        column (Ny + 2) // 2: `q[:, 1:-1, ny // 2]` of the ghosted array.  along 'y': the same with the axes exchanged (length
+        Ny, row ix or rows ix0..ix1, default row (Nx + 2) // 2).  Names default to l0, l1, ...
+        Per point nine fields: rho, jx, jy (the state's own bits), p (the equation of state's pressure of the committed density,
+        bit for bit a probe's p), h (the gap the device holds), tau_xz_bot, tau_yz_bot, tau_xz_top, tau_yz_top (the walls' shear
+        stresses as ``integrals`` evaluates them).  A band adds in a fixed order and divides once: the same state
+        gives the same bits whatever the batch size, stride or kernel that stepped.
+        capacity: the records the device buffer holds (None: as many as fit 64 MiB, or GPF_LINES_MB MiB; at least 1).  A batch
+        never holds more steps than leave that many records, so a small capacity costs launches' latency, nothing else.  On grids
+        small enough for the one-workgroup kernel the batch is also cut at every recorded step: choose a stride there.
+        A step that is rolled back as invalid leaves no record.  Starts a new series (see ``lines``).  Checkpoints do not carry
+        the series: a problem restored from one whose options hold `lines` and `line_list` has them armed again and its series
+        begins at the restart step; lines set from code do not survive a restore.  Not available with surrogate closures, shear
+        thinning or an elastic gap."""
+        self._lines_refusal()
+        every = _lines_stride(every)
+        if capacity is not None and (isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or capacity < 1):
+            raise ValueError(f"lines: capacity must be an integer >= 1 (None: the default), got {capacity!r}")
+        entries = _line_entries(lines, self.grid['Nx'], self.grid['Ny'])
+        _lib.check(self._lib.gpf_lines_set(self._h, every, len(entries), self._line_structs(entries), 0 if capacity is None else int(capacity)))
+        self._lines_every, self._lines_entries = every, entries
+        self._lines_steps, self._lines_times, self._lines_data = [], [], []
+
+    def clear_lines(self):
+        """Stop recording, drop the series and free the device buffers."""
+        if self._lines_every is not None:
+            _lib.check(self._lib.gpf_lines_clear(self._h))
+        self._lines_every = None
+
+    @property
+    def lines(self):
+        """The series of every recorded step since set_lines (or _pre_run), across `update()` and `run()` calls: a dict with
+        `step`, `time` (nrecords,), `names` (the lines', in order) and per line name a dict of the nine arrays (nrecords, length):
+        rho, jx, jy, p, h, tau_xz_bot, tau_yz_bot, tau_xz_top, tau_yz_top.  None when no lines are armed."""
+        if self._lines_every is None:
+            return None
+        nd = len(_lib.LINE_FIELDS) * sum(self._line_lengths(self._lines_entries))
+        data = np.concatenate(self._lines_data) if self._lines_data else np.empty((0, nd))
+        out = {'step': np.array(self._lines_steps, dtype=np.int64), 'time': np.array(self._lines_times, dtype=np.float64),
+               'names': tuple(e['name'] for e in self._lines_entries)}
+        out.update(self._line_split(data, self._lines_entries))
+        return out
+
+    def film_lines(self, lines=None):
+        """The same record for the current state, as {name: {field: array(length)}}: bit for bit what a step committing this
+        state would have recorded.  Of the armed lines, or of `lines` (a list as set_lines takes) without arming anything.
+        Reads only."""
+        self._lines_refusal()
+        if lines is None and self._lines_every is None:
+            raise RuntimeError("film_lines: no lines are set (set_lines), and none are given")
+        entries = self._lines_entries if lines is None else _line_entries(lines, self.grid['Nx'], self.grid['Ny'])
+        self._sync_to_device()
+        out = np.empty((1, len(_lib.LINE_FIELDS) * sum(self._line_lengths(entries))))
+        if lines is None:
+            _lib.check(self._lib.gpf_lines_now(self._h, 0, None, _lib.as_dp(out), out.size))
+        else:
+            _lib.check(self._lib.gpf_lines_now(self._h, len(entries), self._line_structs(entries), _lib.as_dp(out), out.size))
+        return {name: {f: v[0] for f, v in rec.items()} for name, rec in self._line_split(out, entries).items()}
+
+    def _collect_lines(self, entries, before):
+        """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
+        if self._lines_every is None or not entries:
+            return
+        n = _integral_records(before, len(entries), self._lines_every)
+        out = np.empty((n, len(_lib.LINE_FIELDS) * sum(self._line_lengths(self._lines_entries))))
+        steps = np.zeros(n, dtype=np.int64)
+        have = C.c_int64(0)
+        _lib.check(self._lib.gpf_lines_read(self._h, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
+        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._lines_every == 0]
+        if have.value != n or steps.tolist() != want:
+            raise _lib.GapflowHipError(f"lines: {have.value} records of steps {steps.tolist()} for the committed steps "
+                                       f"{before + 1}..{before + len(entries)} at stride {self._lines_every}")
+        self._lines_steps.extend(want)
+        self._lines_times.extend(entries[s - before - 1].simtime for s in want)
+        self._lines_data.append(out)
+
+    def _write_lines(self):
+        """lines.npz: step, time, names, along and at (K, 2: the first and last column / row) of the lines, and `<name>.<field>`
+        (nrecords, length) for every line and field."""
+        s = self.lines
+        arrays = {'step': s['step'], 'time': s['time'], 'names': np.array(s['names']),
+                  'along': np.array([e['along'] for e in self._lines_entries]),
+                  'at': np.array([_line_span(e, self.grid['Nx'], self.grid['Ny']) for e in self._lines_entries], dtype=np.int64)}
+        for name in s['names']:
+            arrays.update({f'{name}.{f}': v for f, v in s[name].items()})
+        np.savez(os.path.join(self.outdir, 'lines.npz'), **arrays)
+
+    # -------------------------------------------------------------------------------------
     # field extrema (no reference counterpart; DESIGN.md 3.3g)
     # -------------------------------------------------------------------------------------
     def _extrema_refusal(self):
@@ -1055,6 +1187,8 @@ class Problem:
             self._weighted_steps, self._weighted_times, self._weighted_data = [], [], []
         if self._regions_every is not None:
             self._regions_steps, self._regions_times, self._regions_sums, self._regions_ints = [], [], [], []
+        if self._lines_every is not None:
+            self._lines_steps, self._lines_times, self._lines_data = [], [], []
         if self._extrema_every is not None:
             self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
 
@@ -1087,6 +1221,7 @@ class Problem:
         self._collect_integrals(entries, before)
         self._collect_weighted(entries, before)
         self._collect_regions(entries, before)
+        self._collect_lines(entries, before)
         self._collect_extrema(entries, before)
         if ran > 0:
             self._mark_device_advanced()
@@ -1245,6 +1380,8 @@ class Problem:
                 self._write_weighted()
             if self._regions_every is not None:
                 self._write_regions()
+            if self._lines_every is not None:
+                self._write_lines()
             if self._extrema_every is not None:
                 self._write_extrema()
             if self._stats_every is not None:
@@ -1540,6 +1677,87 @@ def _keep_regions(input_dict, ymlstring):
                                                                int(grid['Ny']) if 'Ny' in grid else None, where='options.region_list')
     if input_dict['options'].get('regions') and not input_dict['options'].get('region_list'):
         raise ValueError("options.regions: options.region_list must list the regions")
+
+
+def _lines_stride(every, allow_zero=False):
+    low = 0 if allow_zero else 1
+    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
+        raise ValueError(f"lines: the stride must be an integer >= {low}, got {every!r}")
+    return int(every)
+
+
+def _line_centre(along, nx, ny):
+    """The reference's centre line: column ny // 2 of the ghosted frame (ny = Ny + 2) along x, row nx // 2 along y."""
+    return (ny + 2) // 2 if along == 'x' else (nx + 2) // 2
+
+
+def _line_span(entry, nx, ny):
+    """(first, last) column (along x) or row (along y) of a checked entry, the centre line for at = None."""
+    at = entry['at']
+    if at is None:
+        at = _line_centre(entry['along'], nx, ny)
+    return (at, at) if isinstance(at, int) else (at[0], at[1])
+
+
+def _line_entries(lines, nx=None, ny=None, where='lines'):
+    """What set_lines / options.line_list is given, checked and completed: a list of 1 to 8 dicts {along, at, name} with along 'x'
+    or 'y', at None (the centre line), an int or a list of two ints, and the names distinct (l0, l1, ... when absent).
+    ValueError, naming the entry, for an unknown key or axis, an `at` that is no integer or pair of integers first <= last
+    inside the interior (checked against nx, ny where given), a name that is no non-empty string, is used twice or is one of the
+    series' own keys.  Host only: no library call."""
+    if isinstance(lines, (str, bytes, dict)) or not hasattr(lines, '__len__') or not 1 <= len(lines) <= _lib.LINE_MAX:
+        raise ValueError(f"{where}: a list of 1 to {_lib.LINE_MAX} lines {{along, at, name}} is required, got {lines!r}")
+    out = []
+    for k, e in enumerate(lines):
+        def bad(msg):
+            return ValueError(f"{where}: entry {k}: {msg}, got {e!r}")
+
+        def is_int(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+        if not isinstance(e, dict) or set(e) - {'along', 'at', 'name'}:
+            raise bad("a dict with the keys along, at, name is required")
+        if e.get('along') not in _lib.LINE_AXES:
+            raise bad(f"along must be one of {list(_lib.LINE_AXES)}")
+        n = None if nx is None or ny is None else (ny if e['along'] == 'x' else nx)       # the axis `at` counts along
+        at = e.get('at')
+        if at is not None:
+            if is_int(at):
+                at = int(at)
+                lo = hi = at
+            elif not isinstance(at, (str, bytes, dict)) and hasattr(at, '__len__') and len(at) == 2 and all(is_int(v) for v in at):
+                at = [int(v) for v in at]
+                lo, hi = at
+            else:
+                raise bad("at must be an integer or a pair of integers (first, last)")
+            if not 1 <= lo <= hi or (n is not None and hi > n):
+                raise bad("at must be first <= last inside the interior (inclusive, 1-based)")
+        name = e.get('name')
+        name = f'l{k}' if name is None else name
+        if not isinstance(name, str) or not name or name in ('step', 'time', 'names'):
+            raise bad("name must be a non-empty string other than step, time, names")
+        if name in [o['name'] for o in out]:
+            raise bad(f"the name {name!r} is used twice")
+        out.append({'along': e['along'], 'at': at, 'name': name})
+    return out
+
+
+def _keep_lines(input_dict, ymlstring):
+    """`options.lines: N` (the stride; 0 or absent: off) and `options.line_list: [{along: x}, {along: y, at: [1, 32], name: band}]`
+    are this project's own keys: read from the YAML text and set beside the sanitised ones, like the regions' -- only when given,
+    so that every other input's dictionaries stay as they are.  Checked here, on the host (_line_entries)."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    grid = input_dict.get('grid') or {}
+    if opts.get('lines') is not None:
+        input_dict['options']['lines'] = _lines_stride(opts['lines'], allow_zero=True)
+    if opts.get('line_list') is not None:
+        input_dict['options']['line_list'] = _line_entries(opts['line_list'], int(grid['Nx']) if 'Nx' in grid else None,
+                                                           int(grid['Ny']) if 'Ny' in grid else None, where='options.line_list')
+    if input_dict['options'].get('lines') and not input_dict['options'].get('line_list'):
+        raise ValueError("options.lines: options.line_list must list the lines")
 
 
 def _extrema_stride(every, allow_zero=True):

@@ -443,6 +443,14 @@ class SlabProblem:
         """Regions are reduced on unsliced problems only."""
         raise NotImplementedError("regions: not available on a SlabProblem")
 
+    def set_lines(self, *args, **kwargs):
+        """Line profiles are recorded on unsliced problems only."""
+        raise NotImplementedError("lines: not available on a SlabProblem")
+
+    def film_lines(self, *args, **kwargs):
+        """Line profiles are recorded on unsliced problems only."""
+        raise NotImplementedError("lines: not available on a SlabProblem")
+
     def set_extrema(self, *args, **kwargs):
         """Field extrema are recorded on unsliced problems only."""
         raise NotImplementedError("extrema: not available on a SlabProblem")
@@ -475,6 +483,8 @@ class SlabProblem:
             raise NotImplementedError("weighted integrals: not available on a SlabProblem")   # options.weighted_integrals: as set_weighted_integrals
         if (input_dict.get('options') or {}).get('regions'):                         # (0: off, as on a Problem)
             raise NotImplementedError("regions: not available on a SlabProblem")     # options.regions: as set_regions
+        if (input_dict.get('options') or {}).get('lines'):                           # (0: off, as on a Problem)
+            raise NotImplementedError("lines: not available on a SlabProblem")       # options.lines: as set_lines
         if (input_dict.get('options') or {}).get('extrema'):                         # (0: off, as on a Problem)
             raise NotImplementedError("extrema: not available on a SlabProblem")     # options.extrema: as set_extrema
         if (input_dict.get('options') or {}).get('statistics'):                      # (0: off, as on a Problem)
@@ -605,7 +615,7 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None, base_dir=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted, _keep_statistics, _keep_regions
+        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted, _keep_statistics, _keep_regions, _keep_lines
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
@@ -615,6 +625,7 @@ class SlabProblem:
         _keep_weighted(d, text, base_dir)           # options.weighted_integrals: refused below
         _keep_statistics(d, text)                   # options.statistics: refused below
         _keep_regions(d, text)                      # options.regions: refused below
+        _keep_lines(d, text)                        # options.lines: refused below
         _keep_init_from(d, text, base_dir)          # options.init_from: refused below
         return cls(d, device=device, dist=dist)
 

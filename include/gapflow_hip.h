@@ -678,6 +678,60 @@ int gpf_regions_now(gpf_handle* h, double* sums, int64_t* ints, int64_t count);
  * Probes, film integrals, weighted integrals, extrema and statistics are put aside in both modes. */
 int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- line profiles (viz/plotting.py:51-60, viz/animations.py:200-242: the centre lines of the written frames) --------------- */
+/* The reference's plots of a 2-D run are one-dimensional: plot_frame(dim=1) and the animations draw rho, jx, jy, p, the wall shear
+ * stress of both walls and h along the centre lines [1:-1, ny // 2] and [nx // 2, 1:-1] of the ghosted frames.  These entry points
+ * record such lines of the COMMITTED state on the device, so that an x-t diagram needs no frame to leave it.  A line is {along, i0,
+ * i1} in 1-based interior indices: along GPF_LINE_X, a profile over the interior rows ix = 1..Nx (length Nx) at column i0 = i1, or
+ * the arithmetic mean over the columns i0..i1 inclusive (1 <= i0 <= i1 <= Ny); along GPF_LINE_Y, the same with the axes exchanged
+ * (length Ny, rows 1 <= i0 <= i1 <= Nx).  i0 = i1 = 0 is the reference's centre line: column (Ny + 2) / 2 (row (Nx + 2) / 2), the
+ * ny // 2 of the ghosted shape.  Ghost cells are never on a line.  Up to 8 lines per handle.
+ * Per point nine fields, in this order: rho, jx, jy (the planes of the state), p (csrc/closures.hpp eos_pressure of the committed
+ * density: the function k_probe_record calls, the same bits), h (plane 0 of the gap as the device holds it), tau_xz_bot,
+ * tau_yz_bot, tau_xz_top, tau_yz_top (lower[4], lower[3], upper[4], upper[3] of cell_fields: the terms the film integrals add).
+ * Record layout: for each line in order, nine fields, each `length` doubles.
+ * A single-index line holds the cells' own values.  A band adds each field in a fixed order from +0.0 and divides by (double)n
+ * with a true division (csrc/lines.hpp states the order so that a loop on the host can restate it): along x one wave per row,
+ * lane l adding the columns i0 + l, i0 + l + 64, ... ascending and the 64 lanes folded 32, 16, .. 1 apart; along y chunks of 32
+ * consecutive rows from i0 added ascending, then the chunk sums ascending.  A record is a pure function of the state and the
+ * lines: no atomics, no arrival order, and the same bits whichever kernel stepped.  Recording only reads.
+ *   gpf_lines_set     arms recording after every committed step whose new step count is a multiple of `every` (>= 1) with the K
+ *                     lines (copied), and starts with empty records.  `capacity`: the records the device buffer holds; 0: as
+ *                     many as fit 64 MiB (GPF_LINES_MB in the environment: another number of MiB), at least 1; never more than
+ *                     ceil(4096 / every), what the longest batch can leave.  GPF_ERR_INVALID for every < 1, capacity < 0, K
+ *                     outside 1..8, `along` neither 0 nor 1, indices outside the interior or reversed (the message names the
+ *                     line), surrogate closures, shear thinning or an elastic gap; GPF_ERR_STATE on a slab and while a
+ *                     stage-wise step is open.
+ *   gpf_lines_clear   disarms and frees the buffers.
+ *   gpf_lines_read    the records of the LAST gpf_step call, out [record][doubles of a record], and the step count of each in
+ *                     steps_out (either may be NULL); *n_records how many the call left, min(*n_records, capacity_records) are
+ *                     copied.  A batch that stopped on the device leaves the records of the steps that ran; a step that was
+ *                     rolled back as invalid leaves none.  GPF_ERR_STATE unless armed.
+ *   gpf_lines_now     the same record for the current committed state, by the same kernels: of the armed lines (K = 0, lines
+ *                     NULL), or of the K lines given, with buffers of this call's own and nothing armed or disarmed.  `count`:
+ *                     the doubles `out` has room for (>= those of a record).  GPF_ERR_STATE on an invalid run state, and with
+ *                     no lines given unless armed.
+ * Where they are written: k_line_point, k_line_band_x, k_line_band_y_partial + k_line_band_y_fold (csrc/line_kernels.hip; only the
+ * kinds the lines need are launched) behind the step's launch, told the step count the step produces if it commits and writing
+ * only if the device's run state shows that count and a valid state.  The buffer is bounded, so gpf_step never puts more than
+ * `capacity` records into one batch: with lines armed a batch is min(n - done, 4096, capacity * every - steps since the last
+ * record); a call in several batches is bitwise the call in one.  On grids small enough for k_small_steps the batch is also cut
+ * at the recorded steps, like the regions'.  gpf_close_step, gpf_step_timed and the slab calls record nothing. */
+#define GPF_LINE_X 0
+#define GPF_LINE_Y 1
+typedef struct {
+    int32_t along;             /* GPF_LINE_X / GPF_LINE_Y                                           */
+    int32_t i0, i1;            /* columns (along x) / rows (along y), inclusive; both 0: the centre */
+} gpf_line;
+int gpf_lines_set(gpf_handle* h, int64_t every, int K, const gpf_line* lines /* [K] */, int64_t capacity);
+int gpf_lines_clear(gpf_handle* h);
+int gpf_lines_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_lines_now(gpf_handle* h, int K, const gpf_line* lines /* [K], or NULL */, double* out, int64_t count);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording (armed lines are put aside for the call), 1 recording at the armed stride, n no more than one batch may
+ * hold (tools/lines_time.py).  Every other series is put aside in both modes. */
+int gpf_lines_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* ---- ensembles (no reference counterpart: the reference runs a parameter study as one process per problem) ---------------- */
 /* Many small problems advanced by ONE launch per kernel instantiation: workgroup m of k_small_ensemble runs, on member m's own
  * buffers, the very body that k_small_steps runs for a handle alone (csrc/small_kernel.hip), so a member's field, run state
