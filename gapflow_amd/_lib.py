@@ -173,6 +173,7 @@ SIGNATURES = {
     'gpf_integrals_clear': (C.c_int, [C.c_void_p]),
     'gpf_integrals_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_integrals_now': (C.c_int, [C.c_void_p, _DP, C.c_int64]),
+    'gpf_integrals_in_batch': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'gpf_integrals_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_weighted_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_weighted_clear': (C.c_int, [C.c_void_p]),
@@ -207,6 +208,9 @@ SIGNATURES = {
     'gpf_ensemble_create2': (C.c_int, [_VPP, C.c_int, C.c_int, _VPP]),
     'gpf_ensemble_limits2': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     'gpf_ensemble_member_info': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    'gpf_ensemble_integrals_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
+    'gpf_ensemble_integrals_clear': (C.c_int, [C.c_void_p]),
+    'gpf_ensemble_integrals_read': (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_resample': (C.c_int, [C.c_void_p, C.c_void_p]),
     'gpf_resample_time': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _DP]),
 }

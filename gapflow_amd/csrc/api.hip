@@ -20,11 +20,11 @@
 #include "elastic_kernels.hip"
 #include "probe_kernels.hip"
 #include "extrema_kernels.hip"
+#include "integral_kernels.hip"
 #include "small_kernel.hip"
 #include "mid_kernel.hip"
 #include "profile_kernels.hip"
 #include "checkpoint_kernels.hip"
-#include "integral_kernels.hip"
 #include "weighted_kernels.hip"
 #include "stats_kernels.hip"
 #include "region_kernels.hip"
@@ -111,8 +111,10 @@ struct gpf_handle {
     // film integrals (api_integrals.inc): recording stride (0: not armed), sections (nsx 0: not chosen yet), the device records of
     // the batch in flight ([log_cap + 1][9 + nsx + nsy]) and the row scratch ([Nx][FILM_NV]), both allocated on first use (`narrow`:
     // GPF_FILM_NARROW was set then, 8-byte loads); the records of the last stepping call and their step counts on the host
+    // `dev`: the FilmBlockArgs of the record buffer in device memory, for k_small_steps (written with the buffers, freed with them)
     struct { long long every = 0; int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
-             double* rec = nullptr; double* part = nullptr; bool narrow = false; std::vector<double> host; std::vector<long long> steps; } integ;
+             double* rec = nullptr; double* part = nullptr; FilmBlockArgs* dev = nullptr; bool narrow = false; std::vector<double> host;
+             std::vector<long long> steps; } integ;
     // weighted film integrals (api_weighted.inc): recording stride (0: not armed) and number of weight planes K; the planes on the
     // device in this handle's Layout ([K] planes, pitch and offset as topo's, ghost cells zero), the row scratch ([K][Nx][9]) and the
     // device records of the batch in flight ([log_cap + 1][K][9]), all allocated by gpf_weighted_set (`narrow`: GPF_FILM_NARROW was
@@ -382,7 +384,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->integ.dev, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -1038,6 +1040,7 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
     a.log = h->log; a.log_base = log_base; a.log_cap = h->log_cap; a.L = L; a.E = h->E; a.nsteps = nsteps; a.honor_stop = honor_stop;
     a.probe = h->probes.n ? h->probes.dev : nullptr;
     a.extrema = h->extr.every ? h->extr.dev : nullptr;
+    a.film = h->integ.every ? h->integ.dev : nullptr;       // (null while armed: a diagnostic that did not go through integrals_begin; it records none)
     const size_t lds = (size_t)(L.Nx + 2) * (L.Ny + 2) * SMALL_DOUBLES_PER_CELL * 8;
     EOS_DISPATCH(h->cfg.eos, {
         if (h->Ls) {

@@ -5,6 +5,9 @@
 //
 // A member is a handle of its own, borrowed: everything a solo gpf_step of the same count would leave in it -- buffers, run
 // state, log, host_step / next_step, prev_state_valid, g1_ready -- is left in it here, so that it can go on alone.
+//
+// Film-integral series (gpf_ensemble_integrals_*) belong to the ENSEMBLE, not to its members: both kernels record them inside
+// the batch (integral_kernels.hip: film_record_block) into per-member slots that the ensemble owns, so nothing cuts a launch.
 
 struct gpf_ensemble {
     std::vector<gpf_handle*> members;
@@ -20,6 +23,19 @@ struct gpf_ensemble {
     std::vector<int> tier;                  // per member: GPF_ENSEMBLE_TIER_LDS / _WORKSPACE, fixed at create
     std::vector<long long> ws_off;          // per member of the workspace tier: where its workspace starts in `ws`, in bytes
     char* ws = nullptr;                     // one device allocation for all workspaces (mid_layout.hpp)
+    // film-integral series: stride (0: not armed); per member its sections, doubles per record and where its records start in
+    // `rec` (one device allocation, `cap` records per member: what a call of at most LOG_CAPACITY steps can leave at the stride);
+    // the members' FilmBlockArgs in device memory ([m]); the records of the last gpf_ensemble_step and their step counts on the host
+    struct Film {
+        long long every = 0, cap = 0;
+        std::vector<FilmBlockArgs> args;
+        std::vector<size_t> off;
+        double* rec = nullptr;
+        FilmBlockArgs* dev = nullptr;
+        std::vector<std::vector<double>> host;
+        std::vector<std::vector<long long>> steps;
+        int nrec(int i) const { return FILM_NSUM + args[i].nsx + args[i].nsy; }
+    } film;
     size_t args_off() const { return members.size() * sizeof(StepState); }
     size_t bytes() const { return args_off() + members.size() * (sizeof(SmallArgs) + sizeof(Phys) + sizeof(double*)); }
 };
@@ -101,6 +117,9 @@ extern "C" int gpf_ensemble_destroy(gpf_ensemble* e) {
     if (!e) return GPF_OK;
     for (gpf_handle* h : e->members) ensemble_members_drop(h, false);
     hipSetDevice(e->device);
+    hipStreamSynchronize(e->members[0]->stream);        // a launch that records into the buffers below may still be queued
+    if (e->film.rec) hipFree(e->film.rec);
+    if (e->film.dev) hipFree(e->film.dev);
     if (e->dev) hipFree(e->dev);
     if (e->ws) hipFree(e->ws);
     if (e->host) hipHostFree(e->host);
@@ -132,6 +151,7 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
     for (int i = 0; i < m; ++i) {
         e->entries[i] = 0;
         if (n[i] > 0) slots.push_back(i);
+        if (e->film.every) { e->film.host[i].clear(); e->film.steps[i].clear(); }      // the records of the call before go
     }
     std::stable_sort(slots.begin(), slots.end(), [&](int a, int b) { return key(a) < key(b); });
     const int nslots = (int)slots.size();
@@ -151,6 +171,7 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
         a.log = h->log; a.log_base = h->host_step; a.log_cap = h->log_cap; a.L = h->L; a.E = h->E;
         a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop; a.probe = nullptr; a.extrema = nullptr;
+        a.film = e->film.every ? e->film.dev + slots[s] : nullptr;
         hp[s] = h->P;
         hw[s] = e->tier[slots[s]] == GPF_ENSEMBLE_TIER_WORKSPACE ? (double*)(e->ws + e->ws_off[slots[s]]) : nullptr;
     }
@@ -205,6 +226,17 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         const StepState& st = hs[s];
         const long long ran = st.step - h->host_step;
         e->entries[i] = ran + ((st.invalid && ran < n[i]) ? 1 : 0);
+        // the member's film records: the multiples of the stride in (base, base + ran], by its own ran (a member that stopped on
+        // the device ran a prefix of its steps; a rolled-back step left none)
+        const long long cnt = e->film.every ? integrals_count(h->host_step, ran, e->film.every) : 0;
+        if (cnt > 0) {
+            const size_t nrec = (size_t)e->film.nrec(i);
+            std::vector<double> got((size_t)cnt * nrec);
+            if (hip_ok(hipMemcpy(got.data(), e->film.rec + e->film.off[i], got.size() * sizeof(double), hipMemcpyDeviceToHost), "film record copy")) {
+                e->film.host[i].swap(got);
+                for (long long k = 1; k <= cnt; ++k) e->film.steps[i].push_back((h->host_step / e->film.every + k) * e->film.every);
+            }
+        }
         h->host_step = st.step; h->next_step = st.step;
         h->prev_state_valid = ran >= 1 && !st.invalid;
         h->g1_ready = false;
@@ -249,5 +281,85 @@ extern "C" int gpf_ensemble_log(gpf_ensemble* e, int member, gpf_scalars_t* log,
         HIP_TRY(hipSetDevice(e->device));
         HIP_TRY(hipMemcpy(log, h->log, (size_t)take * sizeof(LogEntry), hipMemcpyDeviceToHost));
     }
+    return GPF_OK;
+}
+
+static int ensemble_film_release(gpf_ensemble* e) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->members[0]->stream));       // a recording launch may still be queued
+    if (e->film.rec) HIP_TRY(hipFree(e->film.rec));
+    e->film.rec = nullptr;
+    if (e->film.dev) HIP_TRY(hipFree(e->film.dev));
+    e->film.dev = nullptr;
+    e->film = gpf_ensemble::Film();
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_integrals_set(gpf_ensemble* e, int64_t every, int nsx, const int32_t* ix, int nsy, const int32_t* iy) {
+    if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_set: null argument");
+    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_set: every >= 1 required (gpf_ensemble_integrals_clear disarms), got " + std::to_string(every));
+    if (nsx > FILM_MAX_SECTIONS || nsy > FILM_MAX_SECTIONS)
+        return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_set: " + std::to_string(std::max(nsx, nsy)) + " sections given, at most " +
+                                     std::to_string(FILM_MAX_SECTIONS) + " per direction");
+    const int m = (int)e->members.size();
+    // explicit sections are the same for everyone: they must lie inside every member's interior
+    for (int i = 0; i < m; ++i) {
+        const gpf_handle* h = e->members[i];
+        const std::string who = "gpf_ensemble_integrals_set: member " + std::to_string(i);
+        GPF_TRY(integrals_refusal(h, who));
+        for (int k = 0; ix && k < nsx; ++k)
+            if (ix[k] < 1 || ix[k] > h->L.Nx)
+                return fail(GPF_ERR_INVALID, who + ": x-section " + std::to_string(k) + " at row " + std::to_string(ix[k]) +
+                                             " lies outside its interior rows 1.." + std::to_string(h->L.Nx));
+        for (int k = 0; iy && k < nsy; ++k)
+            if (iy[k] < 1 || iy[k] > h->L.Ny)
+                return fail(GPF_ERR_INVALID, who + ": y-section " + std::to_string(k) + " at column " + std::to_string(iy[k]) +
+                                             " lies outside its interior columns 1.." + std::to_string(h->L.Ny));
+    }
+    GPF_TRY(ensemble_film_release(e));
+    gpf_ensemble::Film f;
+    f.every = every;
+    f.cap = LOG_CAPACITY / every + 1;               // integrals_count(base, ran, every) <= ran / every + 1
+    f.args.resize(m); f.off.resize(m); f.host.resize(m); f.steps.resize(m);
+    size_t total = 0;
+    for (int i = 0; i < m; ++i) {
+        const gpf_handle* h = e->members[i];
+        // default: first and last interior row / column, one where the extent is 1 (integrals_default_sections)
+        int sx[FILM_MAX_SECTIONS] = {1, h->L.Nx}, sy[FILM_MAX_SECTIONS] = {1, h->L.Ny};
+        int mx = h->L.Nx > 1 ? 2 : 1, my = h->L.Ny > 1 ? 2 : 1;
+        if (ix && nsx > 0) { mx = nsx; for (int k = 0; k < nsx; ++k) sx[k] = ix[k]; }
+        if (iy && nsy > 0) { my = nsy; for (int k = 0; k < nsy; ++k) sy[k] = iy[k]; }
+        f.args[i] = film_block_args(nullptr, every, f.cap, h->cfg.dx, h->cfg.dy, mx, sx, my, sy);
+        f.off[i] = total;
+        total += (size_t)f.cap * (size_t)(FILM_NSUM + mx + my);
+    }
+    hipError_t err = hipMalloc(&f.rec, total * sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&f.dev, (size_t)m * sizeof(FilmBlockArgs));
+    for (int i = 0; i < m; ++i) f.args[i].rec = f.rec ? f.rec + f.off[i] : nullptr;
+    if (err == hipSuccess) err = hipMemcpy(f.dev, f.args.data(), (size_t)m * sizeof(FilmBlockArgs), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {
+        if (f.rec) (void)hipFree(f.rec);
+        if (f.dev) (void)hipFree(f.dev);
+        return fail(GPF_ERR_HIP, std::string("gpf_ensemble_integrals_set: ") + hipGetErrorString(err));
+    }
+    e->film = std::move(f);
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_integrals_clear(gpf_ensemble* e) {
+    if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_clear: null argument");
+    return ensemble_film_release(e);
+}
+
+extern "C" int gpf_ensemble_integrals_read(gpf_ensemble* e, int member, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
+    if (!e || !n_records) return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_read: null argument (e and n_records are required)");
+    if (member < 0 || member >= (int)e->members.size())
+        return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_read: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    if (!e->film.every) return fail(GPF_ERR_STATE, "gpf_ensemble_integrals_read: no integrals are armed (gpf_ensemble_integrals_set)");
+    const size_t nrec = (size_t)e->film.nrec(member);
+    const int64_t have = (int64_t)e->film.steps[member].size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
+    *n_records = have;
+    if (out && take > 0) std::memcpy(out, e->film.host[member].data(), (size_t)take * nrec * sizeof(double));
+    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = e->film.steps[member][(size_t)k];
     return GPF_OK;
 }

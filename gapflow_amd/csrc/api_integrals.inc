@@ -1,6 +1,8 @@
 // Part of api.hip (included there, not compiled on its own): whole-film integrals -- load, its moments, the pressure's push on
 // the profiled wall, wall friction and flow rates through cross-sections -- reduced on the device behind the committed steps
 // whose count is a multiple of the armed stride, and handed out once per call.  Kernels: integral_kernels.hip.
+// A handle that steps through k_small_steps records inside the batch (film_record_block, told where by integ.dev): same buffer,
+// same slots, same bits, no launch.
 
 // Records a stepping call leaves for the steps (base, base + ran]: the multiples of `every` among them.
 static long long integrals_count(long long base, long long ran, long long every) {
@@ -37,7 +39,15 @@ static bool film_wide_ok(const gpf_handle* h) {
            (!h->Ls || a16(h->Ls)) && !h->integ.narrow;
 }
 
-// The record buffer (log_cap slots for a batch + one for gpf_integrals_now) and the row scratch, on first use
+static FilmBlockArgs film_block_args(double* rec, long long every, long long cap, double dx, double dy, int nsx, const int* sx, int nsy, const int* sy) {
+    FilmBlockArgs b;
+    b.rec = rec; b.every = every; b.cap = cap; b.dx = dx; b.dy = dy; b.nsx = nsx; b.nsy = nsy;
+    for (int k = 0; k < FILM_MAX_SECTIONS; ++k) { b.sx[k] = k < nsx ? sx[k] : 1; b.sy[k] = k < nsy ? sy[k] : 1; }
+    return b;
+}
+
+// The record buffer (log_cap slots for a batch + one for gpf_integrals_now) and the row scratch, on first use; armed, also the
+// arguments' copy in device memory that k_small_steps reads
 static int integrals_buffers(gpf_handle* h) {
     if (!h->integ.nsx) integrals_default_sections(h);
     if (!h->integ.part) {
@@ -45,6 +55,14 @@ static int integrals_buffers(gpf_handle* h) {
         HIP_TRY(hipMalloc(&h->integ.part, (size_t)h->L.Nx * FILM_NV * sizeof(double)));
     }
     if (!h->integ.rec) HIP_TRY(hipMalloc(&h->integ.rec, (size_t)(h->log_cap + 1) * integrals_nrec(h) * sizeof(double)));
+    if (!h->integ.dev && h->integ.every) {      // what k_small_steps records by: stride and sections are fixed until gpf_integrals_set / _clear frees this
+        FilmBlockArgs b = film_block_args(h->integ.rec, h->integ.every, h->log_cap, h->cfg.dx, h->cfg.dy, h->integ.nsx, h->integ.sx, h->integ.nsy, h->integ.sy);
+        FilmBlockArgs* dev = nullptr;
+        HIP_TRY(hipMalloc(&dev, sizeof(b)));
+        hipError_t e = hipMemcpy(dev, &b, sizeof(b), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(dev); HIP_TRY(e); }
+        h->integ.dev = dev;
+    }
     return GPF_OK;
 }
 
@@ -103,6 +121,8 @@ static int integrals_release(gpf_handle* h) {
     h->integ.rec = nullptr;
     if (h->integ.part) HIP_TRY(hipFree(h->integ.part));
     h->integ.part = nullptr;
+    if (h->integ.dev) HIP_TRY(hipFree(h->integ.dev));
+    h->integ.dev = nullptr;
     h->integ.every = 0; h->integ.nsx = h->integ.nsy = 0;
     h->integ.host.clear(); h->integ.steps.clear();
     return GPF_OK;
@@ -147,6 +167,12 @@ extern "C" int gpf_integrals_read(gpf_handle* h, double* out, int64_t capacity_r
     if (n_records) *n_records = have;
     if (out && take > 0) std::memcpy(out, h->integ.host.data(), (size_t)take * nrec * sizeof(double));
     for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = h->integ.steps[(size_t)k];
+    return GPF_OK;
+}
+
+extern "C" int gpf_integrals_in_batch(gpf_handle* h, int* yes) {
+    if (!h || !yes) return fail(GPF_ERR_INVALID, "gpf_integrals_in_batch: null argument");
+    *yes = h->integ.every && small_grid_eligible(h) ? 1 : 0;
     return GPF_OK;
 }
 

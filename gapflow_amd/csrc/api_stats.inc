@@ -102,19 +102,18 @@ static int stats_release(gpf_handle* h) {
     return GPF_OK;
 }
 
-// A batch of the small-grid kernel, cut at the union of the steps that the series which cut it record (film integrals, weighted
-// integrals, regions, lines, statistics), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
+// A batch of the small-grid kernel, cut at the union of the steps that the series which cut it record (weighted integrals,
+// regions, lines, statistics), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
 // batch in pieces is bitwise the batch in one: every piece starts from the state and the run state the piece before left.
-// With none of them armed this is the one launch.
+// With none of them armed this is the one launch.  Probes, extrema and film integrals do not cut: k_small_steps records them.
 static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base) {
     const long long end = base + batch;
     for (long long at = base; at < end;) {
         long long next = end;
-        for (long long every : {h->integ.every, h->weighted.every, h->regions.every, h->lines.every})
+        for (long long every : {h->weighted.every, h->regions.every, h->lines.every})
             if (every) next = std::min(next, (at / every + 1) * every);
         if (h->stats.every) next = std::min(next, (std::max(at, stats_floor(h)) / h->stats.every + 1) * h->stats.every);
         GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
-        GPF_TRY(integrals_launch(h, next, base));
         GPF_TRY(weighted_launch(h, next, base));
         GPF_TRY(regions_launch(h, next, base));
         GPF_TRY(lines_launch(h, next, base));

@@ -30,13 +30,15 @@ struct MidCursor {
 };
 
 // The whole batch of one member on one workgroup of 512 threads.  The workgroup's only stores to global memory go to its own
-// workspace `ws`, a.qa, a.qb, a.st and a.log.  Probes and extrema are not recorded here (gpf_ensemble_create refuses members
-// that have them armed).  Returns the run state the batch ended on (in LDS; thread 0 alone may read it without a barrier).
+// workspace `ws`, a.qa, a.qb, a.st, a.log and the film records (a.film: film_record_block, whose row vectors pass through the
+// workspace's flux planes under the barriers' release / acquire like everything else here).  Probes and extrema are not recorded
+// here (gpf_ensemble_create refuses members that have them armed).  Returns the run state the batch ended on (in LDS; thread 0 alone may read it without a barrier).
 template <int EOS, bool HAS_LS>
 __device__ __forceinline__ const StepState* mid_steps_body(const SmallArgs& a, const Phys& P, double* ws) {
     __shared__ Acc sm[16];
     __shared__ int sh_flags[2];
     __shared__ StepState sst;                       // the run state stays on-chip for the whole batch
+    __shared__ double film_sm[4][FILM_NV];          // film_record_block's wave staging
     const Layout& G = a.L;                          // layout of the member's own planes
     const int w = G.Ny + 2, nc = (G.Nx + 2) * w;
     Layout D;                                       // dense layout of the workspace planes
@@ -92,6 +94,8 @@ __device__ __forceinline__ const StepState* mid_steps_body(const SmallArgs& a, c
     };
 
     int committed = 0;                              // steps this launch has committed (block-uniform)
+    FilmCursor film;
+    if (a.film) film.begin(a.film, st->step, a.log_base);
     for (int step = 0; step < a.nsteps; ++step) {
         if (st->invalid != 0 || (a.honor_stop && (st->converged || st->step >= st->max_it))) break;     // block-uniform
         const double dt = st->dt;
@@ -149,6 +153,10 @@ __device__ __forceinline__ const StepState* mid_steps_body(const SmallArgs& a, c
         if (sh_flags[1]) break;                     // rolled back: q0 still holds the last valid state
         double* tmp = q0; q0 = q2; q2 = tmp;        // the averaged field is the current one now, q2 the state before this step
         committed += 1;
+        if (a.film && film.due(st->step)) {             // block-uniform; F is free until the next closure pass
+            film_record_block<EOS>(a.film, q0, T, F, film_sm, D.Nx, D.Ny, nc, w, film.slot, P);
+            film.advance();
+        }
     }
     // the current state -> the buffer the (final) parity designates, the state before the last committed step -> the other one
     // (where the launch-per-step kernels leave it too); the run state back to global memory

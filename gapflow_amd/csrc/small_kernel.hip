@@ -21,10 +21,11 @@ struct SmallArgs {
     int nsteps, honor_stop;
     const ProbeArgs* probe; // point probes (probe_kernels.hip), in device memory; null: none
     const ExtremaArgs* extrema;     // field extrema (extrema_kernels.hip), in device memory; null: none
+    const FilmBlockArgs* film;      // film integrals (integral_kernels.hip: film_record_block), in device memory; null: none
 };
 
 // The whole batch of one problem on one workgroup of 512 threads: the body of both kernels below.  Nothing in it reaches
-// beyond `a` and `P`: the workgroup's only stores to global memory go to a.qa, a.qb, a.st, a.log (and the probe and extrema records).
+// beyond `a` and `P`: the workgroup's only stores to global memory go to a.qa, a.qb, a.st, a.log (and the probe, extrema and film records).
 // Returns the run state the batch ended on (in LDS, written by thread 0, which alone may read it without a barrier).
 template <int EOS, bool HAS_LS>
 __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a, const Phys& P) {
@@ -32,6 +33,7 @@ __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a,
     __shared__ Acc sm[16];
     __shared__ int sh_flags[2];
     __shared__ StepState sst;                       // the run state stays on-chip for the whole batch
+    __shared__ double film_sm[4][FILM_NV];          // film_record_block's wave staging
     const Layout& G = a.L;                          // layout of the global planes
     const int w = G.Ny + 2, nc = (G.Nx + 2) * w;
     Layout D;                                       // dense layout of the LDS planes
@@ -88,6 +90,8 @@ __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a,
     int committed = 0;                              // steps this launch has committed (block-uniform)
     ExtremaCursor ext;
     if (a.extrema) ext.begin(a.extrema, st->step, a.log_base);
+    FilmCursor film;
+    if (a.film) film.begin(a.film, st->step, a.log_base);
     for (int step = 0; step < a.nsteps; ++step) {
         if (st->invalid != 0 || (a.honor_stop && (st->converged || st->step >= st->max_it))) break;     // block-uniform
         const double dt = st->dt;
@@ -154,6 +158,10 @@ __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a,
         if (a.extrema && ext.due(st->step)) {           // likewise, at the armed stride
             extrema_record_block<EOS>(ext.x, q0, T, D.Nx, D.Ny, nc, w, ext.slot, P);
             ext.advance();
+        }
+        if (a.film && film.due(st->step)) {             // likewise; the row vectors go through F, dead until the next closure pass
+            film_record_block<EOS>(a.film, q0, T, F, film_sm, D.Nx, D.Ny, nc, w, film.slot, P);
+            film.advance();
         }
     }
     // the current state -> the buffer the (final) parity designates; the run state back to global memory

@@ -3,8 +3,10 @@ the reference runs a parameter study -- three eccentricities of the Sommerfeld t
 process per problem).  DESIGN.md 3.2c.
 
     ens = Ensemble.sweep("journal1d.yaml", {'geometry.eps': [0.5, 0.7, 0.9], 'geometry.U': [0.05, 0.1]})
+    ens.set_integrals(every=10)                 # load, friction and flow histories, recorded inside the launches
     ens.run()
     loads = [r['load'] for r in ens.film_integrals()]
+    history = [s.load for s in ens.integrals]
 
 An ensemble HOLDS its `Problem` objects, it does not copy them: after `run()` or `step()` every member is, bit for bit, what
 the same call on it alone would have made it (`q`, `step`, `simtime`, `dt`, `residual`, `residual_buffer`, `history`, derived
@@ -27,7 +29,8 @@ from datetime import datetime
 import numpy as np
 
 from . import _lib
-from .problem import Problem, _in_main_thread, _termination_signals
+from .problem import (FilmIntegrals, Problem, _in_main_thread, _integral_records, _integral_sections, _integral_stride,
+                      _termination_signals)
 
 
 def member_tier(nx, ny):
@@ -145,6 +148,7 @@ class Ensemble:
                                  "(one launch needs one device)")
         self.problems = problems
         self.parameters = None              # sweep(): what each member got, {dotted key: value}
+        self._integral_every = None         # set_integrals: the stride, per member its sections and its series
         self._lib = problems[0]._lib
         self._e = C.c_void_p()
         handles = (C.c_void_p * len(problems))(*[p._h.value for p in problems])
@@ -225,6 +229,7 @@ class Ensemble:
             _lib.check(self._lib.gpf_ensemble_log(self._e, i, log, n, None))
             before = p.step
             out.append(p._absorb_batch(log, n, int(nexec[i]) - before, before))
+            self._collect_integrals(i, out[-1], before)
         return out
 
     def step(self, n):
@@ -262,6 +267,8 @@ class Ensemble:
                 if running[i] and not p._run_active():
                     running[i] = False
                     p._run_end(cfs[i], keep_open)
+                    if self._integral_every is not None and not keep_open and not p.options['silent']:
+                        np.savez(os.path.join(p.outdir, 'integrals.npz'), **self._member_integrals(i)._asdict())
 
         try:
             retire()
@@ -275,6 +282,73 @@ class Ensemble:
         finally:
             for s, hdl in old.items():
                 signal.signal(s, hdl)
+
+    # -------------------------------------------------------------------------------------
+    # film-integral series
+    # -------------------------------------------------------------------------------------
+    def set_integrals(self, every=1, sections_x=None, sections_y=None):
+        """Record `Problem.set_integrals`' record for EVERY member after each of its committed steps whose count is a multiple
+        of `every`, inside the ensemble's launches: both one-workgroup kernels write it after the step's commit, bit for bit what
+        `film_integrals()` gives for the same state, and no launch is cut.  sections_x / sections_y: None for each member's first
+        and last interior row / column; a list holds for all members and must lie inside every member's interior (ValueError
+        naming the member otherwise).  Starts new series (see ``integrals``).  A member that has `set_integrals` armed on itself
+        is still refused; the members' own `integrals` stay None."""
+        every = _integral_stride(every)
+        layout = []
+        for i, p in enumerate(self.problems):
+            try:
+                layout.append((_integral_sections(sections_x, p.grid['Nx'], 'sections_x'), _integral_sections(sections_y, p.grid['Ny'], 'sections_y')))
+            except ValueError as err:
+                raise ValueError(f"Ensemble.set_integrals: member {i}: {err}") from None
+        i32p = C.POINTER(C.c_int32)
+        ax = np.array(sections_x if sections_x is not None else [], dtype=np.int32)
+        ay = np.array(sections_y if sections_y is not None else [], dtype=np.int32)
+        _lib.check(self._lib.gpf_ensemble_integrals_set(self._e, every, len(ax), ax.ctypes.data_as(i32p) if len(ax) else None,
+                                                        len(ay), ay.ctypes.data_as(i32p) if len(ay) else None))
+        self._integral_every, self._integral_sections = every, layout
+        self._integral_series = [([], [], []) for _ in self.problems]       # per member: steps, times, record blocks
+
+    def clear_integrals(self):
+        """Stop recording and drop the series."""
+        if self._integral_every is not None:
+            _lib.check(self._lib.gpf_ensemble_integrals_clear(self._e))
+        self._integral_every = None
+
+    def _collect_integrals(self, i, entries, before):
+        """Member i's records of the call that took its step count from `before` through `entries` (its committed steps)."""
+        if self._integral_every is None or not entries:
+            return
+        every = self._integral_every
+        n = _integral_records(before, len(entries), every)
+        sx, sy = self._integral_sections[i]
+        out = np.empty((n, len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy)))
+        steps = np.zeros(n, dtype=np.int64)
+        have = C.c_int64(0)
+        _lib.check(self._lib.gpf_ensemble_integrals_read(self._e, i, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
+        want = [s for s in range(before + 1, before + len(entries) + 1) if s % every == 0]
+        if have.value != n or steps.tolist() != want:
+            raise _lib.GapflowHipError(f"Ensemble integrals: member {i}: {have.value} records of steps {steps.tolist()} for the committed "
+                                       f"steps {before + 1}..{before + len(entries)} at stride {every}")
+        series = self._integral_series[i]
+        series[0].extend(want)
+        series[1].extend(entries[s - before - 1].simtime for s in want)
+        series[2].append(out)
+
+    def _member_integrals(self, i):
+        sx, sy = self._integral_sections[i]
+        steps, times, blocks = self._integral_series[i]
+        ns = len(_lib.INTEGRAL_SUMS)
+        data = np.concatenate(blocks) if blocks else np.empty((0, ns + len(sx) + len(sy)))
+        return FilmIntegrals(np.array(steps, dtype=np.int64), np.array(times, dtype=np.float64), *[data[:, k] for k in range(ns)],
+                             data[:, ns:ns + len(sx)], data[:, ns + len(sx):], np.array(sx, dtype=np.int64), np.array(sy, dtype=np.int64))
+
+    @property
+    def integrals(self):
+        """One FilmIntegrals(step, time, load, ..., flow_x, flow_y, sections_x, sections_y) per member -- `Problem.integrals`'
+        type -- of every recorded step since set_integrals, across `step()` and `run()` calls; None when none are armed."""
+        if self._integral_every is None:
+            return None
+        return [self._member_integrals(i) for i in range(len(self.problems))]
 
     # -------------------------------------------------------------------------------------
     # views

@@ -616,7 +616,7 @@ class Problem:
         sum_ix jy h dx on interior column sections_y[k] (at most 8 each; default: first and last interior row / column).
         These are plain integrals of the named fields: NO sign convention (outward normals, which wall acts on which) is applied.
         The same state gives the same bits whatever the batch size or stride.  On grids small enough for the one-workgroup
-        kernel the batch is cut at every recorded step: choose a stride there (every=1 costs one launch per step).
+        kernel the record is written inside the batch (``integrals_in_batch``): no launch is cut, whatever the stride.
         A step that is rolled back as invalid leaves no record.  Starts a new series (see ``integrals``).  Checkpoints do not
         carry the series: a problem restored from one whose options hold `integrals` has them armed again and its series
         begins at the restart step.  Not available with surrogate closures, shear thinning or an elastic gap."""
@@ -635,6 +635,14 @@ class Problem:
         if self._integral_every is not None:
             _lib.check(self._lib.gpf_integrals_clear(self._h))
         self._integral_every = None
+
+    @property
+    def integrals_in_batch(self):
+        """True where the armed film integrals are recorded inside the one-workgroup kernel's batch (small grids), False where
+        two launches behind every recorded step write them, and when none are armed."""
+        yes = C.c_int(0)
+        _lib.check(self._lib.gpf_integrals_in_batch(self._h, C.byref(yes)))
+        return bool(yes.value)
 
     def _integral_layout(self):
         if self._integral_every is not None:

@@ -462,8 +462,10 @@ int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms);
  *                        sections), by the same two kernels; `count`: doubles `out` holds.
  * Where they are written: k_film_partial + k_film_fold (csrc/integral_kernels.hip) behind the step's launch, told the step
  * count the step produces if it commits and writing only if the device's run state shows that count and a valid state.  On
- * grids small enough for k_small_steps the batch is cut at the recorded steps (bitwise the same run): with every = 1 that is
- * one launch per step again, so choose a stride there.  gpf_close_step, gpf_step_timed and the slab calls record nothing.  The
+ * grids small enough for k_small_steps the record is written INSIDE the batch, after the step's commit, by film_record_block
+ * (same file): one workgroup replays the two kernels' summation order on the planes it holds and leaves the same bits in the
+ * same slot, so the batch is not cut and a stride costs no launch (gpf_integrals_in_batch tells which path a handle takes).
+ * gpf_close_step, gpf_step_timed and the slab calls record nothing.  The
  * record buffer ((log_cap + 1) records) and a row scratch (Nx x 18 doubles) are allocated on first use and freed by
  * gpf_integrals_clear / gpf_destroy once the stream is idle.  k_film_partial fetches two columns with one 16-byte load per
  * plane where the layout and the buffers are aligned for it (always, today) and with 8-byte loads otherwise, adding in the same
@@ -473,6 +475,9 @@ int gpf_integrals_set(gpf_handle* h, int64_t every, int nsx, const int32_t* ix, 
 int gpf_integrals_clear(gpf_handle* h);
 int gpf_integrals_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
 int gpf_integrals_now(gpf_handle* h, double* out, int64_t count);
+/* *yes = 1 if this handle, as it stands, records its film integrals inside k_small_steps' batch (armed, and the handle steps
+ * through the one-workgroup kernel), else 0: the two-launch path behind every recorded step.  GPF_ERR_INVALID for a NULL. */
+int gpf_integrals_in_batch(gpf_handle* h, int* yes);
 /* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
  * mode 0 no recording (armed integrals are put aside for the call), 1 recording at the armed stride (tools/integrals_time.py).
  * Probes are put aside in both modes. */
@@ -777,7 +782,24 @@ int gpf_lines_time(gpf_handle* h, int64_t n, int mode, double* ms);
  *   gpf_ensemble_limits2  likewise for the workspace tier: the most cells, ghost cells included, and the doubles per cell of a
  *                         workspace (which is that many doubles per cell, rounded up to 256 bytes).
  *   gpf_ensemble_member_info  the tier member `member` got (GPF_ENSEMBLE_TIER_*) and the bytes of its workspace (0 in the LDS
- *                         tier); either pointer may be NULL. */
+ *                         tier); either pointer may be NULL.
+ * Film-integral series of an ensemble (the record of gpf_integrals_*: nine sums, flow_x, flow_y).  They belong to the ensemble,
+ * not to its members -- a member with gpf_integrals_set armed on itself is still refused -- and both kernels write them inside
+ * the batch (csrc/integral_kernels.hip: film_record_block), in either tier bit for bit what gpf_integrals_now gives for the same
+ * state, without cutting a launch:
+ *   gpf_ensemble_integrals_set    arms recording, for every member, after each of ITS committed steps whose new count is a
+ *                         multiple of `every` (>= 1), and starts with empty records.  ix / iy NULL (or nsx / nsy <= 0): per
+ *                         member its first and last interior row / column (one where the extent is 1).  Explicit sections
+ *                         hold for all members and must lie inside every member's interior: GPF_ERR_INVALID with a message that
+ *                         names the member and the section otherwise, and for every < 1 or more than 8 sections; nothing is
+ *                         changed then.  Allocates, per member, LOG_CAPACITY / every + 1 records and its arguments on the device.
+ *   gpf_ensemble_integrals_clear  disarms and frees them.
+ *   gpf_ensemble_integrals_read   the records member `member` left in the LAST gpf_ensemble_step, [record][9 + nsx + nsy], and
+ *                         the step count of each in steps_out (either may be NULL); *n_records (required) how many -- the
+ *                         multiples of the stride among the steps the member committed in that call, by its own count: a
+ *                         member that stopped on the device leaves those of the steps that ran, a rolled-back step none, a
+ *                         member with n[i] = 0 none --, min(*n_records, capacity_records) are copied.  GPF_ERR_STATE unless
+ *                         armed. */
 #define GPF_ENSEMBLE_FORCE_WORKSPACE 1
 enum { GPF_ENSEMBLE_TIER_LDS = 0, GPF_ENSEMBLE_TIER_WORKSPACE = 1 };
 typedef struct gpf_ensemble gpf_ensemble;
@@ -789,6 +811,9 @@ int gpf_ensemble_limits(int64_t* lds_bytes, int32_t* doubles_per_cell, int64_t* 
 int gpf_ensemble_create2(gpf_handle* const* members, int m, int flags, gpf_ensemble** out);
 int gpf_ensemble_limits2(int64_t* mid_max_cells, int32_t* mid_doubles_per_cell);
 int gpf_ensemble_member_info(gpf_ensemble* e, int member, int32_t* tier, int64_t* workspace_bytes);
+int gpf_ensemble_integrals_set(gpf_ensemble* e, int64_t every, int nsx, const int32_t* ix, int nsy, const int32_t* iy);
+int gpf_ensemble_integrals_clear(gpf_ensemble* e);
+int gpf_ensemble_integrals_read(gpf_ensemble* e, int member, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
 
 /* ---- resampling a state onto another grid (no reference counterpart) ------------------------------- */
 /* dst's state from src's committed state, both covering the same domain with different (Nx, Ny): bilinear interpolation, over
