@@ -210,6 +210,7 @@ struct gpf_handle {
     StepState* st_trial = nullptr;          // plan_step2's timing launches commit into this copy of the run state
     double* plan_master = nullptr;          // copy of the current state while plan_step2 runs its trials
     char plan2_note[400] = "";              // how the plan was arrived at (gpf_plan_note)
+    int step_variant[5] = {-1, -1, -1, 0, -1};  // what the last launch of a step passed to step2_kernel() (gpf_step_variant)
 };
 
 static int enter(gpf_handle* h, bool reads_only) {
@@ -853,6 +854,21 @@ static step2_kernel_t step2_kernel(int eos, bool has_ls, bool piezo, int D, int 
     return k;
 }
 
+// The instantiation a STEP launches (enqueue_step): the arguments go to step2_kernel() from the record gpf_step_variant reports,
+// so the report cannot differ from what ran.  The plan's trial launches pick theirs without it.
+static step2_kernel_t step2_kernel_of_step(gpf_handle* h, int D) {
+    int* v = h->step_variant;
+    v[0] = h->cfg.eos; v[1] = h->Ls != nullptr ? 1 : 0; v[2] = h->cfg.piezo != 0 ? 1 : 0; v[3] = D; v[4] = topo_mode_of(h);
+    return step2_kernel(v[0], v[1] != 0, v[2] != 0, v[3], v[4]);
+}
+
+extern "C" int gpf_step_variant(gpf_handle* h, int out[5]) {
+    if (!h || !out) return fail(GPF_ERR_INVALID, "gpf_step_variant: bad argument");
+    if (h->step_variant[0] < 0) return fail(GPF_ERR_STATE, "gpf_step_variant: this handle has not launched the fused step kernel yet");
+    for (int k = 0; k < 5; ++k) out[k] = h->step_variant[k];
+    return GPF_OK;
+}
+
 // Window geometry of k_step2 for predictor direction D (see Strip2Geom).  Logical column m sits at physical column
 // iy = m (D > 0) or Ny+1-m (D < 0), i.e. at element off + iy of its row with off = 15: a lane's pair must start on an
 // odd physical column.  D > 0: w0 odd.  D < 0: the pair (m, m+1) starts at iy = Ny - m, odd iff m and Ny differ in
@@ -973,7 +989,7 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
     const bool has_ls = h->Ls != nullptr;
     if (fused) {
         // the whole step in one launch (step2_kernel.hip)
-        const step2_kernel_t k2 = step2_kernel(h->cfg.eos, h->Ls != nullptr, h->cfg.piezo != 0, D, topo_mode_of(h));
+        const step2_kernel_t k2 = step2_kernel_of_step(h, D);
         if (ev0) hipEventRecord(ev0, h->stream);
         hipLaunchKernelGGL(k2, dim3(h->nblocks2), dim3(256), 0, h->stream, a2, h->P);
         if (ev1) hipEventRecord(ev1, h->stream);
@@ -993,7 +1009,7 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
             else LS_PIEZO_DISPATCH(has_ls, h->cfg.piezo != 0, hipLaunchKernelGGL((k_ghost_stage1<EOS_, LS_, PZ_, false>), ggrid, dim3(256), 0, h->stream, g, h->P));
         }
         if (ev0) hipEventRecord(ev0, h->stream);
-        hipLaunchKernelGGL(step2_kernel(h->cfg.eos, h->Ls != nullptr, h->cfg.piezo != 0, D, topo_mode_of(h)), dim3(h->nblocks2), dim3(256), 0, h->stream, a2, h->P);
+        hipLaunchKernelGGL(step2_kernel_of_step(h, D), dim3(h->nblocks2), dim3(256), 0, h->stream, a2, h->P);
         if (ev1) hipEventRecord(ev1, h->stream);
         hipLaunchKernelGGL((k_ghost_fill<EOS_>), dim3(h->nghost_blocks + nsend), dim3(256), 0, h->stream, gf, f, h->nghost_blocks, h->P);
         if (p2p) {                          // wait for the peers, commit, stage-1 ghost data of the next step

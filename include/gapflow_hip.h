@@ -155,6 +155,12 @@ const char* gpf_plan_note(gpf_handle* h);
  * GPF_ERR_STATE unless the handle holds a table: the gap varies along x only, no slip-length field or piezo-viscosity, and
  * GPF_ROWCOEF_TABLE was not 0 at gpf_create (the step kernel then evaluates the coefficients itself, as before the table). */
 int gpf_row_coefficients(gpf_handle* h, int source, double* host, size_t count);
+/* Which instantiation of the fused step kernel the handle's last step launched: out = {eos, has_ls, piezo, D, topo} -- the
+ * equation of state (gpf_config.eos), whether it reads a slip-length field, whether the viscosity is piezo-viscous, the sweep
+ * direction of the predictor (+1 / -1) and the gap's form (0 planes, 1 profile over ix, 2 profile over iy, 3 profile over ix with
+ * dh/dy = 0, 4: 3 with the row coefficients from the table).  These are the very values the launch selected its kernel with,
+ * recorded as it did.  GPF_ERR_STATE before the first such launch (problems that fit one workgroup never make one). */
+int gpf_step_variant(gpf_handle* h, int out[5]);
 /* The reference-ordered, unfused stage pipeline (closures -> flux -> source -> axpy -> ghost),
  * one kernel per reference function; same results as gpf_step(h,1,...).  Kept for
  * cross-checking and for _finalize (problem.py:588-610). */
