@@ -1,6 +1,7 @@
 // C ABI of libgapflow_hip.so (see include/gapflow_hip.h for the contract of every entry point).
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1022,8 +1023,6 @@ static int enqueue_step(gpf_handle* h, int honor_stop, long long log_base, doubl
     return GPF_OK;
 }
 
-#include "api_probes.inc"
-
 // Problems that fit one workgroup's LDS advance whole batches of steps in one launch (small_kernel.hip).
 // Why not (null: it does); gpf_ensemble_create names the reason.  one_workgroup_refusal: every reason but the grid's size, which
 // are also the reasons against the ensembles' workspace tier (mid_kernel.hip).
@@ -1075,6 +1074,8 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
 
 static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base);
 
+#include "api_series.inc"
+#include "api_probes.inc"
 #include "api_integrals.inc"
 #include "api_weighted.inc"
 #include "api_extrema.inc"
@@ -1165,9 +1166,7 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
     *kernel_ms = sum; *total_ms = ms;
     for (auto& e : ev) hipEventDestroy(e);
     StepState s;
-    GPF_TRY(read_state(h, s));
-    h->prev_state_valid = s.step > h->host_step && !s.invalid;
-    h->host_step = s.step; h->next_step = s.step;
+    GPF_TRY(series_resync(h, h->host_step, s));
     GPF_TRY(stats_restart(h, s.step));      // steps went by unrecorded: armed statistics begin a new window
     return rc;
 }

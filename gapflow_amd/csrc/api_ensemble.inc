@@ -228,7 +228,7 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         e->entries[i] = ran + ((st.invalid && ran < n[i]) ? 1 : 0);
         // the member's film records: the multiples of the stride in (base, base + ran], by its own ran (a member that stopped on
         // the device ran a prefix of its steps; a rolled-back step left none)
-        const long long cnt = e->film.every ? integrals_count(h->host_step, ran, e->film.every) : 0;
+        const long long cnt = e->film.every ? series_count(h->host_step, ran, e->film.every) : 0;
         if (cnt > 0) {
             const size_t nrec = (size_t)e->film.nrec(i);
             std::vector<double> got((size_t)cnt * nrec);
@@ -319,7 +319,7 @@ extern "C" int gpf_ensemble_integrals_set(gpf_ensemble* e, int64_t every, int ns
     GPF_TRY(ensemble_film_release(e));
     gpf_ensemble::Film f;
     f.every = every;
-    f.cap = LOG_CAPACITY / every + 1;               // integrals_count(base, ran, every) <= ran / every + 1
+    f.cap = LOG_CAPACITY / every + 1;               // series_count(base, ran, every) <= ran / every + 1
     f.args.resize(m); f.off.resize(m); f.host.resize(m); f.steps.resize(m);
     size_t total = 0;
     for (int i = 0; i < m; ++i) {

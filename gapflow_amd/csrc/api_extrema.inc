@@ -10,13 +10,9 @@ static int extrema_refusal(const gpf_handle* h, const std::string& who) {
     return GPF_OK;
 }
 
-// 16-byte pair loads of k_extrema_partial: film_wide_ok's conditions on the planes it reads (GPF_FILM_NARROW, read when the
+// 16-byte pair loads of k_extrema_partial: series_wide_ok's conditions on the planes it reads (GPF_FILM_NARROW, read when the
 // buffers are allocated, asks for the 8-byte loads regardless)
-static bool extrema_wide_ok(const gpf_handle* h) {
-    const Layout& L = h->L;
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    return ((L.off + 1) & 1) == 0 && (L.pitch & 1) == 0 && (L.plane & 1) == 0 && a16(h->q[0]) && a16(h->q[1]) && a16(h->topo) && !h->extr.narrow;
-}
+static bool extrema_wide_ok(const gpf_handle* h) { return series_wide_ok(h, h->extr.narrow, false); }
 
 // The record buffers (log_cap slots for a batch + one for gpf_extrema_now), the row scratch and the arguments' copy in device
 // memory, on first use.  `dev` is set last, once everything it describes is in place.
@@ -71,25 +67,14 @@ static int extrema_enqueue(gpf_handle* h, long long expect, long long slot) {
 // Behind the launches of one step of a batch that began at step count `base`: record it if it takes the count to a multiple
 // of the stride.  No launch otherwise, and none without extrema armed.
 static int extrema_launch(gpf_handle* h, long long expect, long long base) {
-    const long long every = h->extr.every;
-    if (!every || expect % every != 0) return GPF_OK;
-    return extrema_enqueue(h, expect, integrals_count(base, expect - base, every) - 1);
+    if (!series_due(h->extr.every, expect)) return GPF_OK;
+    return extrema_enqueue(h, expect, series_slot(base, expect, h->extr.every));
 }
 
-// After the batch's state has been read (the stream is idle): a batch that stopped on the device ran a prefix of its steps,
-// so the records written are those of the multiples of the stride in (base, base + ran]
+// After the batch's state has been read (the stream is idle): the records of its `ran` committed steps -> host
 static int extrema_collect(gpf_handle* h, long long base, long long ran) {
-    const long long every = h->extr.every;
-    if (!every) return GPF_OK;
-    const long long cnt = integrals_count(base, ran, every);
-    if (cnt <= 0) return GPF_OK;
-    const size_t at = h->extr.steps.size();
-    h->extr.host.resize((at + (size_t)cnt) * EXTREMA_NQ);
-    h->extr.cells.resize((at + (size_t)cnt) * 2 * EXTREMA_NQ);
-    HIP_TRY(hipMemcpy(h->extr.host.data() + at * EXTREMA_NQ, h->extr.a.val, (size_t)cnt * EXTREMA_NQ * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->extr.cells.data() + at * 2 * EXTREMA_NQ, h->extr.a.cell, (size_t)cnt * 2 * EXTREMA_NQ * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (long long k = 1; k <= cnt; ++k) h->extr.steps.push_back((base / every + k) * every);
-    return GPF_OK;
+    return series_collect(h->extr.every, h->extr.steps, base, ran, series_channel(h->extr.host, h->extr.a.val, (size_t)EXTREMA_NQ),
+                          series_channel(h->extr.cells, h->extr.a.cell, (size_t)2 * EXTREMA_NQ));
 }
 
 // gpf_close_step: the closed step's record, if it commits.  An elastic handle's gap deforms after the step closes
@@ -120,16 +105,7 @@ static int extrema_after_elastic_update(gpf_handle* h) {
 static int extrema_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
     ExtremaArgs& a = h->extr.a;
-    if (a.val) HIP_TRY(hipFree(a.val));
-    a.val = nullptr;
-    if (a.cell) HIP_TRY(hipFree(a.cell));
-    a.cell = nullptr;
-    if (a.row_val) HIP_TRY(hipFree(a.row_val));
-    a.row_val = nullptr;
-    if (a.row_iy) HIP_TRY(hipFree(a.row_iy));
-    a.row_iy = nullptr;
-    if (h->extr.dev) HIP_TRY(hipFree(h->extr.dev));
-    h->extr.dev = nullptr;
+    GPF_TRY(series_free({(void**)&a.val, (void**)&a.cell, (void**)&a.row_val, (void**)&a.row_iy, (void**)&h->extr.dev}));
     a.every = 0; a.cap = 0;
     h->extr.every = 0; h->extr.pending = false;
     h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
@@ -156,11 +132,8 @@ extern "C" int gpf_extrema_clear(gpf_handle* h) {
 extern "C" int gpf_extrema_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
     if (!h->extr.every) return fail(GPF_ERR_STATE, "gpf_extrema_read: no extrema are armed (gpf_extrema_set)");
-    const int64_t have = (int64_t)h->extr.steps.size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
-    if (n_records) *n_records = have;
-    if (values && take > 0) std::memcpy(values, h->extr.host.data(), (size_t)take * EXTREMA_NQ * sizeof(double));
-    if (cells && take > 0) std::memcpy(cells, h->extr.cells.data(), (size_t)take * 2 * EXTREMA_NQ * sizeof(int32_t));
-    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = h->extr.steps[(size_t)k];
+    series_read(h->extr.steps, capacity_records, steps_out, n_records, series_channel(h->extr.host, values, (size_t)EXTREMA_NQ),
+                series_channel(h->extr.cells, cells, (size_t)2 * EXTREMA_NQ));
     return GPF_OK;
 }
 
@@ -181,8 +154,7 @@ extern "C" int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14
 }
 
 // Diagnostic (tools/extrema_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed extrema are put aside
-// for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes and film
-// integrals are put aside in both modes; armed statistics begin a new window after the call.
+// for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_extrema_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_extrema_time: call gpf_pre_run first");
@@ -192,49 +164,10 @@ extern "C" int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms) 
     if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
         return fail(GPF_ERR_INVALID, "gpf_extrema_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
     if (mode == 1 && !h->extr.every) return fail(GPF_ERR_STATE, "gpf_extrema_time: mode 1 needs armed extrema (gpf_extrema_set)");
-    const bool small = small_grid_eligible(h);
     GPF_TRY(enter(h));
-    h->integ.host.clear(); h->integ.steps.clear();
-    h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->extr.every, keep_integ = h->integ.every;
-    const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0;
-    int rc = extrema_begin(h);          // (buffers and the device copy of the arguments while the stride is still the armed one)
-    if (mode != 1) { h->extr.every = 0; h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear(); }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    const long long base = h->host_step;
-    float t = 0.f;
-    if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
-    if (rc == GPF_OK && e == hipSuccess) {
-        if (small) rc = enqueue_small_steps(h, (int)n, 0, base);
-        for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
-            rc = enqueue_step(h, 0, base, nullptr);
-            if (rc == GPF_OK) rc = extrema_launch(h, base + i + 1, base);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    // steps may have been queued whatever went wrong after them: the host's counters follow the device's
-    StepState s;
-    const int rs = read_state(h, s);
-    if (rs == GPF_OK) {
-        h->prev_state_valid = s.step > base && !s.invalid;
-        h->host_step = s.step; h->next_step = s.step;
-    }
-    int rcol = GPF_OK;
-    if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = extrema_collect(h, base, s.step - base);
-    h->extr.every = keep_every; h->integ.every = keep_integ; h->probes.n = keep_probes;
-    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
-    GPF_TRY(rc);
-    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_extrema_time: ") + hipGetErrorString(e));
-    GPF_TRY(rs);
-    GPF_TRY(rcol);
-    *ms = t;
-    return GPF_OK;
+    GPF_TRY(extrema_begin(h));          // (buffers and the device copy of the arguments while the stride is still the armed one)
+    SeriesAside aside(h, mode == 1 ? &h->extr.every : nullptr);
+    return series_time(h, "gpf_extrema_time", aside,
+                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return extrema_launch(h, expect, base); }); },
+                       [&](long long base, long long ran) { return extrema_collect(h, base, ran); }, ms);
 }

@@ -4,23 +4,10 @@
 // A handle that steps through k_small_steps records inside the batch (film_record_block, told where by integ.dev): same buffer,
 // same slots, same bits, no launch.
 
-// Records a stepping call leaves for the steps (base, base + ran]: the multiples of `every` among them.
-static long long integrals_count(long long base, long long ran, long long every) {
-    return ran > 0 ? (base + ran) / every - base / every : 0;
-}
-
 static int integrals_nrec(const gpf_handle* h) { return FILM_NSUM + h->integ.nsx + h->integ.nsy; }
 
-// The cases the reduction does not cover, with the error class gpf_probes_set / gpf_gap_profiles give them
-static int integrals_refusal(const gpf_handle* h, const std::string& who) {
-    if (h->E.halo[0] || h->E.halo[1]) return fail(GPF_ERR_STATE, who + ": this handle is a slab; film integrals are not available on slabs");
-    if (h->step_open) return fail(GPF_ERR_STATE, who + ": a stage-wise step is open; close it first");
-    if (h->gp[0].set || h->gp[1].set || h->gp[2].set)
-        return fail(GPF_ERR_INVALID, who + ": surrogate closures: the film integrals evaluate the analytic pressure and wall stress, which this handle replaces");
-    if (h->cfg.thinning != GPF_THINNING_NONE) return fail(GPF_ERR_INVALID, who + ": shear thinning needs grad p (not supported)");
-    if (h->el.on || h->els.on) return fail(GPF_ERR_INVALID, who + ": an elastic handle steps stage-wise and deforms its gap between steps (not supported)");
-    return GPF_OK;
-}
+// The cases the reduction does not cover (series_refusal)
+static int integrals_refusal(const gpf_handle* h, const std::string& who) { return series_refusal(h, who, "film integrals", "the film integrals"); }
 
 // First and last interior row / column; a direction of extent 1 has the one section
 static void integrals_default_sections(gpf_handle* h) {
@@ -28,16 +15,10 @@ static void integrals_default_sections(gpf_handle* h) {
     h->integ.nsy = h->L.Ny > 1 ? 2 : 1; h->integ.sy[0] = 1; h->integ.sy[1] = h->L.Ny;
 }
 
-// 16-byte pair loads of k_film_partial: every pair (1 + 2k, 2 + 2k) of every row of every plane must start on 16 bytes.
-// Layout and hipMalloc give that today, so the 8-byte loads are otherwise out of reach: the environment variable GPF_FILM_NARROW
-// (any value; read when the buffers are allocated, i.e. at the first record after gpf_integrals_set / _clear) asks for them,
-// which is how tests/test_gpu_integrals.py holds them bit for bit against the wide loads.
-static bool film_wide_ok(const gpf_handle* h) {
-    const Layout& L = h->L;
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    return ((L.off + 1) & 1) == 0 && (L.pitch & 1) == 0 && (L.plane & 1) == 0 && a16(h->q[0]) && a16(h->q[1]) && a16(h->topo) &&
-           (!h->Ls || a16(h->Ls)) && !h->integ.narrow;
-}
+// 16-byte pair loads of k_film_partial: series_wide_ok's conditions on the planes it reads (GPF_FILM_NARROW, read when the
+// buffers are allocated, i.e. at the first record after gpf_integrals_set / _clear, asks for the 8-byte loads regardless, which
+// is how tests/test_gpu_integrals.py holds them bit for bit against the wide loads)
+static bool film_wide_ok(const gpf_handle* h) { return series_wide_ok(h, h->integ.narrow, true); }
 
 static FilmBlockArgs film_block_args(double* rec, long long every, long long cap, double dx, double dy, int nsx, const int* sx, int nsy, const int* sy) {
     FilmBlockArgs b;
@@ -96,33 +77,18 @@ static int integrals_enqueue(gpf_handle* h, long long expect, long long slot) {
 // Behind the launches of one step of a batch that began at step count `base`: record it if it takes the count to a multiple
 // of the stride.  No launch otherwise, and none without integrals armed.
 static int integrals_launch(gpf_handle* h, long long expect, long long base) {
-    const long long every = h->integ.every;
-    if (!every || expect % every != 0) return GPF_OK;
-    return integrals_enqueue(h, expect, integrals_count(base, expect - base, every) - 1);
+    if (!series_due(h->integ.every, expect)) return GPF_OK;
+    return integrals_enqueue(h, expect, series_slot(base, expect, h->integ.every));
 }
 
-// After the batch's state has been read (the stream is idle): a batch that stopped on the device ran a prefix of its steps,
-// so the records written are those of the multiples of the stride in (base, base + ran]
+// After the batch's state has been read (the stream is idle): the records of its `ran` committed steps -> host
 static int integrals_collect(gpf_handle* h, long long base, long long ran) {
-    const long long every = h->integ.every;
-    if (!every) return GPF_OK;
-    const long long cnt = integrals_count(base, ran, every);
-    if (cnt <= 0) return GPF_OK;
-    const size_t nrec = (size_t)integrals_nrec(h), at = h->integ.host.size();
-    h->integ.host.resize(at + (size_t)cnt * nrec);
-    HIP_TRY(hipMemcpy(h->integ.host.data() + at, h->integ.rec, (size_t)cnt * nrec * sizeof(double), hipMemcpyDeviceToHost));
-    for (long long k = 1; k <= cnt; ++k) h->integ.steps.push_back((base / every + k) * every);
-    return GPF_OK;
+    return series_collect(h->integ.every, h->integ.steps, base, ran, series_channel(h->integ.host, h->integ.rec, (size_t)integrals_nrec(h)));
 }
 
 static int integrals_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    if (h->integ.rec) HIP_TRY(hipFree(h->integ.rec));
-    h->integ.rec = nullptr;
-    if (h->integ.part) HIP_TRY(hipFree(h->integ.part));
-    h->integ.part = nullptr;
-    if (h->integ.dev) HIP_TRY(hipFree(h->integ.dev));
-    h->integ.dev = nullptr;
+    GPF_TRY(series_free({(void**)&h->integ.rec, (void**)&h->integ.part, (void**)&h->integ.dev}));
     h->integ.every = 0; h->integ.nsx = h->integ.nsy = 0;
     h->integ.host.clear(); h->integ.steps.clear();
     return GPF_OK;
@@ -162,11 +128,7 @@ extern "C" int gpf_integrals_clear(gpf_handle* h) {
 extern "C" int gpf_integrals_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
     if (!h->integ.every) return fail(GPF_ERR_STATE, "gpf_integrals_read: no integrals are armed (gpf_integrals_set)");
-    const size_t nrec = (size_t)integrals_nrec(h);
-    const int64_t have = (int64_t)h->integ.steps.size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
-    if (n_records) *n_records = have;
-    if (out && take > 0) std::memcpy(out, h->integ.host.data(), (size_t)take * nrec * sizeof(double));
-    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = h->integ.steps[(size_t)k];
+    series_read(h->integ.steps, capacity_records, steps_out, n_records, series_channel(h->integ.host, out, (size_t)integrals_nrec(h)));
     return GPF_OK;
 }
 
@@ -194,8 +156,7 @@ extern "C" int gpf_integrals_now(gpf_handle* h, double* out, int64_t count) {
 }
 
 // Diagnostic (tools/integrals_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed integrals are put
-// aside for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes, weighted
-// integrals and statistics are put aside in both modes (armed statistics begin a new window after the call).
+// aside for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_integrals_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_integrals_time: call gpf_pre_run first");
@@ -203,50 +164,10 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
     if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
         return fail(GPF_ERR_INVALID, "gpf_integrals_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
     if (mode == 1 && !h->integ.every) return fail(GPF_ERR_STATE, "gpf_integrals_time: mode 1 needs armed integrals (gpf_integrals_set)");
-    const bool small = small_grid_eligible(h);
     GPF_TRY(enter(h));
-    h->integ.host.clear(); h->integ.steps.clear();
-    h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->integ.every, keep_weighted = h->weighted.every, keep_stats = h->stats.every, keep_regions = h->regions.every,
-                    keep_lines = h->lines.every;
-    const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->weighted.every = 0; h->stats.every = 0; h->regions.every = 0; h->lines.every = 0;
-    if (mode != 1) h->integ.every = 0;
-    int rc = integrals_begin(h);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    const long long base = h->host_step;
-    float t = 0.f;
-    if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
-    if (rc == GPF_OK && e == hipSuccess) {
-        if (small) rc = small_batch_cut(h, n, 0, base);
-        for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
-            rc = enqueue_step(h, 0, base, nullptr);
-            if (rc == GPF_OK) rc = integrals_launch(h, base + i + 1, base);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    // steps may have been queued whatever went wrong after them: the host's counters follow the device's
-    StepState s;
-    const int rs = read_state(h, s);
-    if (rs == GPF_OK) {
-        h->prev_state_valid = s.step > base && !s.invalid;
-        h->host_step = s.step; h->next_step = s.step;
-    }
-    int rcol = GPF_OK;
-    if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = integrals_collect(h, base, s.step - base);
-    h->integ.every = keep_every; h->weighted.every = keep_weighted; h->stats.every = keep_stats; h->regions.every = keep_regions; h->lines.every = keep_lines; h->probes.n = keep_probes;
-    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
-    GPF_TRY(rc);
-    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_integrals_time: ") + hipGetErrorString(e));
-    GPF_TRY(rs);
-    GPF_TRY(rcol);
-    *ms = t;
-    return GPF_OK;
+    SeriesAside aside(h, mode == 1 ? &h->integ.every : nullptr);
+    GPF_TRY(integrals_begin(h));
+    return series_time(h, "gpf_integrals_time", aside,
+                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return integrals_launch(h, expect, base); }); },
+                       [&](long long base, long long ran) { return integrals_collect(h, base, ran); }, ms);
 }

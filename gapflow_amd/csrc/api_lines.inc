@@ -3,16 +3,8 @@
 // committed steps whose count is a multiple of the armed stride, and handed out once per call.  Kernels: line_kernels.hip; the
 // record's layout, the order of a band's additions and the batch limit: lines.hpp.
 
-// The cases the recording does not cover: the regions' (regions_refusal), with their error classes
-static int lines_refusal(const gpf_handle* h, const std::string& who) {
-    if (h->E.halo[0] || h->E.halo[1]) return fail(GPF_ERR_STATE, who + ": this handle is a slab; lines are not available on slabs");
-    if (h->step_open) return fail(GPF_ERR_STATE, who + ": a stage-wise step is open; close it first");
-    if (h->gp[0].set || h->gp[1].set || h->gp[2].set)
-        return fail(GPF_ERR_INVALID, who + ": surrogate closures: the lines evaluate the analytic pressure and wall stress, which this handle replaces");
-    if (h->cfg.thinning != GPF_THINNING_NONE) return fail(GPF_ERR_INVALID, who + ": shear thinning needs grad p (not supported)");
-    if (h->el.on || h->els.on) return fail(GPF_ERR_INVALID, who + ": an elastic handle steps stage-wise and deforms its gap between steps (not supported)");
-    return GPF_OK;
-}
+// The cases the recording does not cover: the regions' (series_refusal), with their error classes
+static int lines_refusal(const gpf_handle* h, const std::string& who) { return series_refusal(h, who, "lines", "the lines"); }
 
 // gpf_line entries checked against the handle's grid and laid out (lines.hpp: lines_layout); i0 = i1 = 0 is the centre line
 static int lines_parse(const gpf_handle* h, const std::string& who, int K, const gpf_line* lines, Line* defs, long long* rec_doubles, long long* scratch_doubles) {
@@ -106,33 +98,21 @@ static long long lines_batch(const gpf_handle* h, long long batch, long long bas
 // Behind the launches of one step of a batch that began at step count `base`: record it if it takes the count to a multiple
 // of the stride.  No launch otherwise, and none without lines armed.
 static int lines_launch(gpf_handle* h, long long expect, long long base) {
-    const long long every = h->lines.every;
-    if (!every || expect % every != 0) return GPF_OK;
-    const long long slot = lines_count(base, expect - base, every) - 1;
+    if (!series_due(h->lines.every, expect)) return GPF_OK;
+    const long long slot = lines_count(base, expect - base, h->lines.every) - 1;
     if (slot >= h->lines.capacity) return fail(GPF_ERR_STATE, "lines: a batch would leave more than the " + std::to_string(h->lines.capacity) + " records the buffer holds");
     return lines_enqueue(h, expect, slot);
 }
 
-// After the batch's state has been read (the stream is idle): the records written are those of the multiples of the stride in
-// (base, base + ran]
+// After the batch's state has been read (the stream is idle): the records of its `ran` committed steps -> host (series_count
+// is lines.hpp's lines_count)
 static int lines_collect(gpf_handle* h, long long base, long long ran) {
-    const long long every = h->lines.every;
-    if (!every) return GPF_OK;
-    const long long cnt = lines_count(base, ran, every);
-    if (cnt <= 0) return GPF_OK;
-    const size_t nd = (size_t)h->lines.rec_doubles, at = h->lines.host.size();
-    h->lines.host.resize(at + (size_t)cnt * nd);
-    HIP_TRY(hipMemcpy(h->lines.host.data() + at, h->lines.rec, (size_t)cnt * nd * sizeof(double), hipMemcpyDeviceToHost));
-    for (long long k = 1; k <= cnt; ++k) h->lines.steps.push_back((base / every + k) * every);
-    return GPF_OK;
+    return series_collect(h->lines.every, h->lines.steps, base, ran, series_channel(h->lines.host, h->lines.rec, (size_t)h->lines.rec_doubles));
 }
 
 static int lines_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    for (double** p : {&h->lines.rec, &h->lines.scratch}) {
-        if (*p) HIP_TRY(hipFree(*p));
-        *p = nullptr;
-    }
+    GPF_TRY(series_free({(void**)&h->lines.rec, (void**)&h->lines.scratch}));
     h->lines.every = 0; h->lines.K = 0; h->lines.capacity = 0; h->lines.rec_doubles = 0;
     h->lines.host.clear(); h->lines.steps.clear();
     return GPF_OK;
@@ -174,11 +154,7 @@ extern "C" int gpf_lines_clear(gpf_handle* h) {
 extern "C" int gpf_lines_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
     if (!h->lines.every) return fail(GPF_ERR_STATE, "gpf_lines_read: no lines are armed (gpf_lines_set)");
-    const size_t nd = (size_t)h->lines.rec_doubles;
-    const int64_t have = (int64_t)h->lines.steps.size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
-    if (n_records) *n_records = have;
-    if (out && take > 0) std::memcpy(out, h->lines.host.data(), (size_t)take * nd * sizeof(double));
-    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = h->lines.steps[(size_t)k];
+    series_read(h->lines.steps, capacity_records, steps_out, n_records, series_channel(h->lines.host, out, (size_t)h->lines.rec_doubles));
     return GPF_OK;
 }
 
@@ -219,8 +195,7 @@ extern "C" int gpf_lines_now(gpf_handle* h, int K, const gpf_line* lines, double
 
 // Diagnostic (tools/lines_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed lines are put aside for the
 // call), 1 recording at the armed stride (n at most what one batch may hold: lines_batch); *ms = first launch to last on the
-// handle's stream.  Probes, film integrals, weighted integrals, regions, extrema and statistics are put aside in both modes
-// (armed statistics begin a new window after the call).
+// handle's stream (series_time).
 extern "C" int gpf_lines_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_lines_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_lines_time: call gpf_pre_run first");
@@ -231,54 +206,10 @@ extern "C" int gpf_lines_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (mode == 1 && n > lines_batch(h, n, h->host_step))
         return fail(GPF_ERR_INVALID, "gpf_lines_time: " + std::to_string(n) + " steps leave more records than the buffer holds (" + std::to_string(h->lines.capacity) +
                                      " at stride " + std::to_string(h->lines.every) + ")");
-    const bool small = small_grid_eligible(h);
     GPF_TRY(enter(h));
-    h->integ.host.clear(); h->integ.steps.clear();
-    h->weighted.host.clear(); h->weighted.steps.clear();
-    h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
-    h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
-    h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->lines.every, keep_integ = h->integ.every, keep_weighted = h->weighted.every, keep_regions = h->regions.every,
-                    keep_extr = h->extr.every, keep_stats = h->stats.every;
-    const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->regions.every = 0; h->extr.every = 0; h->stats.every = 0;
-    if (mode != 1) h->lines.every = 0;
-    int rc = lines_begin(h);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    const long long base = h->host_step;
-    float t = 0.f;
-    if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
-    if (rc == GPF_OK && e == hipSuccess) {
-        if (small) rc = small_batch_cut(h, n, 0, base);
-        for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
-            rc = enqueue_step(h, 0, base, nullptr);
-            if (rc == GPF_OK) rc = lines_launch(h, base + i + 1, base);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    // steps may have been queued whatever went wrong after them: the host's counters follow the device's
-    StepState s;
-    const int rs = read_state(h, s);
-    if (rs == GPF_OK) {
-        h->prev_state_valid = s.step > base && !s.invalid;
-        h->host_step = s.step; h->next_step = s.step;
-    }
-    int rcol = GPF_OK;
-    if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = lines_collect(h, base, s.step - base);
-    h->lines.every = keep_every; h->integ.every = keep_integ; h->weighted.every = keep_weighted; h->regions.every = keep_regions; h->extr.every = keep_extr;
-    h->stats.every = keep_stats; h->probes.n = keep_probes;
-    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
-    GPF_TRY(rc);
-    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_lines_time: ") + hipGetErrorString(e));
-    GPF_TRY(rs);
-    GPF_TRY(rcol);
-    *ms = t;
-    return GPF_OK;
+    SeriesAside aside(h, mode == 1 ? &h->lines.every : nullptr);
+    GPF_TRY(lines_begin(h));
+    return series_time(h, "gpf_lines_time", aside,
+                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return lines_launch(h, expect, base); }); },
+                       [&](long long base, long long ran) { return lines_collect(h, base, ran); }, ms);
 }

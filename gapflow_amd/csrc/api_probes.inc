@@ -54,12 +54,7 @@ static int probes_collect(gpf_handle* h, long long ran) {
 
 static int probes_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    if (h->probes.cells) HIP_TRY(hipFree(h->probes.cells));
-    h->probes.cells = nullptr;
-    if (h->probes.buf) HIP_TRY(hipFree(h->probes.buf));
-    h->probes.buf = nullptr;
-    if (h->probes.dev) HIP_TRY(hipFree(h->probes.dev));
-    h->probes.dev = nullptr;
+    GPF_TRY(series_free({(void**)&h->probes.cells, (void**)&h->probes.buf, (void**)&h->probes.dev}));
     h->probes.n = 0; h->probes.nv = 0;
     h->probes.host.clear(); h->probes.first_step = 0;
     return GPF_OK;
@@ -113,8 +108,6 @@ extern "C" int gpf_probes_read(gpf_handle* h, double* out, int64_t capacity_step
 // Diagnostic (tools/probe_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing, 1 k_probe_record (probes must
 // be set), 2 an empty kernel behind every step; *ms = first launch to last on the handle's stream.  Small grids take
 // k_small_steps, where mode 2 has no meaning and is refused.
-static bool small_grid_eligible(gpf_handle* h);
-static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long long log_base);
 extern "C" int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_probes_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_probes_time: call gpf_pre_run first");
@@ -122,48 +115,17 @@ extern "C" int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (n < 1 || n > h->log_cap || mode < 0 || mode > 2)
         return fail(GPF_ERR_INVALID, "gpf_probes_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..2 required");
     if (mode == 1 && !h->probes.n) return fail(GPF_ERR_STATE, "gpf_probes_time: mode 1 needs probes (gpf_probes_set)");
-    const bool small = small_grid_eligible(h);
-    if (small && mode == 2) return fail(GPF_ERR_INVALID, "gpf_probes_time: the small-grid kernel has no launch per step to stand in for");
+    if (small_grid_eligible(h) && mode == 2) return fail(GPF_ERR_INVALID, "gpf_probes_time: the small-grid kernel has no launch per step to stand in for");
     GPF_TRY(enter(h));
-    // the records of the call before go, whatever the mode: modes 0 and 2 step on and leave none
-    h->probes.host.clear();
-    h->probes.first_step = h->host_step + 1;
     // mode 0 and 2 must not record: the probes are put aside for the call
-    const int keep_n = h->probes.n;
-    if (mode != 1) h->probes.n = 0;
-    int rc = probes_begin(h);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    const long long base = h->host_step;
-    float t = 0.f;
-    if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
-    if (rc == GPF_OK && e == hipSuccess) {
-        if (small) rc = enqueue_small_steps(h, (int)n, 0, base);
-        for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
-            rc = enqueue_step(h, 0, base, nullptr);
-            if (rc == GPF_OK && mode == 1) rc = probes_launch(h, base + i + 1, base);
-            if (rc == GPF_OK && mode == 2) hipLaunchKernelGGL(k_probe_empty, dim3(1), dim3(64), 0, h->stream);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    h->probes.n = keep_n;
-    // steps may have been queued whatever went wrong after them: the host's counters follow the device's
-    StepState s;
-    const int rs = read_state(h, s);
-    if (rs == GPF_OK) {
-        h->prev_state_valid = s.step > base && !s.invalid;
-        h->host_step = s.step; h->next_step = s.step;
-    }
-    GPF_TRY(rc);
-    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_probes_time: ") + hipGetErrorString(e));
-    GPF_TRY(rs);
-    if (mode == 1) GPF_TRY(probes_collect(h, s.step - base));
-    *ms = t;
-    return GPF_OK;
+    SeriesAside aside(h, mode == 1 ? &h->probes.n : nullptr);
+    GPF_TRY(probes_begin(h));
+    return series_time(h, "gpf_probes_time", aside,
+                       [&](long long base) {
+                           return series_time_steps(h, n, base, [&](long long expect) {
+                               if (mode == 2) hipLaunchKernelGGL(k_probe_empty, dim3(1), dim3(64), 0, h->stream);
+                               return probes_launch(h, expect, base);
+                           });
+                       },
+                       [&](long long, long long ran) { return probes_collect(h, ran); }, ms);
 }

@@ -3,28 +3,15 @@
 // the device behind the committed steps whose count is a multiple of the armed stride, and handed out once per call.
 // Kernels: region_kernels.hip; the predicate: regions.hpp.
 
-// The cases the reduction does not cover: the weighted integrals' (weighted_refusal), with their error classes
-static int regions_refusal(const gpf_handle* h, const std::string& who) {
-    if (h->E.halo[0] || h->E.halo[1]) return fail(GPF_ERR_STATE, who + ": this handle is a slab; regions are not available on slabs");
-    if (h->step_open) return fail(GPF_ERR_STATE, who + ": a stage-wise step is open; close it first");
-    if (h->gp[0].set || h->gp[1].set || h->gp[2].set)
-        return fail(GPF_ERR_INVALID, who + ": surrogate closures: the regions evaluate the analytic pressure and wall stress, which this handle replaces");
-    if (h->cfg.thinning != GPF_THINNING_NONE) return fail(GPF_ERR_INVALID, who + ": shear thinning needs grad p (not supported)");
-    if (h->el.on || h->els.on) return fail(GPF_ERR_INVALID, who + ": an elastic handle steps stage-wise and deforms its gap between steps (not supported)");
-    return GPF_OK;
-}
+// The cases the reduction does not cover: the weighted integrals' (series_refusal), with their error classes
+static int regions_refusal(const gpf_handle* h, const std::string& who) { return series_refusal(h, who, "regions", "the regions"); }
 
 static size_t regions_nsum(const gpf_handle* h) { return (size_t)h->regions.K * WFILM_NQ; }
 static size_t regions_nint(const gpf_handle* h) { return (size_t)h->regions.K * REGION_NI; }
 
-// 16-byte pair loads of k_region_partial: film_wide_ok's conditions on the planes it reads (GPF_FILM_NARROW, read by
+// 16-byte pair loads of k_region_partial: series_wide_ok's conditions on the planes it reads (GPF_FILM_NARROW, read by
 // gpf_regions_set, asks for the 8-byte loads regardless)
-static bool regions_wide_ok(const gpf_handle* h) {
-    const Layout& L = h->L;
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    return ((L.off + 1) & 1) == 0 && (L.pitch & 1) == 0 && (L.plane & 1) == 0 && a16(h->q[0]) && a16(h->q[1]) && a16(h->topo) &&
-           (!h->Ls || a16(h->Ls)) && !h->regions.narrow;
-}
+static bool regions_wide_ok(const gpf_handle* h) { return series_wide_ok(h, h->regions.narrow, true); }
 
 // A stepping call begins: its records replace those of the call before
 static int regions_begin(gpf_handle* h) {
@@ -56,33 +43,19 @@ static int regions_enqueue(gpf_handle* h, long long expect, long long slot) {
 // Behind the launches of one step of a batch that began at step count `base`: record it if it takes the count to a multiple
 // of the stride.  No launch otherwise, and none without regions armed.
 static int regions_launch(gpf_handle* h, long long expect, long long base) {
-    const long long every = h->regions.every;
-    if (!every || expect % every != 0) return GPF_OK;
-    return regions_enqueue(h, expect, integrals_count(base, expect - base, every) - 1);
+    if (!series_due(h->regions.every, expect)) return GPF_OK;
+    return regions_enqueue(h, expect, series_slot(base, expect, h->regions.every));
 }
 
-// After the batch's state has been read (the stream is idle): the records written are those of the multiples of the stride in
-// (base, base + ran]
+// After the batch's state has been read (the stream is idle): the records of its `ran` committed steps -> host
 static int regions_collect(gpf_handle* h, long long base, long long ran) {
-    const long long every = h->regions.every;
-    if (!every) return GPF_OK;
-    const long long cnt = integrals_count(base, ran, every);
-    if (cnt <= 0) return GPF_OK;
-    const size_t ns = regions_nsum(h), ni = regions_nint(h), at = h->regions.host.size(), iat = h->regions.ihost.size();
-    h->regions.host.resize(at + (size_t)cnt * ns);
-    h->regions.ihost.resize(iat + (size_t)cnt * ni);
-    HIP_TRY(hipMemcpy(h->regions.host.data() + at, h->regions.rec, (size_t)cnt * ns * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h->regions.ihost.data() + iat, h->regions.irec, (size_t)cnt * ni * sizeof(long long), hipMemcpyDeviceToHost));
-    for (long long k = 1; k <= cnt; ++k) h->regions.steps.push_back((base / every + k) * every);
-    return GPF_OK;
+    return series_collect(h->regions.every, h->regions.steps, base, ran, series_channel(h->regions.host, h->regions.rec, regions_nsum(h)),
+                          series_channel(h->regions.ihost, h->regions.irec, regions_nint(h)));
 }
 
 static int regions_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    for (void** p : {(void**)&h->regions.defs, (void**)&h->regions.part, (void**)&h->regions.ipart, (void**)&h->regions.rec, (void**)&h->regions.irec}) {
-        if (*p) HIP_TRY(hipFree(*p));
-        *p = nullptr;
-    }
+    GPF_TRY(series_free({(void**)&h->regions.defs, (void**)&h->regions.part, (void**)&h->regions.ipart, (void**)&h->regions.rec, (void**)&h->regions.irec}));
     h->regions.every = 0; h->regions.K = 0;
     h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
     return GPF_OK;
@@ -148,12 +121,8 @@ extern "C" int gpf_regions_clear(gpf_handle* h) {
 extern "C" int gpf_regions_read(gpf_handle* h, double* sums, int64_t* ints, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
     if (!h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_read: no regions are armed (gpf_regions_set)");
-    const size_t ns = regions_nsum(h), ni = regions_nint(h);
-    const int64_t have = (int64_t)h->regions.steps.size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
-    if (n_records) *n_records = have;
-    if (sums && take > 0) std::memcpy(sums, h->regions.host.data(), (size_t)take * ns * sizeof(double));
-    if (ints && take > 0) std::memcpy(ints, h->regions.ihost.data(), (size_t)take * ni * sizeof(int64_t));
-    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = h->regions.steps[(size_t)k];
+    series_read(h->regions.steps, capacity_records, steps_out, n_records, series_channel(h->regions.host, sums, regions_nsum(h)),
+                series_channel(h->regions.ihost, (long long*)ints, regions_nint(h)));
     return GPF_OK;
 }
 
@@ -176,8 +145,7 @@ extern "C" int gpf_regions_now(gpf_handle* h, double* sums, int64_t* ints, int64
 }
 
 // Diagnostic (tools/regions_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed regions are put aside for
-// the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream.  Probes, film integrals, weighted
-// integrals, extrema and statistics are put aside in both modes (armed statistics begin a new window after the call).
+// the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_regions_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_regions_time: call gpf_pre_run first");
@@ -185,53 +153,10 @@ extern "C" int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms) 
     if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
         return fail(GPF_ERR_INVALID, "gpf_regions_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
     if (mode == 1 && !h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_time: mode 1 needs armed regions (gpf_regions_set)");
-    const bool small = small_grid_eligible(h);
     GPF_TRY(enter(h));
-    h->integ.host.clear(); h->integ.steps.clear();
-    h->weighted.host.clear(); h->weighted.steps.clear();
-    h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
-    h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->regions.every, keep_integ = h->integ.every, keep_weighted = h->weighted.every, keep_extr = h->extr.every,
-                    keep_stats = h->stats.every, keep_lines = h->lines.every;
-    const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->extr.every = 0; h->stats.every = 0; h->lines.every = 0;
-    if (mode != 1) h->regions.every = 0;
-    int rc = regions_begin(h);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    const long long base = h->host_step;
-    float t = 0.f;
-    if (rc == GPF_OK && e == hipSuccess) e = hipEventRecord(e0, h->stream);
-    if (rc == GPF_OK && e == hipSuccess) {
-        if (small) rc = small_batch_cut(h, n, 0, base);
-        for (int64_t i = 0; i < n && rc == GPF_OK && !small; ++i) {
-            rc = enqueue_step(h, 0, base, nullptr);
-            if (rc == GPF_OK) rc = regions_launch(h, base + i + 1, base);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    // steps may have been queued whatever went wrong after them: the host's counters follow the device's
-    StepState s;
-    const int rs = read_state(h, s);
-    if (rs == GPF_OK) {
-        h->prev_state_valid = s.step > base && !s.invalid;
-        h->host_step = s.step; h->next_step = s.step;
-    }
-    int rcol = GPF_OK;
-    if (rc == GPF_OK && e == hipSuccess && rs == GPF_OK) rcol = regions_collect(h, base, s.step - base);
-    h->regions.every = keep_every; h->integ.every = keep_integ; h->weighted.every = keep_weighted; h->extr.every = keep_extr; h->stats.every = keep_stats;
-    h->lines.every = keep_lines; h->probes.n = keep_probes;
-    if (rs == GPF_OK && rcol == GPF_OK) rcol = stats_restart(h, s.step);
-    GPF_TRY(rc);
-    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_regions_time: ") + hipGetErrorString(e));
-    GPF_TRY(rs);
-    GPF_TRY(rcol);
-    *ms = t;
-    return GPF_OK;
+    SeriesAside aside(h, mode == 1 ? &h->regions.every : nullptr);
+    GPF_TRY(regions_begin(h));
+    return series_time(h, "gpf_regions_time", aside,
+                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return regions_launch(h, expect, base); }); },
+                       [&](long long base, long long ran) { return regions_collect(h, base, ran); }, ms);
 }

@@ -25,13 +25,9 @@ static long long stats_count(const gpf_handle* h, long long step) {
 
 static int stats_nfields(int mask) { return (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1) + ((mask >> 3) & 1); }
 
-// 16-byte pair accesses of k_stats_update: film_wide_ok's conditions on the planes it reads and the accumulator planes
+// 16-byte pair accesses of k_stats_update: series_wide_ok's conditions on the planes it reads and the accumulator planes
 // (GPF_FILM_NARROW, read by gpf_stats_set, asks for the 8-byte accesses regardless)
-static bool stats_wide_ok(const gpf_handle* h) {
-    const Layout& L = h->L;
-    auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    return ((L.off + 1) & 1) == 0 && (L.pitch & 1) == 0 && (L.plane & 1) == 0 && a16(h->q[0]) && a16(h->q[1]) && a16(h->stats.acc) && !h->stats.narrow;
-}
+static bool stats_wide_ok(const gpf_handle* h) { return series_wide_ok(h, h->stats.narrow, false, h->stats.acc); }
 
 // A stepping call begins
 static int stats_begin(gpf_handle* h) {
@@ -93,33 +89,9 @@ static int stats_restart(gpf_handle* h, long long step) {
 
 static int stats_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    if (h->stats.acc) HIP_TRY(hipFree(h->stats.acc));
-    h->stats.acc = nullptr;
-    if (h->stats.rec) HIP_TRY(hipFree(h->stats.rec));
-    h->stats.rec = nullptr;
+    GPF_TRY(series_free({(void**)&h->stats.acc, (void**)&h->stats.rec}));
     h->stats.every = 0; h->stats.after = 0; h->stats.mask = 0; h->stats.arm_step = 0;
     h->stats.host = StatsRecord{};
-    return GPF_OK;
-}
-
-// A batch of the small-grid kernel, cut at the union of the steps that the series which cut it record (weighted integrals,
-// regions, lines, statistics), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
-// batch in pieces is bitwise the batch in one: every piece starts from the state and the run state the piece before left.
-// With none of them armed this is the one launch.  Probes, extrema and film integrals do not cut: k_small_steps records them.
-static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base) {
-    const long long end = base + batch;
-    for (long long at = base; at < end;) {
-        long long next = end;
-        for (long long every : {h->weighted.every, h->regions.every, h->lines.every})
-            if (every) next = std::min(next, (at / every + 1) * every);
-        if (h->stats.every) next = std::min(next, (std::max(at, stats_floor(h)) / h->stats.every + 1) * h->stats.every);
-        GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
-        GPF_TRY(weighted_launch(h, next, base));
-        GPF_TRY(regions_launch(h, next, base));
-        GPF_TRY(lines_launch(h, next, base));
-        GPF_TRY(stats_launch(h, next));
-        at = next;
-    }
     return GPF_OK;
 }
 
@@ -190,8 +162,7 @@ extern "C" int gpf_stats_read(gpf_handle* h, int field, int quantity, double* ou
 // Diagnostic (tools/stats_time.py): with `mode` 0 and 1, n steps as gpf_step enqueues them -- 0 nothing recorded (armed
 // statistics are put aside for the call), 1 recording at the armed stride and `after`; with `mode` 2, n launches of
 // k_stats_stream, the elementwise kernel that moves a record's bytes over the same planes, and no step (the window restarts:
-// its accumulators have been written over).  *ms = first launch to last on the handle's stream.  Probes, film integrals, weighted
-// integrals and extrema are put aside in every mode.
+// its accumulators have been written over).  *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_stats_time: null argument");
     if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_stats_time: call gpf_pre_run first");
@@ -201,61 +172,18 @@ extern "C" int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms) {
     if (n < 1 || n > h->log_cap || mode < 0 || mode > 2)
         return fail(GPF_ERR_INVALID, "gpf_stats_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..2 required");
     if (mode >= 1 && !h->stats.every) return fail(GPF_ERR_STATE, "gpf_stats_time: modes 1 and 2 need armed statistics (gpf_stats_set)");
-    const bool small = small_grid_eligible(h);
     GPF_TRY(enter(h));
-    h->integ.host.clear(); h->integ.steps.clear();
-    h->weighted.host.clear(); h->weighted.steps.clear();
-    h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
-    h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    const long long keep_every = h->stats.every, keep_integ = h->integ.every, keep_weighted = h->weighted.every, keep_extr = h->extr.every, keep_regions = h->regions.every,
-                    keep_lines = h->lines.every;
-    const int keep_probes = h->probes.n;
-    h->probes.n = 0; h->integ.every = 0; h->weighted.every = 0; h->extr.every = 0; h->regions.every = 0; h->lines.every = 0;
-    if (mode != 1) h->stats.every = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    const long long base = h->host_step;
-    int rc = GPF_OK;
-    float t = 0.f;
-    if (e == hipSuccess) e = hipEventRecord(e0, h->stream);
-    if (e == hipSuccess) {
-        if (mode == 2) {
-            int par = 0;
-            rc = current_parity(h, &par);
-            const int mask = h->stats.mask, nin = ((mask & 3) ? 1 : 0) + ((mask >> 2) & 1) + ((mask >> 3) & 1);
-            for (int64_t i = 0; i < n && rc == GPF_OK; ++i)
-                hipLaunchKernelGGL(k_stats_stream, dim3(stats_grid(h)), dim3(256), 0, h->stream, (const double*)h->q[par], h->stats.acc, h->L.plane, nin,
-                                   stats_nfields(mask));
-        } else if (small) {
-            rc = small_batch_cut(h, n, 0, base);
-        } else {
-            for (int64_t i = 0; i < n && rc == GPF_OK; ++i) {
-                rc = enqueue_step(h, 0, base, nullptr);
-                if (rc == GPF_OK) rc = stats_launch(h, base + i + 1);
-            }
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(e1, h->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    // steps may have been queued whatever went wrong after them: the host's counters follow the device's
-    StepState s;
-    const int rs = read_state(h, s);
-    if (rs == GPF_OK) {
-        h->prev_state_valid = s.step > base && !s.invalid;
-        h->host_step = s.step; h->next_step = s.step;
-    }
-    h->stats.every = keep_every; h->integ.every = keep_integ; h->weighted.every = keep_weighted; h->extr.every = keep_extr; h->regions.every = keep_regions; h->lines.every = keep_lines; h->probes.n = keep_probes;
-    int rcol = GPF_OK;
-    if (rs == GPF_OK) rcol = mode == 1 ? stats_collect(h, s.step) : stats_restart(h, s.step);      // steps went by unrecorded: a new window
-    GPF_TRY(rc);
-    if (e != hipSuccess) return fail(GPF_ERR_HIP, std::string("gpf_stats_time: ") + hipGetErrorString(e));
-    GPF_TRY(rs);
-    GPF_TRY(rcol);
-    *ms = t;
-    return GPF_OK;
+    SeriesAside aside(h, mode == 1 ? &h->stats.every : nullptr);
+    return series_time(h, "gpf_stats_time", aside,
+                       [&](long long base) {
+                           if (mode != 2) return series_time_steps(h, n, base, [&](long long expect) { return stats_launch(h, expect); });
+                           int par = 0;
+                           GPF_TRY(current_parity(h, &par));
+                           const int mask = h->stats.mask, nin = ((mask & 3) ? 1 : 0) + ((mask >> 2) & 1) + ((mask >> 3) & 1);
+                           for (int64_t i = 0; i < n; ++i)
+                               hipLaunchKernelGGL(k_stats_stream, dim3(stats_grid(h)), dim3(256), 0, h->stream, (const double*)h->q[par], h->stats.acc, h->L.plane, nin,
+                                                  stats_nfields(mask));
+                           return (int)GPF_OK;
+                       },
+                       [&](long long base, long long ran) { return stats_collect(h, base + ran); }, ms);
 }

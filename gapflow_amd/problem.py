@@ -1519,7 +1519,7 @@ def _keep_probes(input_dict, ymlstring):
 def _integral_records(base, ran, every):
     """Records a stepping call leaves that took the step count from `base` over `ran` committed steps at stride `every`: the
     multiples of `every` in (base, base + ran].  The slot of the step that takes the count to `expect` is
-    _integral_records(base, expect - base, every) - 1 (csrc/api_integrals.inc: integrals_count)."""
+    _integral_records(base, expect - base, every) - 1 (csrc/api_series.inc: series_count)."""
     return (base + ran) // every - base // every if ran > 0 else 0
 
 

@@ -404,6 +404,17 @@ int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes);
  * gpf_checkpoint_save does, without the copies to the host (tools/checkpoint_time.py; yardstick: gpf_stream_probe(3, 3, ...)). */
 int gpf_checkpoint_pack_probe(gpf_handle* h, int reps, double* ms_per_pass);
 
+/* ---- the per-step series and their gpf_*_time diagnostics ------------------------------------------------------------------ */
+/* A handle records up to seven series behind its committed steps: point probes, film integrals, weighted film integrals,
+ * regions, line profiles, field extrema and running statistics (the sections below).  Each has a diagnostic gpf_<series>_time
+ * that enqueues n steps as gpf_step does and reports the time on the handle's stream.  ONE RULE holds for all seven:
+ *   - the call puts aside every series but the one it times, and that one too in the modes that do not record: nothing else
+ *     is launched behind the steps, and what was armed is armed again, unchanged, when the call returns (also on an error);
+ *   - it leaves no records of any other series for their _read calls (0 records; probes: 0 steps): it is a stepping call in
+ *     which they recorded nothing.  The timed series' _read holds what the call recorded, none in a mode that does not record;
+ *   - it begins a new window of armed statistics (count 0) at the step count it leaves, unless the call itself recorded into
+ *     the window (gpf_stats_time, mode 1). */
+
 /* ---- point probes (no reference counterpart: the reference's transient tests read q on the host after every step) -------- */
 /* Per-step time series at up to 256 cells, recorded on the device so that gpf_step keeps advancing whole batches.  A probe is
  * a cell (ix, iy) of the ghosted index space, 0 <= ix <= Nx+1, 0 <= iy <= Ny+1 (ghost cells show the boundary conditions).
@@ -431,8 +442,9 @@ int gpf_probes_set(gpf_handle* h, int n, const int32_t* ix, const int32_t* iy, i
 int gpf_probes_clear(gpf_handle* h);
 int gpf_probes_read(gpf_handle* h, double* out, int64_t capacity_steps, int64_t* first_step, int64_t* n_steps);
 /* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
- * mode 0 no recording (set probes are put aside for the call), 1 k_probe_record behind every step (k_small_steps: recording
- * inside), 2 an empty kernel in k_probe_record's place -- the floor of one more launch per step (tools/probe_time.py). */
+ * mode 0 no recording, 1 k_probe_record behind every step (k_small_steps: recording inside), 2 an empty kernel in
+ * k_probe_record's place -- the floor of one more launch per step (tools/probe_time.py).  What is put aside, left for _read
+ * and restarted: the one rule of the gpf_*_time diagnostics, above. */
 int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- film integrals (no reference counterpart: the reference leaves load, friction and flow rates to post-processing) ---- */
@@ -485,8 +497,8 @@ int gpf_integrals_now(gpf_handle* h, double* out, int64_t count);
  * through the one-workgroup kernel), else 0: the two-launch path behind every recorded step.  GPF_ERR_INVALID for a NULL. */
 int gpf_integrals_in_batch(gpf_handle* h, int* yes);
 /* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
- * mode 0 no recording (armed integrals are put aside for the call), 1 recording at the armed stride (tools/integrals_time.py).
- * Probes are put aside in both modes. */
+ * mode 0 no recording, 1 recording at the armed stride (tools/integrals_time.py).  The other series: the one rule of the
+ * gpf_*_time diagnostics (before the point probes). */
 int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- weighted film integrals (no reference counterpart: per-pad loads, windows and Fourier modes are post-processing there) -- */
@@ -531,8 +543,8 @@ int gpf_weighted_clear(gpf_handle* h);
 int gpf_weighted_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
 int gpf_weighted_now(gpf_handle* h, double* out, int64_t count);
 /* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
- * mode 0 no recording (armed weighted integrals are put aside for the call), 1 recording at the armed stride
- * (tools/weighted_time.py).  Probes, film integrals and extrema are put aside in both modes. */
+ * mode 0 no recording, 1 recording at the armed stride (tools/weighted_time.py).  The other series: the one rule of the
+ * gpf_*_time diagnostics (before the point probes). */
 int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- field extrema (no reference counterpart: the reference's users run np.argmax on a downloaded field) ------------------ */
@@ -575,8 +587,8 @@ int gpf_extrema_clear(gpf_handle* h);
 int gpf_extrema_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
 int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14]);
 /* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
- * mode 0 no recording (armed extrema are put aside for the call), 1 recording at the armed stride (tools/extrema_time.py).
- * Probes and film integrals are put aside in both modes. */
+ * mode 0 no recording, 1 recording at the armed stride (tools/extrema_time.py).  The other series: the one rule of the
+ * gpf_*_time diagnostics (before the point probes). */
 int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- running field statistics (no reference counterpart: its users download q after every step and average on the host) ---- */
@@ -621,9 +633,9 @@ int gpf_stats_clear(gpf_handle* h);
 int gpf_stats_info(gpf_handle* h, int64_t* count, int64_t* first_step, int64_t* last_step, double* t_first, double* t_last);
 int gpf_stats_read(gpf_handle* h, int field, int quantity, double* out, size_t n_doubles);
 /* Diagnostic (tools/stats_time.py): *ms from the first launch to the last on the handle's stream of, mode 0, n steps (1..4096)
- * enqueued as gpf_step does with nothing recorded (armed statistics are put aside for the call); 1, the same recording at the
- * armed stride; 2, n launches of an elementwise kernel that moves one record's bytes over the same planes, and no step.
- * Probes, film integrals, weighted integrals and extrema are put aside in every mode; modes 0 and 2 begin a new window. */
+ * enqueued as gpf_step does with nothing recorded; 1, the same recording at the armed stride; 2, n launches of an elementwise
+ * kernel that moves one record's bytes over the same planes, and no step.  The other series, and the window (modes 0 and 2
+ * begin a new one): the one rule of the gpf_*_time diagnostics (before the point probes). */
 int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- region series (no reference counterpart: its users download q and mask it on the host) -------------------------------- */
@@ -685,8 +697,8 @@ int gpf_regions_clear(gpf_handle* h);
 int gpf_regions_read(gpf_handle* h, double* sums, int64_t* ints, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
 int gpf_regions_now(gpf_handle* h, double* sums, int64_t* ints, int64_t count);
 /* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
- * mode 0 no recording (armed regions are put aside for the call), 1 recording at the armed stride (tools/regions_time.py).
- * Probes, film integrals, weighted integrals, extrema and statistics are put aside in both modes. */
+ * mode 0 no recording, 1 recording at the armed stride (tools/regions_time.py).  The other series: the one rule of the
+ * gpf_*_time diagnostics (before the point probes). */
 int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- line profiles (viz/plotting.py:51-60, viz/animations.py:200-242: the centre lines of the written frames) --------------- */
@@ -739,8 +751,8 @@ int gpf_lines_clear(gpf_handle* h);
 int gpf_lines_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
 int gpf_lines_now(gpf_handle* h, int K, const gpf_line* lines /* [K], or NULL */, double* out, int64_t count);
 /* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
- * mode 0 no recording (armed lines are put aside for the call), 1 recording at the armed stride, n no more than one batch may
- * hold (tools/lines_time.py).  Every other series is put aside in both modes. */
+ * mode 0 no recording, 1 recording at the armed stride, n no more than one batch may hold (tools/lines_time.py).  The other
+ * series: the one rule of the gpf_*_time diagnostics (before the point probes). */
 int gpf_lines_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- ensembles (no reference counterpart: the reference runs a parameter study as one process per problem) ---------------- */

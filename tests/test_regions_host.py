@@ -158,7 +158,7 @@ def test_entry_points_are_declared_bound_and_exported():
 
 
 def cuts_model(base, ran, strides):
-    """A model of csrc/api_stats.inc: small_batch_cut for series that record at the multiples of their strides (0: not armed): the
+    """A model of csrc/api_series.inc: small_batch_cut for series that record at the multiples of their strides (0: not armed): the
     step counts at which a small-grid batch over the steps (base, base + ran] is cut.  The C++ itself is held by
     tests/test_gpu_regions.py (series armed together at different strides); this pins the arithmetic it must agree with."""
     end, at, cuts = base + ran, base, []

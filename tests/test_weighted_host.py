@@ -180,7 +180,7 @@ def test_entry_points_are_declared_bound_and_exported():
 
 
 def cuts_model(base, ran, every_a, every_b):
-    """A model of csrc/api_weighted.inc: weighted_next_cut applied until the batch's end -- the step counts at which a small-grid
+    """A model of csrc/api_series.inc: small_batch_cut's next cut applied until the batch's end -- the step counts at which a small-grid
     batch over the steps (base, base + ran] is cut when two series record at strides `every_a` and `every_b` (0: not armed).  The
     C++ itself is held by tests/test_gpu_weighted.py (series armed together at different strides); this pins the arithmetic it
     must agree with: shared cuts, and for each series the slots of its OWN stride (gapflow_amd.problem._integral_records)."""
