@@ -58,19 +58,12 @@ static int integrals_begin(gpf_handle* h) {
 // The two launches on the handle's stream: the record of the committed state into `slot` if the step count is `expect`
 static int integrals_enqueue(gpf_handle* h, long long expect, long long slot) {
     FilmArgs f;
-    f.qa = h->q[0]; f.qb = h->q[1]; f.topo = h->topo; f.Ls = h->Ls; f.st = h->st;
-    f.part = h->integ.part; f.rec = h->integ.rec; f.L = h->L; f.dx = h->cfg.dx; f.dy = h->cfg.dy;
+    series_row_args(h, film_wide_ok(h), slot, f);
+    f.part = h->integ.part; f.rec = h->integ.rec;
     f.nsx = h->integ.nsx; f.nsy = h->integ.nsy;
     for (int k = 0; k < FILM_MAX_SECTIONS; ++k) { f.sx[k] = k < f.nsx ? h->integ.sx[k] : 1; f.sy[k] = k < f.nsy ? h->integ.sy[k] : 1; }
-    f.wide = film_wide_ok(h) ? 1 : 0;
-    f.slot = slot; f.cap = h->log_cap;
-    EOS_DISPATCH(h->cfg.eos, {
-        if (h->Ls) hipLaunchKernelGGL((k_film_partial<EOS_, true>), dim3(h->L.Nx), dim3(256), 0, h->stream, f, h->P, expect);
-        else hipLaunchKernelGGL((k_film_partial<EOS_, false>), dim3(h->L.Nx), dim3(256), 0, h->stream, f, h->P, expect);
-    });
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_film_fold, dim3(1), dim3(256), 0, h->stream, f, expect);
-    HIP_TRY(hipGetLastError());
+    const dim3 grid(h->L.Nx);
+    SERIES_ROWS_ENQUEUE(h, k_film_partial, k_film_fold, grid, f, expect);
     return GPF_OK;
 }
 

@@ -24,19 +24,11 @@ static int regions_begin(gpf_handle* h) {
 // The two launches on the handle's stream: the record of the committed state into `slot` if the step count is `expect`
 static int regions_enqueue(gpf_handle* h, long long expect, long long slot) {
     RegionArgs f;
-    f.qa = h->q[0]; f.qb = h->q[1]; f.topo = h->topo; f.Ls = h->Ls; f.regions = h->regions.defs; f.st = h->st;
-    f.part = h->regions.part; f.ipart = h->regions.ipart; f.rec = h->regions.rec; f.irec = h->regions.irec;
-    f.L = h->L; f.dx = h->cfg.dx; f.dy = h->cfg.dy;
-    f.K = h->regions.K; f.wide = regions_wide_ok(h) ? 1 : 0;
-    f.slot = slot; f.cap = h->log_cap;
+    series_row_args(h, regions_wide_ok(h), slot, f);
+    f.regions = h->regions.defs; f.part = h->regions.part; f.ipart = h->regions.ipart; f.rec = h->regions.rec; f.irec = h->regions.irec;
+    f.K = h->regions.K;
     const dim3 grid(h->L.Nx, f.K);
-    EOS_DISPATCH(h->cfg.eos, {
-        if (h->Ls) hipLaunchKernelGGL((k_region_partial<EOS_, true>), grid, dim3(256), 0, h->stream, f, h->P, expect);
-        else hipLaunchKernelGGL((k_region_partial<EOS_, false>), grid, dim3(256), 0, h->stream, f, h->P, expect);
-    });
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_region_fold, dim3(f.K), dim3(256), 0, h->stream, f, expect);
-    HIP_TRY(hipGetLastError());
+    SERIES_ROWS_ENQUEUE(h, k_region_partial, k_region_fold, grid, f, expect);
     return GPF_OK;
 }
 

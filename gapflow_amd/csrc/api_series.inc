@@ -1,8 +1,8 @@
 // Part of api.hip (included there, not compiled on its own): what the per-step recorders of a handle -- probes, film integrals,
 // weighted integrals, regions, lines, extrema, statistics (api_<name>.inc, included behind this file) -- have in common: the
-// arithmetic of a stride's records, their way to the host and out of it, the alignment test of the 16-byte loads, the cases the
-// film reductions refuse, how series are put aside for a call, the frame of the gpf_*_time diagnostics, and the cut of a
-// small-grid batch.  A new series is named here in SeriesAside, series_forget_records and, if it cuts, small_batch_cut.
+// arithmetic of a stride's records, their way to the host and out of it, the alignment test of the 16-byte loads, the arguments
+// and the two launches of the row-reduced series (device side: series_rows.hpp), the cases the film reductions refuse, how
+// series are put aside for a call, the frame of the gpf_*_time diagnostics, and the cut of a small-grid batch.  A new series is named here in SeriesAside, series_forget_records and, if it cuts, small_batch_cut.
 
 // ---- records of a stride -----------------------------------------------------------------------------------------------------
 // Records a stepping call leaves for the steps (base, base + ran]: the multiples of `every` among them.
@@ -76,6 +76,29 @@ static bool series_wide_ok(const gpf_handle* h, bool narrow, bool with_Ls, const
     return ((L.off + 1) & 1) == 0 && (L.pitch & 1) == 0 && (L.plane & 1) == 0 && a16(h->q[0]) && a16(h->q[1]) && a16(h->topo) &&
            (!with_Ls || !h->Ls || a16(h->Ls)) && a16(own) && !narrow;
 }
+
+// ---- the row-reduced series' launches (series_rows.hpp) ----------------------------------------------------------------------
+// What their kernels are told about the handle, the leading part of FilmArgs, WFilmArgs and RegionArgs by name (each keeps its
+// own layout): the record of the committed state goes into `slot`
+template <class Args> static void series_row_args(const gpf_handle* h, bool wide, long long slot, Args& f) {
+    f.qa = h->q[0]; f.qb = h->q[1]; f.topo = h->topo; f.Ls = h->Ls; f.st = h->st;
+    f.L = h->L; f.dx = h->cfg.dx; f.dy = h->cfg.dy;
+    f.wide = wide ? 1 : 0;
+    f.slot = slot; f.cap = h->log_cap;
+}
+
+// The two launches on the handle's stream, partial<EOS, HAS_LS> on `grid` (x: the interior rows) and fold on grid.y workgroups:
+// the record if the step count is `expect`.  Returns from the calling function on a launch error.  `grid` and `f`: variables.
+#define SERIES_ROWS_ENQUEUE(h, partial, fold, grid, f, expect)                                                                   \
+    do {                                                                                                                        \
+        EOS_DISPATCH((h)->cfg.eos, {                                                                                            \
+            if ((h)->Ls) hipLaunchKernelGGL((partial<EOS_, true>), (grid), dim3(256), 0, (h)->stream, (f), (h)->P, (expect));   \
+            else hipLaunchKernelGGL((partial<EOS_, false>), (grid), dim3(256), 0, (h)->stream, (f), (h)->P, (expect));          \
+        });                                                                                                                     \
+        HIP_TRY(hipGetLastError());                                                                                             \
+        hipLaunchKernelGGL(fold, dim3((grid).y), dim3(256), 0, (h)->stream, (f), (expect));                                     \
+        HIP_TRY(hipGetLastError());                                                                                             \
+    } while (0)
 
 // ---- refusals ----------------------------------------------------------------------------------------------------------------
 // The cases the film reductions (film integrals, weighted integrals, regions, lines) do not cover, with the error class

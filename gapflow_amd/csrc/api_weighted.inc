@@ -22,18 +22,10 @@ static int weighted_begin(gpf_handle* h) {
 // The two launches on the handle's stream: the record of the committed state into `slot` if the step count is `expect`
 static int weighted_enqueue(gpf_handle* h, long long expect, long long slot) {
     WFilmArgs f;
-    f.qa = h->q[0]; f.qb = h->q[1]; f.topo = h->topo; f.Ls = h->Ls; f.w = h->weighted.w; f.st = h->st;
-    f.part = h->weighted.part; f.rec = h->weighted.rec; f.L = h->L; f.dx = h->cfg.dx; f.dy = h->cfg.dy;
-    f.K = h->weighted.K; f.wide = weighted_wide_ok(h) ? 1 : 0;
-    f.slot = slot; f.cap = h->log_cap;
+    series_row_args(h, weighted_wide_ok(h), slot, f);
+    f.w = h->weighted.w; f.part = h->weighted.part; f.rec = h->weighted.rec; f.K = h->weighted.K;
     const dim3 grid(h->L.Nx, f.K);
-    EOS_DISPATCH(h->cfg.eos, {
-        if (h->Ls) hipLaunchKernelGGL((k_wfilm_partial<EOS_, true>), grid, dim3(256), 0, h->stream, f, h->P, expect);
-        else hipLaunchKernelGGL((k_wfilm_partial<EOS_, false>), grid, dim3(256), 0, h->stream, f, h->P, expect);
-    });
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_wfilm_fold, dim3(f.K), dim3(256), 0, h->stream, f, expect);
-    HIP_TRY(hipGetLastError());
+    SERIES_ROWS_ENQUEUE(h, k_wfilm_partial, k_wfilm_fold, grid, f, expect);
     return GPF_OK;
 }
 

@@ -14,17 +14,17 @@
 //   extrema_record_block                 inside k_small_steps, after commit_step, from the field the workgroup holds in LDS
 //                                        (one wave per quantity)
 // k_extrema_partial runs one 256-thread workgroup per interior row; thread t owns the column pairs (1 + 2k, 2 + 2k) for
-// k = t, t + 256, ..., fetched with one 16-byte load per plane where the buffers allow it (film_wide_ok) and with 8-byte loads
+// k = t, t + 256, ..., fetched with one 16-byte load per plane where the buffers allow it (series_wide_ok) and with 8-byte loads
 // otherwise; the ghost column an odd Ny reaches is loaded and never compared.  It reads 4 planes (rho, jx, jy, h: 32 B per
 // cell) and stores seven (value, iy) pairs per row; k_extrema_fold folds the Nx rows in one workgroup.
 #pragma once
+
+#include "series_rows.hpp"
 
 namespace gpf {
 
 constexpr int EXTREMA_NQ = 7;       // p_max p_min rho_max rho_min h_min u_max v_max
 constexpr int EXTREMA_NO_CELL = 0x7fffffff;
-
-typedef double ext_d2 __attribute__((ext_vector_type(2)));
 
 struct ExtremaArgs {
     double* val;            // [cap + 1][7]
@@ -104,8 +104,7 @@ __global__ __launch_bounds__(256) void k_extrema_partial(const double* qa, const
                                                          const Layout L, const Phys P, const ExtremaArgs x, int wide, long long expect,
                                                          long long slot) {
     __shared__ ExtAcc sm[4];
-    if (st->step != expect || st->invalid != 0) return;                // uniform: the step did not run, or was rolled back
-    if (slot < 0 || slot > x.cap) return;
+    if (series_skip(st, expect, slot, x.cap)) return;
     const int ix = 1 + blockIdx.x;
     const double* q = st->parity ? qb : qa;
     ExtAcc a;
@@ -115,16 +114,16 @@ __global__ __launch_bounds__(256) void k_extrema_partial(const double* qa, const
         const int iy = 1 + 2 * k;
         const bool two = iy + 1 <= L.Ny;
         const long long o = L.at(ix, iy);
-        ext_d2 in[4];
+        series_d2 in[4];
         if (wide) {
 #pragma unroll
-            for (int p = 0; p < 3; ++p) in[p] = *reinterpret_cast<const ext_d2*>(q + p * L.plane + o);
-            in[3] = *reinterpret_cast<const ext_d2*>(topo + o);
+            for (int p = 0; p < 3; ++p) in[p] = *reinterpret_cast<const series_d2*>(q + p * L.plane + o);
+            in[3] = *reinterpret_cast<const series_d2*>(topo + o);
         } else {
             const long long o1 = two ? o + 1 : o;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) in[p] = ext_d2{q[p * L.plane + o], q[p * L.plane + o1]};
-            in[3] = ext_d2{topo[o], topo[o1]};
+            for (int p = 0; p < 3; ++p) in[p] = series_d2{q[p * L.plane + o], q[p * L.plane + o1]};
+            in[3] = series_d2{topo[o], topo[o1]};
         }
         a.cell(eos_pressure<EOS>(in[0].x, P), in[0].x, in[1].x, in[2].x, in[3].x, ix, iy);
         if (two) a.cell(eos_pressure<EOS>(in[0].y, P), in[0].y, in[1].y, in[2].y, in[3].y, ix, iy + 1);
@@ -140,8 +139,7 @@ __global__ __launch_bounds__(256) void k_extrema_partial(const double* qa, const
 
 __global__ __launch_bounds__(256) void k_extrema_fold(const StepState* st, const ExtremaArgs x, int Nx, long long expect, long long slot) {
     __shared__ ExtAcc sm[4];
-    if (st->step != expect || st->invalid != 0) return;
-    if (slot < 0 || slot > x.cap) return;
+    if (series_skip(st, expect, slot, x.cap)) return;
     ExtAcc a;
     a.none();
     for (int row = threadIdx.x; row < Nx; row += 256) {
@@ -156,25 +154,11 @@ __global__ __launch_bounds__(256) void k_extrema_fold(const StepState* st, const
 
 // The same record from the dense LDS field of k_small_steps (q: planes of nc cells, rows of w; h: the gap plane): the whole
 // block (at least seven waves) calls it after the commit of a step whose count is a multiple of the stride, with the slot of
-// that step among the batch's recorded steps (ExtremaCursor keeps both, without a division per step).
+// that step among the batch's recorded steps (a SeriesCursor keeps both; the arguments are fetched from device
+// memory once per launch and stay beside it).
 // Block-uniform; reads only, and needs no barrier: the committed field is not written again before the commit after next.
 // Wave k takes quantity k alone, so that a record costs a fraction of a step: its lanes evaluate the quantity of their
 // cells and keep the first, shuffles fold the lanes -- by the same comparison -- and lane 0 stores the value and the cell.
-// Which step k_small_steps records next and where: the arguments are fetched from device memory once per launch, the first
-// multiple of the stride beyond the count the launch starts at and its slot -- the rank among the multiples in (base, .] --
-// are worked out once, and each record moves both on.
-struct ExtremaCursor {
-    ExtremaArgs x;
-    long long next, slot;
-    __device__ __forceinline__ void begin(const ExtremaArgs* args, long long step, long long base) {
-        x = *args;
-        next = (step / x.every + 1) * x.every;
-        slot = next / x.every - base / x.every - 1;
-    }
-    __device__ __forceinline__ bool due(long long step) const { return step == next; }
-    __device__ __forceinline__ void advance() { next += x.every; slot += 1; }
-};
-
 template <int EOS>
 __device__ __forceinline__ void extrema_record_block(const ExtremaArgs& x, const double* q, const double* h, int Nx, int Ny, int nc, int w,
                                                      long long slot, const Phys& P) {

@@ -94,8 +94,8 @@ __device__ __forceinline__ const StepState* mid_steps_body(const SmallArgs& a, c
     };
 
     int committed = 0;                              // steps this launch has committed (block-uniform)
-    FilmCursor film;
-    if (a.film) film.begin(a.film, st->step, a.log_base);
+    SeriesCursor film;
+    if (a.film) film.begin(a.film->every, st->step, a.log_base);
     for (int step = 0; step < a.nsteps; ++step) {
         if (st->invalid != 0 || (a.honor_stop && (st->converged || st->step >= st->max_it))) break;     // block-uniform
         const double dt = st->dt;

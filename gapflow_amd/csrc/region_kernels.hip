@@ -5,17 +5,15 @@
 // pressure limit -- so no plane fixed in advance can stand for it: the 0 / 1 weight is evaluated per cell from the state
 // (regions.hpp, which also compiles for the host), and nothing is uploaded or stored per cell.
 //
-// Two launches per record, both guarded by the device's run state like k_wfilm_partial / k_wfilm_fold:
-//   k_region_partial   grid (Nx, K): one 256-thread workgroup per interior row ix and region k, with k_wfilm_partial's geometry:
-//                      thread t owns the column pairs (1 + 2j, 2 + 2j) for j = t, t + 256, ..., the lower column first, and adds
-//                      each cell through wfilm_cell with the weight 1.0 (member) or 0.0 (not); wfilm_block_sum folds the 256
-//                      register sets.  Beside them every thread counts its members and keeps the least and the largest iy among
-//                      them; shuffles and the four waves' slots fold these integers.  Thread 0 stores the row's nine doubles to
-//                      part[k][ix - 1][9] and (count, iy_min, iy_max) to ipart[k][ix - 1][3], with plain stores.
-//   k_region_fold      grid (K): thread t takes rows t, t + 256, ... in order: the doubles as k_wfilm_fold adds them, the counts
-//                      added, iy_min / iy_max by min / max, ix_min / ix_max from the rows whose count is not zero; the same tree
-//                      folds the threads, thread 0 applies dx dy and stores the slot: nine doubles to rec[slot][k][9] and
-//                      (cells, ix_min, ix_max, iy_min, iy_max) as int64 to irec[slot][k][5], all -1 behind cells = 0.
+// The two launches per record, the pair walk, the fold tree and the guard are series_rows.hpp's, as for the weighted integrals:
+//   k_region_partial   grid (Nx, K): one workgroup per interior row ix and region k; each cell goes through wfilm_cell with the
+//                      weight 1.0 (member) or 0.0 (not).  Beside the sums every thread counts its members and keeps the least and
+//                      the largest iy among them; shuffles and the four waves' slots fold these integers.  Thread 0 stores the row's
+//                      nine doubles to part[k][ix - 1][9] and (count, iy_min, iy_max) to ipart[k][ix - 1][3], with plain stores.
+//   k_region_fold      grid (K): the rows' doubles through add_rows, in the same loop the counts added, iy_min / iy_max by min / max, ix_min /
+//                      ix_max from the rows whose count is not zero; thread 0 applies dx dy and stores the slot: nine doubles to
+//                      rec[slot][k][9] and (cells, ix_min, ix_max, iy_min, iy_max) as int64 to irec[slot][k][5], all -1 behind
+//                      cells = 0.
 // The doubles go through weighted_kernels.hip's own functions in its own order with a weight of exactly 1.0 or 0.0, so on a
 // finite state the nine sums equal, in every bit, what k_wfilm_partial / k_wfilm_fold give for the 0 / 1 plane of the same
 // predicate: acc += canonicalize(w * term) adds the term's own bits, or a zero.  (On a state that is not finite a
@@ -24,12 +22,12 @@
 // arrival order, no ticket: a record is a pure function of the state and the region list.
 // `p` in a predicate is eos_pressure<EOS> of the committed density -- the p of the probes, the extrema and the statistics, not
 // film_pressure, which the first of the nine sums adds --, `h` plane 0 of the gap, rho / jx / jy the planes of q[parity].  It is
-// evaluated only by the workgroups of a region that asks for it.  A pair is fetched with one 16-byte load per plane under
-// film_wide_ok's conditions and with two 8-byte loads otherwise; the column Ny + 1 the last pair of an odd Ny reaches is the row's
-// ghost cell: loaded, never tested, never added.  One plane fewer than k_wfilm_partial reads: there is no weight plane.
+// evaluated only by the workgroups of a region that asks for it.  One plane fewer than k_wfilm_partial reads: there is no weight
+// plane.
 #pragma once
 
 #include "regions.hpp"
+#include "series_rows.hpp"
 
 namespace gpf {
 
@@ -65,7 +63,7 @@ struct RegionInts {
     }
 };
 
-// The 256 threads' integers folded into wave slots sm[4]: call it BEFORE wfilm_block_sum, whose barrier publishes the slots;
+// The 256 threads' integers folded into wave slots sm[4]: call it BEFORE block_sum, whose barrier publishes the slots;
 // region_ints_total then reads them (thread 0 needs the result).
 __device__ __forceinline__ void region_ints_to_slots(RegionInts a, RegionInts* sm) {
     for (int s = 32; s >= 1; s >>= 1) {
@@ -110,49 +108,18 @@ template <int EOS, bool HAS_LS>
 __global__ __launch_bounds__(256) void k_region_partial(const RegionArgs f, const Phys P, long long expect) {
     __shared__ double sm[4][WFILM_NQ];
     __shared__ RegionInts smi[4];
-    if (f.st->step != expect || f.st->invalid != 0) return;            // uniform: the step did not run, or was rolled back
-    if (f.slot < 0 || f.slot > f.cap) return;
+    if (series_skip(f.st, expect, f.slot, f.cap)) return;
     const Layout& L = f.L;
     const int ix = 1 + blockIdx.x, kr = blockIdx.y;
     if (ix > L.Nx || kr >= f.K) return;
-    const double* q = f.st->parity ? f.qb : f.qa;
     const Region r = f.regions[kr];
     WFilmAcc a;
     a.zero();
     RegionInts n;
     n.zero();
-    const int npair = (L.Ny + 1) / 2;
-    for (int k = threadIdx.x; k < npair; k += 256) {
-        const int iy = 1 + 2 * k;
-        const bool two = iy + 1 <= L.Ny;
-        const long long o = L.at(ix, iy);
-        film_d2 in[7];
-        if (f.wide) {
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                in[p] = *reinterpret_cast<const film_d2*>(q + p * L.plane + o);
-                in[3 + p] = *reinterpret_cast<const film_d2*>(f.topo + p * L.plane + o);
-            }
-            in[6] = HAS_LS ? *reinterpret_cast<const film_d2*>(f.Ls + o) : film_d2{0.0, 0.0};
-        } else {
-            const long long o1 = two ? o + 1 : o;
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                in[p] = film_d2{q[p * L.plane + o], q[p * L.plane + o1]};
-                in[3 + p] = film_d2{f.topo[p * L.plane + o], f.topo[p * L.plane + o1]};
-            }
-            in[6] = HAS_LS ? film_d2{f.Ls[o], f.Ls[o1]} : film_d2{0.0, 0.0};
-        }
-        CellIn c;
-        c.rho = in[0].x; c.jx = in[1].x; c.jy = in[2].x; c.h = in[3].x; c.hx = in[4].x; c.hy = in[5].x; c.Ls = in[6].x;
-        region_cell<EOS>(a, n, r, P, c, ix, iy);
-        if (two) {
-            c.rho = in[0].y; c.jx = in[1].y; c.jy = in[2].y; c.h = in[3].y; c.hx = in[4].y; c.hy = in[5].y; c.Ls = in[6].y;
-            region_cell<EOS>(a, n, r, P, c, ix, iy + 1);
-        }
-    }
+    row_pairs<FilmPlanes<HAS_LS>>(f, nullptr, ix, [&](const CellIn& c, double, int iy, double) { region_cell<EOS>(a, n, r, P, c, ix, iy); });
     region_ints_to_slots(n, smi);
-    const WFilmAcc s = wfilm_block_sum(a, sm);
+    const WFilmAcc s = block_sum(a, sm);
     if (threadIdx.x == 0) {
         const long long row = (long long)kr * L.Nx + (ix - 1);
         double* out = f.part + row * WFILM_NQ;
@@ -167,28 +134,21 @@ __global__ __launch_bounds__(256) void k_region_partial(const RegionArgs f, cons
 __global__ __launch_bounds__(256) void k_region_fold(const RegionArgs f, long long expect) {
     __shared__ double sm[4][WFILM_NQ];
     __shared__ RegionInts smi[4];
-    if (f.st->step != expect || f.st->invalid != 0) return;
-    if (f.slot < 0 || f.slot > f.cap) return;
+    if (series_skip(f.st, expect, f.slot, f.cap)) return;
     const int kr = blockIdx.x;
     if (kr >= f.K) return;
-    WFilmAcc a;
-    a.zero();
     RegionInts n;
     n.zero();
-    for (int row = threadIdx.x; row < f.L.Nx; row += 256) {
-        const long long at = (long long)kr * f.L.Nx + row;
-        const double* in = f.part + at * WFILM_NQ;
-#pragma unroll
-        for (int k = 0; k < WFILM_NQ; ++k) a.v[k] += in[k];
-        const int* iin = f.ipart + at * REGION_NROW;
+    const WFilmAcc a = add_rows<WFILM_NQ>(f.part, kr, f.L.Nx, [&](int row) {
+        const int* iin = f.ipart + ((long long)kr * f.L.Nx + row) * REGION_NROW;
         if (iin[0] > 0) {
             RegionInts o;
             o.cells = iin[0]; o.ix_min = o.ix_max = row + 1; o.iy_min = iin[1]; o.iy_max = iin[2];
             n.merge(o);
         }
-    }
+    });
     region_ints_to_slots(n, smi);
-    const WFilmAcc s = wfilm_block_sum(a, sm);
+    const WFilmAcc s = block_sum(a, sm);
     if (threadIdx.x != 0) return;
     double* out = f.rec + (f.slot * f.K + kr) * WFILM_NQ;
     const double dA = f.dx * f.dy;

@@ -88,10 +88,10 @@ __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a,
     };
 
     int committed = 0;                              // steps this launch has committed (block-uniform)
-    ExtremaCursor ext;
-    if (a.extrema) ext.begin(a.extrema, st->step, a.log_base);
-    FilmCursor film;
-    if (a.film) film.begin(a.film, st->step, a.log_base);
+    ExtremaArgs ext_x;                              // fetched once per launch; the film's arguments when a record is due
+    SeriesCursor ext, film;
+    if (a.extrema) { ext_x = *a.extrema; ext.begin(ext_x.every, st->step, a.log_base); }
+    if (a.film) film.begin(a.film->every, st->step, a.log_base);
     for (int step = 0; step < a.nsteps; ++step) {
         if (st->invalid != 0 || (a.honor_stop && (st->converged || st->step >= st->max_it))) break;     // block-uniform
         const double dt = st->dt;
@@ -156,7 +156,7 @@ __device__ __forceinline__ const StepState* small_steps_body(const SmallArgs& a,
         committed += 1;
         if (a.probe) probe_record_block<EOS>(*a.probe, q0, nc, w, st->step - 1 - a.log_base, a.log_cap, P);     // block-uniform; reads only
         if (a.extrema && ext.due(st->step)) {           // likewise, at the armed stride
-            extrema_record_block<EOS>(ext.x, q0, T, D.Nx, D.Ny, nc, w, ext.slot, P);
+            extrema_record_block<EOS>(ext_x, q0, T, D.Nx, D.Ny, nc, w, ext.slot, P);
             ext.advance();
         }
         if (a.film && film.due(st->step)) {             // likewise; the row vectors go through F, dead until the next closure pass
