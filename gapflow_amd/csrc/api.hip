@@ -31,6 +31,7 @@
 #include "region_kernels.hip"
 #include "line_kernels.hip"
 #include "resample_kernels.hip"
+#include "elastic_series_kernels.hip"
 
 using namespace gpf;
 
@@ -113,9 +114,10 @@ struct gpf_handle {
     // the batch in flight ([log_cap + 1][9 + nsx + nsy]) and the row scratch ([Nx][FILM_NV]), both allocated on first use (`narrow`:
     // GPF_FILM_NARROW was set then, 8-byte loads); the records of the last stepping call and their step counts on the host
     // `dev`: the FilmBlockArgs of the record buffer in device memory, for k_small_steps (written with the buffers, freed with them)
+    // `pending`: an elastic handle's closed step waits for gpf_elastic_update to record it, `pending_base` the count it began at
     struct { long long every = 0; int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
-             double* rec = nullptr; double* part = nullptr; FilmBlockArgs* dev = nullptr; bool narrow = false; std::vector<double> host;
-             std::vector<long long> steps; } integ;
+             double* rec = nullptr; double* part = nullptr; FilmBlockArgs* dev = nullptr; bool narrow = false; bool pending = false;
+             long long pending_base = 0; std::vector<double> host; std::vector<long long> steps; } integ;
     // weighted film integrals (api_weighted.inc): recording stride (0: not armed) and number of weight planes K; the planes on the
     // device in this handle's Layout ([K] planes, pitch and offset as topo's, ghost cells zero), the row scratch ([K][Nx][9]) and the
     // device records of the batch in flight ([log_cap + 1][K][9]), all allocated by gpf_weighted_set (`narrow`: GPF_FILM_NARROW was
@@ -140,6 +142,13 @@ struct gpf_handle {
     // `pending`: an elastic handle's closed step waits for gpf_elastic_update to record it, `pending_base` the count it began at
     struct { long long every = 0; ExtremaArgs a = {}; ExtremaArgs* dev = nullptr; bool narrow = false; bool pending = false; long long pending_base = 0;
              std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } extr;
+    // deformation series of an elastic handle (api_elastic_series.inc): recording stride (0: not armed); the device records
+    // ([log_cap + 1][6] doubles, [log_cap + 1][4] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was
+    // set then); the records of the last stepping call on the host.  `pending`, `pending_base`: as the extrema's -- every record
+    // is written behind gpf_elastic_update
+    struct { long long every = 0; double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
+             bool narrow = false; bool pending = false; long long pending_base = 0;
+             std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } eldef;
     // running field statistics (api_stats.inc): recording stride (0: not armed), the step count records are taken above, the
     // requested fields (bit 0 p, 1 rho, 2 jx, 3 jy) and the step count at which the window began; the accumulator planes
     // ([requested fields][mean m2 min max] planes of this handle's Layout) and the device's record of the window, both allocated by
@@ -386,7 +395,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->integ.dev, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->integ.dev, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->eldef.rec, h->eldef.cell, h->eldef.part, h->eldef.row_val, h->eldef.row_iy, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -1079,6 +1088,7 @@ static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long 
 #include "api_integrals.inc"
 #include "api_weighted.inc"
 #include "api_extrema.inc"
+#include "api_elastic_series.inc"
 #include "api_regions.inc"
 #include "api_lines.inc"
 #include "api_stats.inc"

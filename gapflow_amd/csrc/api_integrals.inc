@@ -6,8 +6,10 @@
 
 static int integrals_nrec(const gpf_handle* h) { return FILM_NSUM + h->integ.nsx + h->integ.nsy; }
 
-// The cases the reduction does not cover (series_refusal)
-static int integrals_refusal(const gpf_handle* h, const std::string& who) { return series_refusal(h, who, "film integrals", "the film integrals"); }
+// The cases the reduction does not cover: series_refusal's, with its classes and texts, except the elastic gap of one handle
+// (el.on).  Its gap is h->topo, the planes the kernels read anyway; only the moment of the record differs
+// (integrals_close_step_launch).  An elastic slab is refused as a slab.
+static int integrals_refusal(const gpf_handle* h, const std::string& who) { return series_refusal(h, who, "film integrals", "the film integrals", true); }
 
 // First and last interior row / column; a direction of extent 1 has the one section
 static void integrals_default_sections(gpf_handle* h) {
@@ -49,6 +51,7 @@ static int integrals_buffers(gpf_handle* h) {
 
 // A stepping call begins: its records replace those of the call before
 static int integrals_begin(gpf_handle* h) {
+    h->integ.pending = false;
     if (!h->integ.every) return GPF_OK;
     GPF_TRY(integrals_refusal(h, "gpf_step with film integrals armed"));
     h->integ.host.clear(); h->integ.steps.clear();
@@ -79,10 +82,38 @@ static int integrals_collect(gpf_handle* h, long long base, long long ran) {
     return series_collect(h->integ.every, h->integ.steps, base, ran, series_channel(h->integ.host, h->integ.rec, (size_t)integrals_nrec(h)));
 }
 
+// gpf_close_step of an elastic handle (el.on): its gap deforms after the step closes (gpf_elastic_update), so the closed step's
+// record waits for that call, as the extrema's does (extrema_close_step_launch), and holds the gap the handle holds with that
+// state.  Other handles' closed steps leave no film-integral record, as before.
+static int integrals_close_step_launch(gpf_handle* h) {
+    h->integ.pending = false;
+    if (!h->integ.every || !h->el.on) return GPF_OK;
+    GPF_TRY(integrals_begin(h));
+    h->integ.pending = true; h->integ.pending_base = h->host_step;
+    return GPF_OK;
+}
+
+// ... the step did not commit: nothing to wait for
+static void integrals_close_step_collect(gpf_handle* h, long long ran) {
+    if (ran < 1) h->integ.pending = false;
+}
+
+// gpf_elastic_update, behind its launches: the record of the step gpf_close_step committed just before, at the armed stride
+static int integrals_after_elastic_update(gpf_handle* h) {
+    if (!h->integ.pending) return GPF_OK;
+    h->integ.pending = false;
+    const long long base = h->integ.pending_base;
+    if (!h->integ.every || h->host_step != base + 1) return GPF_OK;
+    if (!series_due(h->integ.every, h->host_step)) return GPF_OK;
+    GPF_TRY(integrals_launch(h, h->host_step, base));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return integrals_collect(h, base, 1);
+}
+
 static int integrals_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
     GPF_TRY(series_free({(void**)&h->integ.rec, (void**)&h->integ.part, (void**)&h->integ.dev}));
-    h->integ.every = 0; h->integ.nsx = h->integ.nsy = 0;
+    h->integ.every = 0; h->integ.nsx = h->integ.nsy = 0; h->integ.pending = false;
     h->integ.host.clear(); h->integ.steps.clear();
     return GPF_OK;
 }
@@ -159,6 +190,15 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
     if (mode == 1 && !h->integ.every) return fail(GPF_ERR_STATE, "gpf_integrals_time: mode 1 needs armed integrals (gpf_integrals_set)");
     GPF_TRY(enter(h));
     SeriesAside aside(h, mode == 1 ? &h->integ.every : nullptr);
+    if (h->el.on) {         // an elastic handle: n stage-wise steps, each with its gpf_elastic_update and the record behind it
+        std::vector<double> host;
+        std::vector<long long> steps;
+        const int rc = series_time(h, "gpf_integrals_time", aside,
+                                   [&](long long) { return series_time_elastic_steps(h, n, [&] { series_time_keep(h->integ.host, h->integ.steps, host, steps); }); },
+                                   [&](long long, long long) { h->integ.host.swap(host); h->integ.steps.swap(steps); return (int)GPF_OK; }, ms);
+        h->prev_state_valid = false;        // (series_resync speaks of fused steps: a closed step leaves its working field in the other buffer)
+        return rc;
+    }
     GPF_TRY(integrals_begin(h));
     return series_time(h, "gpf_integrals_time", aside,
                        [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return integrals_launch(h, expect, base); }); },

@@ -1,5 +1,6 @@
 // Part of api.hip (included there, not compiled on its own): what the per-step recorders of a handle -- probes, film integrals,
-// weighted integrals, regions, lines, extrema, statistics (api_<name>.inc, included behind this file) -- have in common: the
+// weighted integrals, regions, lines, extrema, statistics, an elastic handle's deformation series (api_<name>.inc, included
+// behind this file) -- have in common: the
 // arithmetic of a stride's records, their way to the host and out of it, the alignment test of the 16-byte loads, the arguments
 // and the two launches of the row-reduced series (device side: series_rows.hpp), the cases the film reductions refuse, how
 // series are put aside for a call, the frame of the gpf_*_time diagnostics, and the cut of a small-grid batch.  A new series is named here in SeriesAside, series_forget_records and, if it cuts, small_batch_cut.
@@ -103,28 +104,29 @@ template <class Args> static void series_row_args(const gpf_handle* h, bool wide
 // ---- refusals ----------------------------------------------------------------------------------------------------------------
 // The cases the film reductions (film integrals, weighted integrals, regions, lines) do not cover, with the error class
 // gpf_probes_set / gpf_gap_profiles give them.  `what` names the series as a whole, `the_what` where it evaluates.
-static int series_refusal(const gpf_handle* h, const std::string& who, const char* what, const char* the_what) {
+// `elastic_gap_ok`: the series records an elastic handle's closed step behind gpf_elastic_update (the film integrals alone).
+static int series_refusal(const gpf_handle* h, const std::string& who, const char* what, const char* the_what, bool elastic_gap_ok = false) {
     if (h->E.halo[0] || h->E.halo[1]) return fail(GPF_ERR_STATE, who + ": this handle is a slab; " + what + " are not available on slabs");
     if (h->step_open) return fail(GPF_ERR_STATE, who + ": a stage-wise step is open; close it first");
     if (h->gp[0].set || h->gp[1].set || h->gp[2].set)
         return fail(GPF_ERR_INVALID, who + ": surrogate closures: " + the_what + " evaluate the analytic pressure and wall stress, which this handle replaces");
     if (h->cfg.thinning != GPF_THINNING_NONE) return fail(GPF_ERR_INVALID, who + ": shear thinning needs grad p (not supported)");
-    if (h->el.on || h->els.on) return fail(GPF_ERR_INVALID, who + ": an elastic handle steps stage-wise and deforms its gap between steps (not supported)");
+    if ((h->el.on && !elastic_gap_ok) || h->els.on) return fail(GPF_ERR_INVALID, who + ": an elastic handle steps stage-wise and deforms its gap between steps (not supported)");
     return GPF_OK;
 }
 
 // ---- series put aside for a call ---------------------------------------------------------------------------------------------
-// What arms each of the seven series -- the probes' count and the six strides -- remembered, and all of them disarmed except
+// What arms each of the eight series -- the probes' count and the seven strides -- remembered, and all of them disarmed except
 // `keep` (the address of one of these fields, or null: none).  restore() puts the values back; the destructor does if nobody
 // asked.  Every recorder returns at once while its series is disarmed, so this is all it takes to step without it.
 struct SeriesAside {
     gpf_handle* const h;
     const void* const keep;
     const int probes;
-    long long every[6];
+    long long every[7];
     bool restored = false;
-    std::array<long long*, 6> strides() const {
-        return {&h->integ.every, &h->weighted.every, &h->regions.every, &h->lines.every, &h->extr.every, &h->stats.every};
+    std::array<long long*, 7> strides() const {
+        return {&h->integ.every, &h->weighted.every, &h->regions.every, &h->lines.every, &h->extr.every, &h->stats.every, &h->eldef.every};
     }
     SeriesAside(gpf_handle* handle, const void* keep_armed) : h(handle), keep(keep_armed), probes(handle->probes.n) {
         if (keep != &h->probes.n) h->probes.n = 0;
@@ -156,6 +158,7 @@ static void series_forget_records(gpf_handle* h) {
     h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
     h->lines.host.clear(); h->lines.steps.clear();
     h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
+    h->eldef.host.clear(); h->eldef.cells.clear(); h->eldef.steps.clear();
 }
 
 // ---- the gpf_*_time diagnostics ----------------------------------------------------------------------------------------------
@@ -216,6 +219,33 @@ template <class Behind> static int series_time_steps(gpf_handle* h, int64_t n, l
         GPF_TRY(behind(base + i + 1));
     }
     return GPF_OK;
+}
+
+// n steps of an elastic handle as a host takes them: the stage-wise calls, then gpf_elastic_update, behind whose launches the
+// film integrals and the deformation series write the closed step's record (every call synchronises, so *ms of series_time is
+// the host's time too).  Every gpf_close_step begins its series' records afresh: `keep()` behind each update moves what the step
+// left to where the call's collect finds it.  Stops at a step that did not commit.
+template <class Keep> static int series_time_elastic_steps(gpf_handle* h, int64_t n, Keep&& keep) {
+    for (int64_t i = 0; i < n; ++i) {
+        GPF_TRY(gpf_open_step(h));
+        for (int stage = 0; stage < 2; ++stage) {
+            GPF_TRY(gpf_stage_closures(h));
+            GPF_TRY(gpf_stage_advance(h, stage));
+        }
+        gpf_scalars_t sc;
+        GPF_TRY(gpf_close_step(h, &sc));
+        if (sc.invalid) break;
+        GPF_TRY(gpf_elastic_update(h));
+        keep();
+    }
+    return GPF_OK;
+}
+
+// keep() of a series whose record is a channel of doubles and the step counts: appended to `host`, `steps` of the call
+static void series_time_keep(std::vector<double>& from, std::vector<long long>& from_steps, std::vector<double>& host, std::vector<long long>& steps) {
+    host.insert(host.end(), from.begin(), from.end());
+    steps.insert(steps.end(), from_steps.begin(), from_steps.end());
+    from.clear(); from_steps.clear();
 }
 
 // ---- a small grid's batch ----------------------------------------------------------------------------------------------------

@@ -39,6 +39,8 @@ RegionSeries = namedtuple('RegionSeries', ('step', 'time', 'names') + _lib.WEIGH
 RegionSeries.__doc__ = """Time series of Problem.regions: step, time (nrecords,), names (the K regions'), per integrand an array (nrecords, K), cells (nrecords, K) int64, area = cells dx dy, bbox (nrecords, K, 4) = (ix_min, ix_max, iy_min, iy_max), -1 for an empty region."""
 FieldExtrema = namedtuple('FieldExtrema', ('step', 'time') + _lib.EXTREMA_NAMES + ('cells', 'index'))
 FieldExtrema.__doc__ = """Time series of Problem.extrema: step, time and the seven values (nrecords,), cells (nrecords, 7, 2) -- (ix, iy) of each value in the ghosted index space --, index: name -> position along the cells' second axis."""
+ElasticSeries = namedtuple('ElasticSeries', ('step', 'time') + _lib.ELASTIC_SERIES_NAMES + ('cells',))
+ElasticSeries.__doc__ = """Time series of Problem.elastic_series: step, time, the four sums and d_max, d_min (nrecords,), cells (nrecords, 2, 2) -- (ix, iy) of d_max, then of d_min, in the ghosted index space."""
 
 
 def _termination_signals():
@@ -141,6 +143,9 @@ class Problem:
         self._extrema_every = None
         if options.get('extrema'):                  # options.extrema (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_extrema(options['extrema'])
+        self._elastic_series_every = None
+        if options.get('elastic_series'):           # options.elastic_series (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
+            self.set_elastic_series(options['elastic_series'])
         self._stats_every = None
         if options.get('statistics'):               # options.statistics (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_statistics(options['statistics'], options.get('statistics_fields', _lib.STATS_FIELDS), options.get('statistics_after', 0))
@@ -188,6 +193,7 @@ class Problem:
         _keep_probes(input_dict, ymlstring)
         _keep_integrals(input_dict, ymlstring)
         _keep_extrema(input_dict, ymlstring)
+        _keep_elastic_series(input_dict, ymlstring)
         _keep_weighted(input_dict, ymlstring, base_dir)
         _keep_statistics(input_dict, ymlstring)
         _keep_regions(input_dict, ymlstring)
@@ -600,8 +606,8 @@ class Problem:
             raise NotImplementedError("integrals: surrogate (GP) closures replace the pressure and wall stress the integrals evaluate")
         if self._cfg.thinning:
             raise NotImplementedError("integrals: shear thinning needs grad p, which the reduction does not model")
-        if self._elastic or self.topo.elastic:
-            raise NotImplementedError("integrals: an elastic gap steps stage-wise and deforms between steps (not supported)")
+        if self.topo.elastic and not self._elastic:
+            raise NotImplementedError("integrals: this problem's elastic gap is deformed by its caller, not on the device (not supported)")
 
     def set_integrals(self, every=1, sections_x=None, sections_y=None):
         """Record whole-film integrals of the committed state after every step whose count is a multiple of `every`, on the
@@ -619,7 +625,10 @@ class Problem:
         kernel the record is written inside the batch (``integrals_in_batch``): no launch is cut, whatever the stride.
         A step that is rolled back as invalid leaves no record.  Starts a new series (see ``integrals``).  Checkpoints do not
         carry the series: a problem restored from one whose options hold `integrals` has them armed again and its series
-        begins at the restart step.  Not available with surrogate closures, shear thinning or an elastic gap."""
+        begins at the restart step.  With an elastic gap the record of a step is taken behind the deformation that follows it
+        (`update()` and `run()` step such a problem stage-wise): it pairs the committed state with the deformed gap `topo.h`
+        shows after that step, bit for bit what ``film_integrals()`` gives then.  Not available with surrogate closures or
+        shear thinning."""
         self._integrals_refusal()
         every = _integral_stride(every)
         sx = _integral_sections(sections_x, self.grid['Nx'], 'sections_x')
@@ -1104,6 +1113,90 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'extrema.npz'), names=np.array(sorted(index, key=index.get)), **s)
 
     # -------------------------------------------------------------------------------------
+    # deformation series of an elastic gap (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _elastic_series_refusal(self):
+        if not self._elastic:
+            raise NotImplementedError("elastic series: this problem has no elastic gap deformed on the device (properties.elastic)")
+
+    def set_elastic_series(self, every=1):
+        """Record how far the wall gives way after every step whose count is a multiple of `every`, on the device, behind the
+        deformation that follows the step (an elastic problem steps stage-wise, `update()` and `run()` alike).
+
+        Per record, over the interior cells 1..Nx x 1..Ny, with d the deformation the device holds (what `topo.deformation`
+        shows after that step), p the pressure ``integrals`` sums as `load` and h the deformed gap: d_sum (the displaced
+        volume), d2_sum (sum of d d: the RMS deflection is sqrt(d2_sum / area)), p_d (sum of p d: twice the elastic work of a
+        linear half-space -- the factor 1/2 is yours), h_sum (the film's volume), each summed in the order ``integrals`` adds
+        and multiplied by dx dy once; and d_max, d_min with their cells (ix, iy) of the ghosted index space, ties going to the
+        smallest ix, then the smallest iy, as in ``extrema``.  The same state, gap and deformation give the same bits whatever
+        the stride.  A step that is rolled back as invalid leaves no record.  Starts a new series (see ``elastic_series``).
+        Checkpoints do not carry the series: a problem restored from one whose options hold `elastic_series` has it armed again
+        and its series begins at the restart step.  May be armed beside every other series an elastic problem accepts.  Not
+        available without an elastic gap."""
+        self._elastic_series_refusal()
+        every = _elastic_series_stride(every, allow_zero=False)
+        _lib.check(self._lib.gpf_elastic_series_set(self._h, every))
+        self._elastic_series_every = every
+        self._elastic_series_steps, self._elastic_series_times, self._elastic_series_values, self._elastic_series_cells = [], [], [], []
+
+    def clear_elastic_series(self):
+        """Stop recording and drop the series."""
+        if self._elastic_series_every is not None:
+            _lib.check(self._lib.gpf_elastic_series_clear(self._h))
+        self._elastic_series_every = None
+
+    @property
+    def elastic_series(self):
+        """ElasticSeries(step, time, d_sum, d2_sum, p_d, h_sum, d_max, d_min, cells) of every recorded step since
+        set_elastic_series (or _pre_run), across `update()` and `run()` calls; None when the series is not armed.
+        cells[n, 0] is the (ix, iy) of d_max, cells[n, 1] that of d_min."""
+        if self._elastic_series_every is None:
+            return None
+        nq = len(_lib.ELASTIC_SERIES_NAMES)
+        vals = np.concatenate(self._elastic_series_values) if self._elastic_series_values else np.empty((0, nq))
+        cells = np.concatenate(self._elastic_series_cells) if self._elastic_series_cells else np.empty((0, 2, 2), dtype=np.int32)
+        return ElasticSeries(np.array(self._elastic_series_steps, dtype=np.int64), np.array(self._elastic_series_times, dtype=np.float64),
+                             *[vals[:, k] for k in range(nq)], cells)
+
+    def film_elastic(self):
+        """The same record for the current state, gap and deformation, as a dict: the six names of ``elastic_series`` and
+        `d_max_cell`, `d_min_cell` = (ix, iy).  Bit for bit what a step leaving them would have recorded.  Armed or not.
+        Reads only."""
+        self._elastic_series_refusal()
+        self._sync_to_device()
+        vals = np.empty(len(_lib.ELASTIC_SERIES_NAMES))
+        cells = np.zeros((2, 2), dtype=np.int32)
+        _lib.check(self._lib.gpf_elastic_series_now(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32))))
+        res = {name: np.float64(vals[k]) for k, name in enumerate(_lib.ELASTIC_SERIES_NAMES)}
+        res['d_max_cell'] = (int(cells[0, 0]), int(cells[0, 1]))
+        res['d_min_cell'] = (int(cells[1, 0]), int(cells[1, 1]))
+        return res
+
+    def _collect_elastic_series(self, entries, before):
+        """The records of the step that took the step count from `before` through `entries` (its committed step)."""
+        if self._elastic_series_every is None or not entries:
+            return
+        n = _integral_records(before, len(entries), self._elastic_series_every)
+        nq = len(_lib.ELASTIC_SERIES_NAMES)
+        vals = np.empty((n, nq))
+        cells = np.zeros((n, 2, 2), dtype=np.int32)
+        steps = np.zeros(n, dtype=np.int64)
+        have = C.c_int64(0)
+        _lib.check(self._lib.gpf_elastic_series_read(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                                     steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
+        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._elastic_series_every == 0]
+        if have.value != n or steps.tolist() != want:
+            raise _lib.GapflowHipError(f"elastic series: {have.value} records of steps {steps.tolist()} for the committed steps "
+                                       f"{before + 1}..{before + len(entries)} at stride {self._elastic_series_every}")
+        self._elastic_series_steps.extend(want)
+        self._elastic_series_times.extend(entries[s - before - 1].simtime for s in want)
+        self._elastic_series_values.append(vals)
+        self._elastic_series_cells.append(cells)
+
+    def _write_elastic_series(self):
+        np.savez(os.path.join(self.outdir, 'elastic_series.npz'), **self.elastic_series._asdict())
+
+    # -------------------------------------------------------------------------------------
     # running field statistics (no reference counterpart; DESIGN.md 3.3j)
     # -------------------------------------------------------------------------------------
     def set_statistics(self, every=1, fields=_lib.STATS_FIELDS, after=0):
@@ -1199,6 +1292,8 @@ class Problem:
             self._lines_steps, self._lines_times, self._lines_data = [], [], []
         if self._extrema_every is not None:
             self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
+        if self._elastic_series_every is not None:
+            self._elastic_series_steps, self._elastic_series_times, self._elastic_series_values, self._elastic_series_cells = [], [], [], []
 
     def _absorb(self, entries):
         """Fold the per-step records of a batch into the host-side mirror of the run state."""
@@ -1290,6 +1385,9 @@ class Problem:
         self._absorb([sc])
         self._collect_probes([sc])
         self._collect_extrema([sc], before)     # (an elastic gap's record was taken behind gpf_elastic_update, of the deformed gap)
+        if self._elastic:                       # likewise its film integrals and its deformation series
+            self._collect_integrals([sc], before)
+            self._collect_elastic_series([sc], before)
         self._mark_device_advanced()
         # the derived fields on the device ARE what the reference's field objects hold now: the closures of the corrector stage
         # (problem.py:531-560; neither the averaging nor Topography.update re-evaluates them)
@@ -1392,6 +1490,8 @@ class Problem:
                 self._write_lines()
             if self._extrema_every is not None:
                 self._write_extrema()
+            if self._elastic_series_every is not None:
+                self._write_elastic_series()
             if self._stats_every is not None:
                 self._write_statistics()
             for name, m in self._gp_models.items():  # problem.py:490-503
@@ -1786,6 +1886,26 @@ def _keep_extrema(input_dict, ymlstring):
         return
     if opts.get('extrema') is not None:
         input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
+
+
+def _elastic_series_stride(every, allow_zero=True):
+    low = 0 if allow_zero else 1
+    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
+        raise ValueError(f"elastic series: the stride must be an integer >= {low}, got {every!r}")
+    return int(every)
+
+
+def _keep_elastic_series(input_dict, ymlstring):
+    """`options.elastic_series: N` (the stride; 0 or absent: off) is this project's own key: read from the YAML text and set beside
+    the sanitised ones, like the extrema's -- only when given, so that every other input's dictionaries stay as they are.
+    Checked here, on the host."""
+    import yaml
+    raw = yaml.full_load(ymlstring) or {}
+    opts = raw.get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    if opts.get('elastic_series') is not None:
+        input_dict['options']['elastic_series'] = _elastic_series_stride(opts['elastic_series'])
 
 
 def _statistics_stride(v, key, low):

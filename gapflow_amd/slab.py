@@ -459,6 +459,14 @@ class SlabProblem:
         """Field extrema are taken on unsliced problems only."""
         raise NotImplementedError("extrema: not available on a SlabProblem")
 
+    def set_elastic_series(self, *args, **kwargs):
+        """The deformation series is recorded on unsliced problems only."""
+        raise NotImplementedError("elastic series: not available on a SlabProblem")
+
+    def film_elastic(self, *args, **kwargs):
+        """The deformation series is taken on unsliced problems only."""
+        raise NotImplementedError("elastic series: not available on a SlabProblem")
+
     def set_statistics(self, *args, **kwargs):
         """Running field statistics are kept on unsliced problems only."""
         raise NotImplementedError("statistics: not available on a SlabProblem")
@@ -487,6 +495,8 @@ class SlabProblem:
             raise NotImplementedError("lines: not available on a SlabProblem")       # options.lines: as set_lines
         if (input_dict.get('options') or {}).get('extrema'):                         # (0: off, as on a Problem)
             raise NotImplementedError("extrema: not available on a SlabProblem")     # options.extrema: as set_extrema
+        if (input_dict.get('options') or {}).get('elastic_series'):                  # (0: off, as on a Problem)
+            raise NotImplementedError("elastic series: not available on a SlabProblem")      # options.elastic_series: as set_elastic_series
         if (input_dict.get('options') or {}).get('statistics'):                      # (0: off, as on a Problem)
             raise NotImplementedError("statistics: not available on a SlabProblem")  # options.statistics: as set_statistics
         import torch
@@ -616,8 +626,10 @@ class SlabProblem:
     @classmethod
     def from_string(cls, text, device=0, dist=None, base_dir=None):
         from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted, _keep_statistics, _keep_regions, _keep_lines
+        from .problem import _keep_elastic_series
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
+        _keep_elastic_series(d, text)               # options.elastic_series: refused below
         _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
         _keep_probes(d, text)                       # options.probes: refused below
         _keep_integrals(d, text)                    # options.integrals: refused below

@@ -405,9 +405,10 @@ int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes);
 int gpf_checkpoint_pack_probe(gpf_handle* h, int reps, double* ms_per_pass);
 
 /* ---- the per-step series and their gpf_*_time diagnostics ------------------------------------------------------------------ */
-/* A handle records up to seven series behind its committed steps: point probes, film integrals, weighted film integrals,
- * regions, line profiles, field extrema and running statistics (the sections below).  Each has a diagnostic gpf_<series>_time
- * that enqueues n steps as gpf_step does and reports the time on the handle's stream.  ONE RULE holds for all seven:
+/* A handle records up to eight series behind its committed steps: point probes, film integrals, weighted film integrals,
+ * regions, line profiles, field extrema, running statistics and, with an elastic gap, the deformation series (the sections
+ * below).  Each has a diagnostic gpf_<series>_time that enqueues n steps as gpf_step does (an elastic handle's: as its host
+ * does, stage-wise) and reports the time on the handle's stream.  ONE RULE holds for all eight:
  *   - the call puts aside every series but the one it times, and that one too in the modes that do not record: nothing else
  *     is launched behind the steps, and what was armed is armed again, unchanged, when the call returns (also on an error);
  *   - it leaves no records of any other series for their _read calls (0 records; probes: 0 steps): it is a stepping call in
@@ -470,7 +471,8 @@ int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms);
  *                        starts with empty records.  ix / iy NULL (or nsx / nsy <= 0): the default sections.  GPF_ERR_INVALID
  *                        with a message that names the offending section for a row outside 1..Nx, a column outside 1..Ny or
  *                        more than 8; GPF_ERR_STATE on a slab and while a stage-wise step is open; GPF_ERR_INVALID with
- *                        surrogate closures, shear thinning or an elastic gap (such handles step stage-wise).
+ *                        surrogate closures or shear thinning.  An elastic gap is recorded behind gpf_elastic_update (see
+ *                        "deformation series", below: WHEN).
  *   gpf_integrals_clear  disarms and frees the buffers.
  *   gpf_integrals_read   the records of the LAST gpf_step call, [record][9 + nsx + nsy], and the step count of each in
  *                        steps_out (either may be NULL); *n_records how many the call left, min(*n_records, capacity_records)
@@ -590,6 +592,52 @@ int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14]);
  * mode 0 no recording, 1 recording at the armed stride (tools/extrema_time.py).  The other series: the one rule of the
  * gpf_*_time diagnostics (before the point probes). */
 int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
+/* ---- deformation series of an elastic gap (no reference counterpart: its users download the gap after every step) ---------- */
+/* What the wall gives way by under the film it carries, reduced on the device.  A record is six doubles and two cells, taken
+ * over the interior cells 1..Nx x 1..Ny with d = the deformation plane the handle holds (GPF_FIELD_DEFORMATION), p = the
+ * pressure the film integrals' `load` sums (csrc/closures.hpp film_pressure of the committed density) and h = the deformed gap:
+ *   0 d_sum     sum of d, times dx dy: the displaced volume
+ *   1 d2_sum    sum of d d, times dx dy (RMS deflection: sqrt(d2_sum / area))
+ *   2 p_d       sum of p d, times dx dy (the elastic work of a linear half-space is half of it; the factor is the caller's)
+ *   3 h_sum     sum of h, times dx dy: the film's volume
+ *   4 d_max, 5 d_min   the largest and the smallest d, each with its cell (ix, iy) of the ghosted index space
+ * Host layout: values [record][6] doubles, cells [record][2][2] int32 (d_max's ix, iy, then d_min's).  The sums are added in the
+ * film integrals' order (k_film_partial's pair walk, its fold tree, k_film_fold's row loop), the products d d and p d rounded on
+ * their own, and multiplied by dx dy once; the extrema are ordered by the field extrema's one comparison (value, then the
+ * smaller ix, then the smaller iy).  A record is a pure function of (q, gap, deformation): no floating-point atomics, the same
+ * bits whatever the stride, behind a step or from gpf_elastic_series_now.  Recording only reads.
+ * WHEN: an elastic gap deforms after its step closes (gpf_elastic_update), so the record of a closed step is pending at
+ * gpf_close_step and written behind the launches of the gpf_elastic_update that follows, with the state, the gap and the
+ * deformation the handle then holds.  A step that did not commit leaves none, nor does one whose update is never called.  The
+ * film integrals of an elastic handle (gpf_integrals_*, above) are recorded at the same moment by the same rule: there, and only
+ * there, gpf_close_step + gpf_elastic_update leave a film-integral record, and gpf_integrals_in_batch is 0.
+ *   gpf_elastic_series_set    arms recording after every committed step whose new step count is a multiple of `every` (>= 1,
+ *                             else GPF_ERR_INVALID) and starts with empty records.  GPF_ERR_STATE on a handle without an elastic
+ *                             gap ("no elastic gap"), on a slab and while a stage-wise step is open; GPF_ERR_INVALID on a handle
+ *                             whose pressure comes from a surrogate.
+ *   gpf_elastic_series_clear  disarms and frees the buffers.
+ *   gpf_elastic_series_read   the records of the LAST gpf_close_step + gpf_elastic_update (one closed step) and the step count
+ *                             of each in steps_out (values, cells, steps_out may be NULL); *n_records how many the call left,
+ *                             min(*n_records, capacity_records) are copied.  GPF_ERR_STATE unless armed.
+ *   gpf_elastic_series_now    the same record for the state, gap and deformation the handle holds, armed or not; GPF_ERR_STATE
+ *                             on an invalid run state.
+ * Where they are written: k_eldef_partial (one workgroup per interior row, 3 planes read: rho, h, d) + k_eldef_fold
+ * (csrc/elastic_series_kernels.hip), guarded by the device's run state like every recording kernel.  Buffers ((log_cap + 1)
+ * records and a row scratch) are allocated on first use and freed by gpf_elastic_series_clear / gpf_destroy once the stream is
+ * idle.  Pairs of columns are fetched with one 16-byte load per plane where the three planes are aligned for it and with 8-byte
+ * loads otherwise; GPF_FILM_NARROW (read when the buffers are allocated) asks for the 8-byte loads regardless -- a test switch;
+ * the records are the same in every bit. */
+int gpf_elastic_series_set(gpf_handle* h, int64_t every);
+int gpf_elastic_series_clear(gpf_handle* h);
+int gpf_elastic_series_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_elastic_series_now(gpf_handle* h, double values[6], int32_t cells[4]);
+/* Diagnostic: n steps (1..4096) as a host takes them on an elastic handle -- gpf_open_step, two stages, gpf_close_step,
+ * gpf_elastic_update per step --, *ms from the first launch to the last on the handle's stream (every such call synchronises:
+ * the host's share is part of it), with mode 0 no recording, 1 recording at the armed stride (tools/elastic_series_time.py).
+ * gpf_integrals_time steps an elastic handle the same way.  The other series: the one rule of the gpf_*_time diagnostics
+ * (before the point probes). */
+int gpf_elastic_series_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- running field statistics (no reference counterpart: its users download q after every step and average on the host) ---- */
 /* WHERE on the film something happened over a run: per cell of the GHOSTED grid (Nx+2) x (Ny+2) -- the shape q has -- and per
