@@ -248,5 +248,9 @@ class OracleProblem:
             mask = g[f'bc_{side}_{bc_type}']
             adj = p[mask, :, -2:-1] if direction > 0 else p[mask, :, 1:2]
         if bc_type == 'D':
-            return (g[f'bc_{side}_D_val'] - 0.5 * adj) / 0.5
+            # The reference reads bc_<side>_D_val before it looks at the mask (problem.py:739-753) and so raises KeyError for an edge
+            # without a Dirichlet component.  gapflow_amd runs such an edge -- an extension, meaning "copy the adjacent cell" for
+            # every component -- so the value is looked up only where the mask selects something.
+            target = g[f'bc_{side}_D_val'] if any(mask) else 0.0
+            return (target - 0.5 * adj) / 0.5
         return (0.5 * adj) / 0.5
