@@ -29,8 +29,8 @@ from datetime import datetime
 import numpy as np
 
 from . import _lib
-from .problem import (FilmIntegrals, Problem, _in_main_thread, _integral_records, _integral_sections, _integral_stride,
-                      _termination_signals)
+from .problem import Problem, _film_series, _in_main_thread, _termination_signals
+from .series import SERIES, _Series, _integral_sections, _integral_stride
 
 
 def member_tier(nx, ny):
@@ -63,21 +63,9 @@ def _refusal(p):
                                      f"({_lib.SMALL_GRID_DOUBLES_PER_CELL} doubles per cell, ghost cells included, in "
                                      f"{_lib.SMALL_GRID_LDS_BYTES // 1024} KB) nor the workspace tier (at most "
                                      f"{_lib.MID_GRID_MAX_CELLS} cells, ghost cells included)")
-    if p._integral_every is not None:
-        return NotImplementedError, "film integrals are armed on it (they cut the batch per member): clear_integrals(), or run it alone"
-    if getattr(p, '_weighted_every', None) is not None:        # (getattr: a Problem made without __init__ has no such attribute)
-        return NotImplementedError, ("weighted integrals are armed on it (they cut the batch per member): clear_weighted_integrals(), "
-                                     "or run it alone")
-    if getattr(p, '_stats_every', None) is not None:
-        return NotImplementedError, "statistics are armed on it (they cut the batch per member): clear_statistics(), or run it alone"
-    if getattr(p, '_regions_every', None) is not None:
-        return NotImplementedError, "regions are armed on it (they cut the batch per member): clear_regions(), or run it alone"
-    if getattr(p, '_lines_every', None) is not None:
-        return NotImplementedError, "lines are armed on it (they cut the batch per member): clear_lines(), or run it alone"
-    if p._probe_cells is not None:
-        return NotImplementedError, "probes are armed on it (their records need per-member slots): clear_probes(), or run it alone"
-    if p._extrema_every is not None:
-        return NotImplementedError, "extrema are armed on it (their records need per-member slots): clear_extrema(), or run it alone"
+    for row in sorted((r for r in SERIES if r.refusal), key=lambda r: r.refusal[0]):
+        if getattr(p, row.marker, None) is not None:            # (getattr: a Problem made without __init__ may lack the attribute)
+            return NotImplementedError, f"{row.noun} are armed on it ({row.refusal[1]}): {row.clear}(), or run it alone"
     return None
 
 
@@ -306,7 +294,7 @@ class Ensemble:
         _lib.check(self._lib.gpf_ensemble_integrals_set(self._e, every, len(ax), ax.ctypes.data_as(i32p) if len(ax) else None,
                                                         len(ay), ay.ctypes.data_as(i32p) if len(ay) else None))
         self._integral_every, self._integral_sections = every, layout
-        self._integral_series = [([], [], []) for _ in self.problems]       # per member: steps, times, record blocks
+        self._integral_series = [_Series(f'Ensemble integrals: member {i}', every) for i in range(len(self.problems))]
 
     def clear_integrals(self):
         """Stop recording and drop the series."""
@@ -316,31 +304,16 @@ class Ensemble:
 
     def _collect_integrals(self, i, entries, before):
         """Member i's records of the call that took its step count from `before` through `entries` (its committed steps)."""
-        if self._integral_every is None or not entries:
+        if self._integral_every is None:
             return
-        every = self._integral_every
-        n = _integral_records(before, len(entries), every)
         sx, sy = self._integral_sections[i]
-        out = np.empty((n, len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy)))
-        steps = np.zeros(n, dtype=np.int64)
-        have = C.c_int64(0)
-        _lib.check(self._lib.gpf_ensemble_integrals_read(self._e, i, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
-        want = [s for s in range(before + 1, before + len(entries) + 1) if s % every == 0]
-        if have.value != n or steps.tolist() != want:
-            raise _lib.GapflowHipError(f"Ensemble integrals: member {i}: {have.value} records of steps {steps.tolist()} for the committed "
-                                       f"steps {before + 1}..{before + len(entries)} at stride {every}")
-        series = self._integral_series[i]
-        series[0].extend(want)
-        series[1].extend(entries[s - before - 1].simtime for s in want)
-        series[2].append(out)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_ensemble_integrals_read(self._e, i, _lib.as_dp(b[0]), n, steps, have))
+        self._integral_series[i].collect(read, entries, before, [((len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy),), np.float64)])
 
     def _member_integrals(self, i):
-        sx, sy = self._integral_sections[i]
-        steps, times, blocks = self._integral_series[i]
-        ns = len(_lib.INTEGRAL_SUMS)
-        data = np.concatenate(blocks) if blocks else np.empty((0, ns + len(sx) + len(sy)))
-        return FilmIntegrals(np.array(steps, dtype=np.int64), np.array(times, dtype=np.float64), *[data[:, k] for k in range(ns)],
-                             data[:, ns:ns + len(sx)], data[:, ns + len(sx):], np.array(sx, dtype=np.int64), np.array(sy, dtype=np.int64))
+        return _film_series(self._integral_series[i], *self._integral_sections[i])
 
     @property
     def integrals(self):

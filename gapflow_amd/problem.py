@@ -24,6 +24,9 @@ import numpy as np
 from . import _lib
 from . import __version__
 from .io import read_yaml_input, write_yaml, create_output_directory, history_to_csv
+from .series import (SERIES, _Series, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
+                     _integral_stride, _line_centre, _line_entries, _line_span, _lines_stride, _probe_cells, _region_entries,
+                     _regions_stride, _statistics_fields, _statistics_stride, _stride, _weight_planes, _weighted_stride)
 from .topography import Topography
 from .stress import Pressure, WallStress, BulkStress
 
@@ -41,6 +44,14 @@ FieldExtrema = namedtuple('FieldExtrema', ('step', 'time') + _lib.EXTREMA_NAMES 
 FieldExtrema.__doc__ = """Time series of Problem.extrema: step, time and the seven values (nrecords,), cells (nrecords, 7, 2) -- (ix, iy) of each value in the ghosted index space --, index: name -> position along the cells' second axis."""
 ElasticSeries = namedtuple('ElasticSeries', ('step', 'time') + _lib.ELASTIC_SERIES_NAMES + ('cells',))
 ElasticSeries.__doc__ = """Time series of Problem.elastic_series: step, time, the four sums and d_max, d_min (nrecords,), cells (nrecords, 2, 2) -- (ix, iy) of d_max, then of d_min, in the ghosted index space."""
+
+
+def _film_series(rec, sx, sy):
+    """FilmIntegrals of the records the _Series `rec` holds, taken with the flow sections sx, sy (Problem's and an Ensemble member's)."""
+    ns = len(_lib.INTEGRAL_SUMS)
+    data = rec.stacked(0, (ns + len(sx) + len(sy),))
+    return FilmIntegrals(rec.step_array(), rec.time_array(), *[data[:, k] for k in range(ns)], data[:, ns:ns + len(sx)],
+                         data[:, ns + len(sx):], np.array(sx, dtype=np.int64), np.array(sy, dtype=np.int64))
 
 
 def _termination_signals():
@@ -189,16 +200,7 @@ class Problem:
     def from_string(cls, ymlstring, device=0, init_from=None, base_dir=None):
         with _io.StringIO(ymlstring) as f:
             input_dict = read_yaml_input(f)
-        _keep_checkpoint_freq(input_dict, ymlstring)
-        _keep_probes(input_dict, ymlstring)
-        _keep_integrals(input_dict, ymlstring)
-        _keep_extrema(input_dict, ymlstring)
-        _keep_elastic_series(input_dict, ymlstring)
-        _keep_weighted(input_dict, ymlstring, base_dir)
-        _keep_statistics(input_dict, ymlstring)
-        _keep_regions(input_dict, ymlstring)
-        _keep_lines(input_dict, ymlstring)
-        _keep_init_from(input_dict, ymlstring, base_dir)
+        _keep_own_options(input_dict, ymlstring, base_dir)
         if init_from is not None:
             input_dict['options']['init_from'] = os.path.abspath(os.fspath(init_from))
         return cls._from_dict(input_dict, device=device)
@@ -557,8 +559,7 @@ class Problem:
         iy = np.ascontiguousarray(cells[:, 1], dtype=np.int32)
         i32p = C.POINTER(C.c_int32)
         _lib.check(self._lib.gpf_probes_set(self._h, len(cells), ix.ctypes.data_as(i32p), iy.ctypes.data_as(i32p), int(bool(pressure))))
-        self._probe_cells, self._probe_pressure = cells, bool(pressure)
-        self._probe_steps, self._probe_times, self._probe_data = [], [], []
+        self._probe_cells, self._probe_pressure, self._probe_rec = cells, bool(pressure), _Series('probes')
 
     def clear_probes(self):
         """Stop recording and drop the series."""
@@ -573,25 +574,19 @@ class Problem:
         the same steps; p is None unless pressure was asked for."""
         if self._probe_cells is None:
             return None
-        n, nv = len(self._probe_cells), 4 if self._probe_pressure else 3
-        data = np.concatenate(self._probe_data) if self._probe_data else np.empty((0, n, nv))
-        return ProbeSeries(np.array(self._probe_steps, dtype=np.int64), np.array(self._probe_times, dtype=np.float64),
-                           self._probe_cells.copy(), data[:, :, 0], data[:, :, 1], data[:, :, 2], data[:, :, 3] if nv == 4 else None)
+        rec, nv = self._probe_rec, 4 if self._probe_pressure else 3
+        data = rec.stacked(0, (len(self._probe_cells), nv))
+        return ProbeSeries(rec.step_array(), rec.time_array(), self._probe_cells.copy(), data[:, :, 0], data[:, :, 1], data[:, :, 2],
+                           data[:, :, 3] if nv == 4 else None)
 
-    def _collect_probes(self, entries):
+    def _collect_probes(self, entries, before=None):
         """The probe records of the stepping call that returned `entries` (its committed steps' scalar records)."""
-        if self._probe_cells is None or not entries:
+        if self._probe_cells is None:
             return
-        n, nv = len(self._probe_cells), 4 if self._probe_pressure else 3
-        out = np.empty((len(entries), n, nv))
-        first, have = C.c_int64(0), C.c_int64(0)
-        _lib.check(self._lib.gpf_probes_read(self._h, _lib.as_dp(out), len(entries), C.byref(first), C.byref(have)))
-        if have.value != len(entries) or first.value != entries[0].step:
-            raise _lib.GapflowHipError(f"probes: {have.value} records from step {first.value} for {len(entries)} committed steps "
-                                       f"from step {entries[0].step}")
-        self._probe_steps.extend(int(e.step) for e in entries)
-        self._probe_times.extend(e.simtime for e in entries)
-        self._probe_data.append(out)
+
+        def read(out, n, first, have):
+            _lib.check(self._lib.gpf_probes_read(self._h, _lib.as_dp(out), n, first, have))
+        self._probe_rec.collect_every_step(read, entries, (len(self._probe_cells), 4 if self._probe_pressure else 3))
 
     def _write_probes(self):
         s = self.probes
@@ -636,8 +631,7 @@ class Problem:
         ax, ay = np.array(sx, dtype=np.int32), np.array(sy, dtype=np.int32)
         i32p = C.POINTER(C.c_int32)
         _lib.check(self._lib.gpf_integrals_set(self._h, every, len(sx), ax.ctypes.data_as(i32p), len(sy), ay.ctypes.data_as(i32p)))
-        self._integral_every, self._integral_sections = every, (sx, sy)
-        self._integral_steps, self._integral_times, self._integral_data = [], [], []
+        self._integral_every, self._integral_sections, self._integral_rec = every, (sx, sy), _Series('integrals', every)
 
     def clear_integrals(self):
         """Stop recording and drop the series."""
@@ -664,12 +658,7 @@ class Problem:
         set_integrals (or _pre_run), across `update()` and `run()` calls; None when no integrals are armed."""
         if self._integral_every is None:
             return None
-        sx, sy = self._integral_sections
-        ns = len(_lib.INTEGRAL_SUMS)
-        data = np.concatenate(self._integral_data) if self._integral_data else np.empty((0, ns + len(sx) + len(sy)))
-        return FilmIntegrals(np.array(self._integral_steps, dtype=np.int64), np.array(self._integral_times, dtype=np.float64),
-                             *[data[:, k] for k in range(ns)], data[:, ns:ns + len(sx)], data[:, ns + len(sx):],
-                             np.array(sx, dtype=np.int64), np.array(sy, dtype=np.int64))
+        return _film_series(self._integral_rec, *self._integral_sections)
 
     def film_integrals(self):
         """The same record for the current state, as a dict of the names of ``integrals`` (flow_x, flow_y arrays over the
@@ -688,21 +677,13 @@ class Problem:
 
     def _collect_integrals(self, entries, before):
         """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
-        if self._integral_every is None or not entries:
+        if self._integral_every is None:
             return
-        n = _integral_records(before, len(entries), self._integral_every)
         sx, sy = self._integral_sections
-        out = np.empty((n, len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy)))
-        steps = np.zeros(n, dtype=np.int64)
-        have = C.c_int64(0)
-        _lib.check(self._lib.gpf_integrals_read(self._h, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
-        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._integral_every == 0]
-        if have.value != n or steps.tolist() != want:
-            raise _lib.GapflowHipError(f"integrals: {have.value} records of steps {steps.tolist()} for the committed steps "
-                                       f"{before + 1}..{before + len(entries)} at stride {self._integral_every}")
-        self._integral_steps.extend(want)
-        self._integral_times.extend(entries[s - before - 1].simtime for s in want)
-        self._integral_data.append(out)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_integrals_read(self._h, _lib.as_dp(b[0]), n, steps, have))
+        self._integral_rec.collect(read, entries, before, [((len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy),), np.float64)])
 
     def _write_integrals(self):
         np.savez(os.path.join(self.outdir, 'integrals.npz'), **self.integrals._asdict())
@@ -742,8 +723,7 @@ class Problem:
         ghosted = np.zeros((len(planes),) + self._shape)
         ghosted[:, 1:-1, 1:-1] = planes
         _lib.check(self._lib.gpf_weighted_set(self._h, every, len(planes), _lib.as_dp(ghosted)))
-        self._weighted_every, self._weighted_names = every, names
-        self._weighted_steps, self._weighted_times, self._weighted_data = [], [], []
+        self._weighted_every, self._weighted_names, self._weighted_rec = every, names, _Series('weighted integrals', every)
 
     def clear_weighted_integrals(self):
         """Stop recording, drop the series and free the weight planes."""
@@ -757,10 +737,9 @@ class Problem:
         _pre_run), across `update()` and `run()` calls: one array (nrecords, K) per integrand; None when none are armed."""
         if self._weighted_every is None:
             return None
-        K, nq = len(self._weighted_names), len(_lib.WEIGHTED_INTEGRANDS)
-        data = np.concatenate(self._weighted_data) if self._weighted_data else np.empty((0, K, nq))
-        return WeightedIntegrals(np.array(self._weighted_steps, dtype=np.int64), np.array(self._weighted_times, dtype=np.float64),
-                                 tuple(self._weighted_names), *[data[:, :, k] for k in range(nq)])
+        rec, nq = self._weighted_rec, len(_lib.WEIGHTED_INTEGRANDS)
+        data = rec.stacked(0, (len(self._weighted_names), nq))
+        return WeightedIntegrals(rec.step_array(), rec.time_array(), tuple(self._weighted_names), *[data[:, :, k] for k in range(nq)])
 
     def film_weighted(self):
         """The same record for the current state, as {integrand: array(K)}: bit for bit what a step committing this state would
@@ -775,20 +754,12 @@ class Problem:
 
     def _collect_weighted(self, entries, before):
         """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
-        if self._weighted_every is None or not entries:
+        if self._weighted_every is None:
             return
-        n = _integral_records(before, len(entries), self._weighted_every)
-        out = np.empty((n, len(self._weighted_names), len(_lib.WEIGHTED_INTEGRANDS)))
-        steps = np.zeros(n, dtype=np.int64)
-        have = C.c_int64(0)
-        _lib.check(self._lib.gpf_weighted_read(self._h, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
-        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._weighted_every == 0]
-        if have.value != n or steps.tolist() != want:
-            raise _lib.GapflowHipError(f"weighted integrals: {have.value} records of steps {steps.tolist()} for the committed steps "
-                                       f"{before + 1}..{before + len(entries)} at stride {self._weighted_every}")
-        self._weighted_steps.extend(want)
-        self._weighted_times.extend(entries[s - before - 1].simtime for s in want)
-        self._weighted_data.append(out)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_weighted_read(self._h, _lib.as_dp(b[0]), n, steps, have))
+        self._weighted_rec.collect(read, entries, before, [((len(self._weighted_names), len(_lib.WEIGHTED_INTEGRANDS)), np.float64)])
 
     def _write_weighted(self):
         s = self.weighted_integrals._asdict()
@@ -834,14 +805,18 @@ class Problem:
             r.field, r.lo, r.hi = _lib.REGION_FIELDS.index(e['field']), e['above'], e['below']
             r.box[:] = e['box'] if e['box'] is not None else (1, self.grid['Nx'], 1, self.grid['Ny'])
         _lib.check(self._lib.gpf_regions_set(self._h, every, len(entries), arr))
-        self._regions_every, self._regions_names = every, [e['name'] for e in entries]
-        self._regions_steps, self._regions_times, self._regions_sums, self._regions_ints = [], [], [], []
+        self._regions_every, self._regions_names, self._regions_rec = every, [e['name'] for e in entries], _Series('regions', every)
 
     def clear_regions(self):
         """Stop recording, drop the series and free the device buffers."""
         if self._regions_every is not None:
             _lib.check(self._lib.gpf_regions_clear(self._h))
         self._regions_every = None
+
+    def _region_shapes(self):
+        """(trailing shape, dtype) of a record's sums and of its integers"""
+        K = len(self._regions_names)
+        return [((K, len(_lib.WEIGHTED_INTEGRANDS)), np.float64), ((K, len(_lib.REGION_INTS)), np.int64)]
 
     def _region_record(self, steps, times, sums, ints):
         nq = len(_lib.WEIGHTED_INTEGRANDS)
@@ -856,10 +831,8 @@ class Problem:
         bbox (nrecords, K, 4); None when none are armed."""
         if self._regions_every is None:
             return None
-        K = len(self._regions_names)
-        sums = np.concatenate(self._regions_sums) if self._regions_sums else np.empty((0, K, len(_lib.WEIGHTED_INTEGRANDS)))
-        ints = np.concatenate(self._regions_ints) if self._regions_ints else np.empty((0, K, len(_lib.REGION_INTS)), dtype=np.int64)
-        return self._region_record(np.array(self._regions_steps, dtype=np.int64), np.array(self._regions_times, dtype=np.float64), sums, ints)
+        rec, (sums, ints) = self._regions_rec, self._region_shapes()
+        return self._region_record(rec.step_array(), rec.time_array(), rec.stacked(0, *sums), rec.stacked(1, *ints))
 
     def film_regions(self):
         """The same record for the current state, as {name: array(K)} for the nine integrands, `cells` and `area`, and
@@ -877,24 +850,12 @@ class Problem:
 
     def _collect_regions(self, entries, before):
         """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
-        if self._regions_every is None or not entries:
+        if self._regions_every is None:
             return
-        n = _integral_records(before, len(entries), self._regions_every)
-        K = len(self._regions_names)
-        sums = np.empty((n, K, len(_lib.WEIGHTED_INTEGRANDS)))
-        ints = np.zeros((n, K, len(_lib.REGION_INTS)), dtype=np.int64)
-        steps = np.zeros(n, dtype=np.int64)
-        have = C.c_int64(0)
-        i64p = C.POINTER(C.c_int64)
-        _lib.check(self._lib.gpf_regions_read(self._h, _lib.as_dp(sums), ints.ctypes.data_as(i64p), n, steps.ctypes.data_as(i64p), C.byref(have)))
-        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._regions_every == 0]
-        if have.value != n or steps.tolist() != want:
-            raise _lib.GapflowHipError(f"regions: {have.value} records of steps {steps.tolist()} for the committed steps "
-                                       f"{before + 1}..{before + len(entries)} at stride {self._regions_every}")
-        self._regions_steps.extend(want)
-        self._regions_times.extend(entries[s - before - 1].simtime for s in want)
-        self._regions_sums.append(sums)
-        self._regions_ints.append(ints)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_regions_read(self._h, _lib.as_dp(b[0]), b[1].ctypes.data_as(C.POINTER(C.c_int64)), n, steps, have))
+        self._regions_rec.collect(read, entries, before, self._region_shapes())
 
     def _write_regions(self):
         s = self.regions._asdict()
@@ -921,6 +882,9 @@ class Problem:
 
     def _line_lengths(self, entries):
         return [self.grid['Nx'] if e['along'] == 'x' else self.grid['Ny'] for e in entries]
+
+    def _line_doubles(self, entries):
+        return len(_lib.LINE_FIELDS) * sum(self._line_lengths(entries))
 
     def _line_split(self, data, entries):
         """{name: {field: array(n, length)}} of records (n, doubles of a record) in the library's layout: per line, nine fields,
@@ -960,8 +924,7 @@ class Problem:
             raise ValueError(f"lines: capacity must be an integer >= 1 (None: the default), got {capacity!r}")
         entries = _line_entries(lines, self.grid['Nx'], self.grid['Ny'])
         _lib.check(self._lib.gpf_lines_set(self._h, every, len(entries), self._line_structs(entries), 0 if capacity is None else int(capacity)))
-        self._lines_every, self._lines_entries = every, entries
-        self._lines_steps, self._lines_times, self._lines_data = [], [], []
+        self._lines_every, self._lines_entries, self._lines_rec = every, entries, _Series('lines', every)
 
     def clear_lines(self):
         """Stop recording, drop the series and free the device buffers."""
@@ -976,11 +939,9 @@ class Problem:
         rho, jx, jy, p, h, tau_xz_bot, tau_yz_bot, tau_xz_top, tau_yz_top.  None when no lines are armed."""
         if self._lines_every is None:
             return None
-        nd = len(_lib.LINE_FIELDS) * sum(self._line_lengths(self._lines_entries))
-        data = np.concatenate(self._lines_data) if self._lines_data else np.empty((0, nd))
-        out = {'step': np.array(self._lines_steps, dtype=np.int64), 'time': np.array(self._lines_times, dtype=np.float64),
-               'names': tuple(e['name'] for e in self._lines_entries)}
-        out.update(self._line_split(data, self._lines_entries))
+        rec = self._lines_rec
+        out = {'step': rec.step_array(), 'time': rec.time_array(), 'names': tuple(e['name'] for e in self._lines_entries)}
+        out.update(self._line_split(rec.stacked(0, (self._line_doubles(self._lines_entries),)), self._lines_entries))
         return out
 
     def film_lines(self, lines=None):
@@ -992,7 +953,7 @@ class Problem:
             raise RuntimeError("film_lines: no lines are set (set_lines), and none are given")
         entries = self._lines_entries if lines is None else _line_entries(lines, self.grid['Nx'], self.grid['Ny'])
         self._sync_to_device()
-        out = np.empty((1, len(_lib.LINE_FIELDS) * sum(self._line_lengths(entries))))
+        out = np.empty((1, self._line_doubles(entries)))
         if lines is None:
             _lib.check(self._lib.gpf_lines_now(self._h, 0, None, _lib.as_dp(out), out.size))
         else:
@@ -1001,20 +962,12 @@ class Problem:
 
     def _collect_lines(self, entries, before):
         """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
-        if self._lines_every is None or not entries:
+        if self._lines_every is None:
             return
-        n = _integral_records(before, len(entries), self._lines_every)
-        out = np.empty((n, len(_lib.LINE_FIELDS) * sum(self._line_lengths(self._lines_entries))))
-        steps = np.zeros(n, dtype=np.int64)
-        have = C.c_int64(0)
-        _lib.check(self._lib.gpf_lines_read(self._h, _lib.as_dp(out), n, steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
-        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._lines_every == 0]
-        if have.value != n or steps.tolist() != want:
-            raise _lib.GapflowHipError(f"lines: {have.value} records of steps {steps.tolist()} for the committed steps "
-                                       f"{before + 1}..{before + len(entries)} at stride {self._lines_every}")
-        self._lines_steps.extend(want)
-        self._lines_times.extend(entries[s - before - 1].simtime for s in want)
-        self._lines_data.append(out)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_lines_read(self._h, _lib.as_dp(b[0]), n, steps, have))
+        self._lines_rec.collect(read, entries, before, [((self._line_doubles(self._lines_entries),), np.float64)])
 
     def _write_lines(self):
         """lines.npz: step, time, names, along and at (K, 2: the first and last column / row) of the lines, and `<name>.<field>`
@@ -1051,8 +1004,7 @@ class Problem:
         self._extrema_refusal()
         every = _extrema_stride(every, allow_zero=False)
         _lib.check(self._lib.gpf_extrema_set(self._h, every))
-        self._extrema_every = every
-        self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
+        self._extrema_every, self._extrema_rec = every, _Series('extrema', every)
 
     def clear_extrema(self):
         """Stop recording and drop the series."""
@@ -1066,11 +1018,10 @@ class Problem:
         across `update()` and `run()` calls; None when no extrema are armed.  cells[n, index[name]] is the (ix, iy) of `name`."""
         if self._extrema_every is None:
             return None
-        nq = len(_lib.EXTREMA_NAMES)
-        vals = np.concatenate(self._extrema_values) if self._extrema_values else np.empty((0, nq))
-        cells = np.concatenate(self._extrema_cells) if self._extrema_cells else np.empty((0, nq, 2), dtype=np.int32)
-        return FieldExtrema(np.array(self._extrema_steps, dtype=np.int64), np.array(self._extrema_times, dtype=np.float64),
-                            *[vals[:, k] for k in range(nq)], cells, {name: k for k, name in enumerate(_lib.EXTREMA_NAMES)})
+        rec, nq = self._extrema_rec, len(_lib.EXTREMA_NAMES)
+        vals = rec.stacked(0, (nq,))
+        return FieldExtrema(rec.step_array(), rec.time_array(), *[vals[:, k] for k in range(nq)], rec.stacked(1, (nq, 2), np.int32),
+                            {name: k for k, name in enumerate(_lib.EXTREMA_NAMES)})
 
     def field_extrema(self):
         """The same record for the current state, as a dict: the seven names of ``extrema`` and, for each, `<name>_cell` =
@@ -1088,24 +1039,13 @@ class Problem:
 
     def _collect_extrema(self, entries, before):
         """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
-        if self._extrema_every is None or not entries:
+        if self._extrema_every is None:
             return
-        n = _integral_records(before, len(entries), self._extrema_every)
         nq = len(_lib.EXTREMA_NAMES)
-        vals = np.empty((n, nq))
-        cells = np.zeros((n, nq, 2), dtype=np.int32)
-        steps = np.zeros(n, dtype=np.int64)
-        have = C.c_int64(0)
-        _lib.check(self._lib.gpf_extrema_read(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32)), n,
-                                              steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
-        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._extrema_every == 0]
-        if have.value != n or steps.tolist() != want:
-            raise _lib.GapflowHipError(f"extrema: {have.value} records of steps {steps.tolist()} for the committed steps "
-                                       f"{before + 1}..{before + len(entries)} at stride {self._extrema_every}")
-        self._extrema_steps.extend(want)
-        self._extrema_times.extend(entries[s - before - 1].simtime for s in want)
-        self._extrema_values.append(vals)
-        self._extrema_cells.append(cells)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_extrema_read(self._h, _lib.as_dp(b[0]), b[1].ctypes.data_as(C.POINTER(C.c_int32)), n, steps, have))
+        self._extrema_rec.collect(read, entries, before, [((nq,), np.float64), ((nq, 2), np.int32)])
 
     def _write_extrema(self):
         s = self.extrema._asdict()
@@ -1136,8 +1076,7 @@ class Problem:
         self._elastic_series_refusal()
         every = _elastic_series_stride(every, allow_zero=False)
         _lib.check(self._lib.gpf_elastic_series_set(self._h, every))
-        self._elastic_series_every = every
-        self._elastic_series_steps, self._elastic_series_times, self._elastic_series_values, self._elastic_series_cells = [], [], [], []
+        self._elastic_series_every, self._elastic_series_rec = every, _Series('elastic series', every)
 
     def clear_elastic_series(self):
         """Stop recording and drop the series."""
@@ -1152,11 +1091,9 @@ class Problem:
         cells[n, 0] is the (ix, iy) of d_max, cells[n, 1] that of d_min."""
         if self._elastic_series_every is None:
             return None
-        nq = len(_lib.ELASTIC_SERIES_NAMES)
-        vals = np.concatenate(self._elastic_series_values) if self._elastic_series_values else np.empty((0, nq))
-        cells = np.concatenate(self._elastic_series_cells) if self._elastic_series_cells else np.empty((0, 2, 2), dtype=np.int32)
-        return ElasticSeries(np.array(self._elastic_series_steps, dtype=np.int64), np.array(self._elastic_series_times, dtype=np.float64),
-                             *[vals[:, k] for k in range(nq)], cells)
+        rec, nq = self._elastic_series_rec, len(_lib.ELASTIC_SERIES_NAMES)
+        vals = rec.stacked(0, (nq,))
+        return ElasticSeries(rec.step_array(), rec.time_array(), *[vals[:, k] for k in range(nq)], rec.stacked(1, (2, 2), np.int32))
 
     def film_elastic(self):
         """The same record for the current state, gap and deformation, as a dict: the six names of ``elastic_series`` and
@@ -1174,24 +1111,12 @@ class Problem:
 
     def _collect_elastic_series(self, entries, before):
         """The records of the step that took the step count from `before` through `entries` (its committed step)."""
-        if self._elastic_series_every is None or not entries:
+        if self._elastic_series_every is None:
             return
-        n = _integral_records(before, len(entries), self._elastic_series_every)
-        nq = len(_lib.ELASTIC_SERIES_NAMES)
-        vals = np.empty((n, nq))
-        cells = np.zeros((n, 2, 2), dtype=np.int32)
-        steps = np.zeros(n, dtype=np.int64)
-        have = C.c_int64(0)
-        _lib.check(self._lib.gpf_elastic_series_read(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32)), n,
-                                                     steps.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(have)))
-        want = [s for s in range(before + 1, before + len(entries) + 1) if s % self._elastic_series_every == 0]
-        if have.value != n or steps.tolist() != want:
-            raise _lib.GapflowHipError(f"elastic series: {have.value} records of steps {steps.tolist()} for the committed steps "
-                                       f"{before + 1}..{before + len(entries)} at stride {self._elastic_series_every}")
-        self._elastic_series_steps.extend(want)
-        self._elastic_series_times.extend(entries[s - before - 1].simtime for s in want)
-        self._elastic_series_values.append(vals)
-        self._elastic_series_cells.append(cells)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_elastic_series_read(self._h, _lib.as_dp(b[0]), b[1].ctypes.data_as(C.POINTER(C.c_int32)), n, steps, have))
+        self._elastic_series_rec.collect(read, entries, before, [((len(_lib.ELASTIC_SERIES_NAMES),), np.float64), ((2, 2), np.int32)])
 
     def _write_elastic_series(self):
         np.savez(os.path.join(self.outdir, 'elastic_series.npz'), **self.elastic_series._asdict())
@@ -1280,20 +1205,9 @@ class Problem:
         self.dt = sc.dt
         self.tol = self.numerics['tol']
         self.max_it = self.numerics['max_it']
-        if self._probe_cells is not None:           # the step count starts over: so does the series
-            self._probe_steps, self._probe_times, self._probe_data = [], [], []
-        if self._integral_every is not None:
-            self._integral_steps, self._integral_times, self._integral_data = [], [], []
-        if self._weighted_every is not None:
-            self._weighted_steps, self._weighted_times, self._weighted_data = [], [], []
-        if self._regions_every is not None:
-            self._regions_steps, self._regions_times, self._regions_sums, self._regions_ints = [], [], [], []
-        if self._lines_every is not None:
-            self._lines_steps, self._lines_times, self._lines_data = [], [], []
-        if self._extrema_every is not None:
-            self._extrema_steps, self._extrema_times, self._extrema_values, self._extrema_cells = [], [], [], []
-        if self._elastic_series_every is not None:
-            self._elastic_series_steps, self._elastic_series_times, self._elastic_series_values, self._elastic_series_cells = [], [], [], []
+        for row in SERIES:                          # the step count starts over: so does every armed series
+            if row.recorder is not None and getattr(self, row.marker) is not None:
+                getattr(self, row.recorder).reset()
 
     def _absorb(self, entries):
         """Fold the per-step records of a batch into the host-side mirror of the run state."""
@@ -1320,12 +1234,9 @@ class Problem:
         log: its n per-step records, zero where none was written (shared with Ensemble, whose members' batches run in one launch)."""
         entries = [log[i] for i in range(ran)]
         self._absorb(entries)
-        self._collect_probes(entries)
-        self._collect_integrals(entries, before)
-        self._collect_weighted(entries, before)
-        self._collect_regions(entries, before)
-        self._collect_lines(entries, before)
-        self._collect_extrema(entries, before)
+        for row in SERIES:
+            if row.fused:
+                getattr(self, row.collect)(entries, before)
         if ran > 0:
             self._mark_device_advanced()
         failed = ran < n and log[ran].invalid != 0 if ran < n else False
@@ -1478,22 +1389,9 @@ class Problem:
         print(33 * '=')
         if not silent:
             history_to_csv(os.path.join(self.outdir, 'history.csv'), self.history)
-            if self._probe_cells is not None:
-                self._write_probes()
-            if self._integral_every is not None:
-                self._write_integrals()
-            if self._weighted_every is not None:
-                self._write_weighted()
-            if self._regions_every is not None:
-                self._write_regions()
-            if self._lines_every is not None:
-                self._write_lines()
-            if self._extrema_every is not None:
-                self._write_extrema()
-            if self._elastic_series_every is not None:
-                self._write_elastic_series()
-            if self._stats_every is not None:
-                self._write_statistics()
+            for row in SERIES:                      # (the statistics last)
+                if getattr(self, row.marker) is not None:
+                    getattr(self, row.write)()
             for name, m in self._gp_models.items():  # problem.py:490-503
                 history_to_csv(os.path.join(self.outdir, f'gp_{name}.csv'), m.history)
                 with open(os.path.join(self.outdir, f'gp_{name}.txt'), 'w') as f:
@@ -1567,47 +1465,17 @@ def _batch_length(step, write_freq, max_it, checkpoint_freq=0):
     return min(n, checkpoint_freq - step % checkpoint_freq) if checkpoint_freq > 0 else n
 
 
-def _keep_checkpoint_freq(input_dict, ymlstring):
-    """`options.checkpoint_freq` is this project's own key: the sanitiser keeps the reference's keys only (as the reference, which
-    ignores unknown ones), so it is read from the YAML text and set beside them."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    freq = (raw.get('options') or {}).get('checkpoint_freq', 0)
-    if input_dict.get('options') is not None:
-        input_dict['options']['checkpoint_freq'] = int(freq or 0)
+# This project's own `options` keys.  The sanitiser keeps the reference's keys only (as the reference, which ignores unknown ones),
+# so they are read from the YAML text and set beside the sanitised ones -- only when given (checkpoint_freq apart), so that every
+# other input's dictionaries stay as they are -- and checked here, on the host.  One function per key family, each taking the
+# sanitised dictionaries, the text's `options` mapping and the YAML file's directory.
+def _own_checkpoint_freq(input_dict, opts, base_dir):
+    """`options.checkpoint_freq`: always written, 0 when absent."""
+    input_dict['options']['checkpoint_freq'] = int(opts.get('checkpoint_freq', 0) or 0)
 
 
-def _probe_cells(cells, shape=None):
-    """Probe cells as an (n, 2) integer array; ValueError for anything that is not 1..256 pairs of integers or, when the ghosted
-    shape (Nx+2, Ny+2) is given, for a cell outside it.  Host only: no library call."""
-    if isinstance(cells, (str, bytes, dict)) or not hasattr(cells, '__len__'):
-        raise ValueError(f"probes: a list of [ix, iy] cells is required, got {cells!r}")
-    if len(cells) < 1:
-        raise ValueError("probes: at least one cell is required (clear_probes removes them)")
-    if len(cells) > _lib.PROBE_MAX:
-        raise ValueError(f"probes: {len(cells)} cells, at most {_lib.PROBE_MAX} per problem")
-    out = np.empty((len(cells), 2), dtype=np.int64)
-    for k, c in enumerate(cells):
-        ok = not isinstance(c, (str, bytes, dict)) and hasattr(c, '__len__') and len(c) == 2 and \
-            all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in c)
-        if not ok:
-            raise ValueError(f"probes: entry {k} must be a pair of integers [ix, iy], got {c!r}")
-        ix, iy = int(c[0]), int(c[1])
-        if shape is not None and not (0 <= ix < shape[0] and 0 <= iy < shape[1]):
-            raise ValueError(f"probes: cell ({ix}, {iy}) (entry {k}) lies outside the ghosted grid 0..{shape[0] - 1} x 0..{shape[1] - 1}")
-        out[k] = ix, iy
-    return out
-
-
-def _keep_probes(input_dict, ymlstring):
-    """`options.probes: [[ix, iy], ...]` and `options.probes_pressure` are this project's own keys: read from the YAML text and set
-    beside the sanitised ones, like checkpoint_freq -- but only when given, so that every other input's dictionaries stay as
-    they are.  The cells are checked here, on the host (against the grid, when the input has one)."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
+def _own_probes(input_dict, opts, base_dir):
+    """`options.probes: [[ix, iy], ...]` and `options.probes_pressure`; the cells are checked against the grid, when the input has one."""
     if opts.get('probes') is not None:
         grid = input_dict.get('grid') or {}
         shape = (int(grid['Nx']) + 2, int(grid['Ny']) + 2) if 'Nx' in grid and 'Ny' in grid else None
@@ -1616,47 +1484,9 @@ def _keep_probes(input_dict, ymlstring):
             input_dict['options']['probes_pressure'] = bool(opts['probes_pressure'])
 
 
-def _integral_records(base, ran, every):
-    """Records a stepping call leaves that took the step count from `base` over `ran` committed steps at stride `every`: the
-    multiples of `every` in (base, base + ran].  The slot of the step that takes the count to `expect` is
-    _integral_records(base, expect - base, every) - 1 (csrc/api_series.inc: series_count)."""
-    return (base + ran) // every - base // every if ran > 0 else 0
-
-
-def _integral_stride(every):
-    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < 1:
-        raise ValueError(f"integrals: the stride must be an integer >= 1, got {every!r}")
-    return int(every)
-
-
-def _integral_sections(sections, n, what):
-    """Interior rows / columns of the flow sections as a list of ints; None: the first and last of 1..n (one where n == 1).
-    ValueError for anything that is not 1..8 integers within 1..n.  Host only: no library call."""
-    if sections is None:
-        return [1, n] if n > 1 else [1]
-    if isinstance(sections, (str, bytes, dict)) or not hasattr(sections, '__len__'):
-        raise ValueError(f"integrals: {what} must be a list of interior indices, got {sections!r}")
-    if not 1 <= len(sections) <= _lib.INTEGRAL_MAX_SECTIONS:
-        raise ValueError(f"integrals: {what} holds {len(sections)} sections, 1 to {_lib.INTEGRAL_MAX_SECTIONS} required")
-    out = []
-    for k, v in enumerate(sections):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"integrals: {what}[{k}] must be an integer, got {v!r}")
-        if not 1 <= int(v) <= n:
-            raise ValueError(f"integrals: {what}[{k}] = {int(v)} lies outside the interior 1..{n}")
-        out.append(int(v))
-    return out
-
-
-def _keep_integrals(input_dict, ymlstring):
-    """`options.integrals: N` (the stride) and `options.integrals_sections_x / _y` are this project's own keys: read from the YAML
-    text and set beside the sanitised ones, like the probes' -- only when given, so that every other input's dictionaries stay
-    as they are.  Checked here, on the host (the sections against the grid, when the input has one)."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
+def _own_integrals(input_dict, opts, base_dir):
+    """`options.integrals: N` (the stride) and `options.integrals_sections_x / _y`; the sections are checked against the grid, when
+    the input has one."""
     if opts.get('integrals') is not None:
         grid = input_dict.get('grid') or {}
         input_dict['options']['integrals'] = _integral_stride(opts['integrals'])
@@ -1665,51 +1495,22 @@ def _keep_integrals(input_dict, ymlstring):
                 input_dict['options'][key] = _integral_sections(opts[key], int(grid[n]) if n in grid else 2**31 - 1, key)
 
 
-def _weighted_stride(every, allow_zero=False):
-    low = 0 if allow_zero else 1
-    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
-        raise ValueError(f"weighted integrals: the stride must be an integer >= {low}, got {every!r}")
-    return int(every)
+def _own_extrema(input_dict, opts, base_dir):
+    """`options.extrema: N` (the stride; 0 or absent: off)."""
+    if opts.get('extrema') is not None:
+        input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
 
 
-def _weight_planes(weights, names, nx, ny):
-    """(planes (K, nx, ny) float64, names) of what set_weighted_integrals is given; ValueError for a shape other than (K, nx, ny) /
-    (nx, ny), K outside 1..8, a weight that is not finite (plane and cell named, the cell in the ghosted index space as the library
-    names it) or names that do not match.  Host only: no library call."""
-    try:
-        a = np.array(weights, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"weighted integrals: weights must be an array of shape (K, {nx}, {ny}) or ({nx}, {ny})") from None
-    if a.ndim == 2:
-        a = a[None]
-    if a.ndim != 3 or a.shape[1:] != (nx, ny):
-        raise ValueError(f"weighted integrals: weights of shape {np.shape(weights)}; (K, {nx}, {ny}) or ({nx}, {ny}) required "
-                         "(interior cells; ghost cells never contribute)")
-    if not 1 <= len(a) <= _lib.WEIGHTED_MAX_PLANES:
-        raise ValueError(f"weighted integrals: {len(a)} weight planes, 1 to {_lib.WEIGHTED_MAX_PLANES} required")
-    bad = np.argwhere(~np.isfinite(a))
-    if len(bad):
-        k, i, j = (int(v) for v in bad[0])
-        raise ValueError(f"weighted integrals: weight plane {k} is not finite at cell ({i + 1}, {j + 1})")
-    if names is None:
-        names = [f'w{k}' for k in range(len(a))]
-    if isinstance(names, (str, bytes)) or not hasattr(names, '__len__') or len(names) != len(a) or \
-            not all(isinstance(n, str) and n for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"weighted integrals: names must be {len(a)} distinct non-empty strings, got {names!r}")
-    return np.ascontiguousarray(a), [str(n) for n in names]
+def _own_elastic_series(input_dict, opts, base_dir):
+    """`options.elastic_series: N` (the stride; 0 or absent: off)."""
+    if opts.get('elastic_series') is not None:
+        input_dict['options']['elastic_series'] = _elastic_series_stride(opts['elastic_series'])
 
 
-def _keep_weighted(input_dict, ymlstring, base_dir=None):
+def _own_weighted(input_dict, opts, base_dir):
     """`options.weighted_integrals: N` (the stride; 0 or absent: off) and `options.weights: [{box: ...}, {mode: ...}, {file: ...}]`
-    are this project's own keys: read from the YAML text and set beside the sanitised ones, like the integrals' -- only when
-    given, so that every other input's dictionaries stay as they are.  Checked here, on the host (gapflow_amd/weights.py:
-    parse_entries); a `file` becomes an absolute path, relative ones taken from the YAML file's directory."""
-    import yaml
+    (gapflow_amd/weights.py: parse_entries); a `file` becomes an absolute path, relative ones taken from the YAML file's directory."""
     from . import weights as _weights
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
     if opts.get('weighted_integrals') is not None:
         input_dict['options']['weighted_integrals'] = _weighted_stride(opts['weighted_integrals'], allow_zero=True)
     if opts.get('weights') is not None:
@@ -1718,65 +1519,19 @@ def _keep_weighted(input_dict, ymlstring, base_dir=None):
         raise ValueError("options.weighted_integrals: options.weights must list the weight planes")
 
 
-def _regions_stride(every, allow_zero=False):
-    low = 0 if allow_zero else 1
-    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
-        raise ValueError(f"regions: the stride must be an integer >= {low}, got {every!r}")
-    return int(every)
+def _own_statistics(input_dict, opts, base_dir):
+    """`options.statistics: N` (the stride; 0 or absent: off), `options.statistics_fields: [p, rho]` and `options.statistics_after: M`."""
+    if opts.get('statistics') is not None:
+        input_dict['options']['statistics'] = _statistics_stride(opts['statistics'], 'statistics', low=0)
+    if opts.get('statistics_fields') is not None:
+        input_dict['options']['statistics_fields'] = list(_statistics_fields(opts['statistics_fields']))
+    if opts.get('statistics_after') is not None:
+        input_dict['options']['statistics_after'] = _statistics_stride(opts['statistics_after'], 'statistics_after', low=0)
 
 
-def _region_entries(regions, nx=None, ny=None, where='regions'):
-    """What set_regions / options.region_list is given, checked and completed: a list of 1 to 8 dicts {field, above, below, box,
-    name} with above / below as floats (-inf / +inf when absent), box a list of four ints or None (the whole interior) and the
-    names distinct (r0, r1, ... when absent).  ValueError, naming the entry, for an unknown key or field, bounds that are no
-    numbers, a NaN among them or above >= below, a box that is not four integers ix0 <= ix1, iy0 <= iy1 inside the interior
-    (checked against nx, ny where given), a name that is no non-empty string or is used twice.  Host only: no library call."""
-    if isinstance(regions, (str, bytes, dict)) or not hasattr(regions, '__len__') or not 1 <= len(regions) <= _lib.REGION_MAX:
-        raise ValueError(f"{where}: a list of 1 to {_lib.REGION_MAX} regions {{field, above, below, box, name}} is required, got {regions!r}")
-    out = []
-    for k, e in enumerate(regions):
-        def bad(msg):
-            return ValueError(f"{where}: entry {k}: {msg}, got {e!r}")
-        if not isinstance(e, dict) or set(e) - {'field', 'above', 'below', 'box', 'name'}:
-            raise bad("a dict with the keys field, above, below, box, name is required")
-        if e.get('field') not in _lib.REGION_FIELDS:
-            raise bad(f"field must be one of {list(_lib.REGION_FIELDS)}")
-        bounds = []
-        for key, default in (('above', -np.inf), ('below', np.inf)):
-            v = e.get(key)
-            v = default if v is None else v
-            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or np.isnan(v):
-                raise bad(f"{key} must be a number (inf allowed, NaN not)")
-            bounds.append(float(v))
-        if not bounds[0] < bounds[1]:
-            raise bad("above < below is required (above is inclusive, below exclusive)")
-        box = e.get('box')
-        if box is not None:
-            if isinstance(box, (str, bytes, dict)) or not hasattr(box, '__len__') or len(box) != 4 or \
-                    any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in box):
-                raise bad("box must be four integers [ix0, ix1, iy0, iy1]")
-            box = [int(v) for v in box]
-            if not (1 <= box[0] <= box[1] and 1 <= box[2] <= box[3]) or (nx is not None and box[1] > nx) or (ny is not None and box[3] > ny):
-                raise bad("box must be ix0 <= ix1 and iy0 <= iy1 inside the interior (inclusive, 1-based)")
-        name = e.get('name')
-        name = f'r{k}' if name is None else name
-        if not isinstance(name, str) or not name:
-            raise bad("name must be a non-empty string")
-        if name in [o['name'] for o in out]:
-            raise bad(f"the name {name!r} is used twice")
-        out.append({'field': e['field'], 'above': bounds[0], 'below': bounds[1], 'box': box, 'name': name})
-    return out
-
-
-def _keep_regions(input_dict, ymlstring):
+def _own_regions(input_dict, opts, base_dir):
     """`options.regions: N` (the stride; 0 or absent: off) and `options.region_list: [{field: rho, below: 850.0, name: cavitated},
-    ...]` are this project's own keys: read from the YAML text and set beside the sanitised ones, like the weighted integrals'
-    -- only when given, so that every other input's dictionaries stay as they are.  Checked here, on the host (_region_entries)."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
+    ...]` (_region_entries)."""
     grid = input_dict.get('grid') or {}
     if opts.get('regions') is not None:
         input_dict['options']['regions'] = _regions_stride(opts['regions'], allow_zero=True)
@@ -1787,77 +1542,9 @@ def _keep_regions(input_dict, ymlstring):
         raise ValueError("options.regions: options.region_list must list the regions")
 
 
-def _lines_stride(every, allow_zero=False):
-    low = 0 if allow_zero else 1
-    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
-        raise ValueError(f"lines: the stride must be an integer >= {low}, got {every!r}")
-    return int(every)
-
-
-def _line_centre(along, nx, ny):
-    """The reference's centre line: column ny // 2 of the ghosted frame (ny = Ny + 2) along x, row nx // 2 along y."""
-    return (ny + 2) // 2 if along == 'x' else (nx + 2) // 2
-
-
-def _line_span(entry, nx, ny):
-    """(first, last) column (along x) or row (along y) of a checked entry, the centre line for at = None."""
-    at = entry['at']
-    if at is None:
-        at = _line_centre(entry['along'], nx, ny)
-    return (at, at) if isinstance(at, int) else (at[0], at[1])
-
-
-def _line_entries(lines, nx=None, ny=None, where='lines'):
-    """What set_lines / options.line_list is given, checked and completed: a list of 1 to 8 dicts {along, at, name} with along 'x'
-    or 'y', at None (the centre line), an int or a list of two ints, and the names distinct (l0, l1, ... when absent).
-    ValueError, naming the entry, for an unknown key or axis, an `at` that is no integer or pair of integers first <= last
-    inside the interior (checked against nx, ny where given), a name that is no non-empty string, is used twice or is one of the
-    series' own keys.  Host only: no library call."""
-    if isinstance(lines, (str, bytes, dict)) or not hasattr(lines, '__len__') or not 1 <= len(lines) <= _lib.LINE_MAX:
-        raise ValueError(f"{where}: a list of 1 to {_lib.LINE_MAX} lines {{along, at, name}} is required, got {lines!r}")
-    out = []
-    for k, e in enumerate(lines):
-        def bad(msg):
-            return ValueError(f"{where}: entry {k}: {msg}, got {e!r}")
-
-        def is_int(v):
-            return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-        if not isinstance(e, dict) or set(e) - {'along', 'at', 'name'}:
-            raise bad("a dict with the keys along, at, name is required")
-        if e.get('along') not in _lib.LINE_AXES:
-            raise bad(f"along must be one of {list(_lib.LINE_AXES)}")
-        n = None if nx is None or ny is None else (ny if e['along'] == 'x' else nx)       # the axis `at` counts along
-        at = e.get('at')
-        if at is not None:
-            if is_int(at):
-                at = int(at)
-                lo = hi = at
-            elif not isinstance(at, (str, bytes, dict)) and hasattr(at, '__len__') and len(at) == 2 and all(is_int(v) for v in at):
-                at = [int(v) for v in at]
-                lo, hi = at
-            else:
-                raise bad("at must be an integer or a pair of integers (first, last)")
-            if not 1 <= lo <= hi or (n is not None and hi > n):
-                raise bad("at must be first <= last inside the interior (inclusive, 1-based)")
-        name = e.get('name')
-        name = f'l{k}' if name is None else name
-        if not isinstance(name, str) or not name or name in ('step', 'time', 'names'):
-            raise bad("name must be a non-empty string other than step, time, names")
-        if name in [o['name'] for o in out]:
-            raise bad(f"the name {name!r} is used twice")
-        out.append({'along': e['along'], 'at': at, 'name': name})
-    return out
-
-
-def _keep_lines(input_dict, ymlstring):
+def _own_lines(input_dict, opts, base_dir):
     """`options.lines: N` (the stride; 0 or absent: off) and `options.line_list: [{along: x}, {along: y, at: [1, 32], name: band}]`
-    are this project's own keys: read from the YAML text and set beside the sanitised ones, like the regions' -- only when given,
-    so that every other input's dictionaries stay as they are.  Checked here, on the host (_line_entries)."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
+    (_line_entries)."""
     grid = input_dict.get('grid') or {}
     if opts.get('lines') is not None:
         input_dict['options']['lines'] = _lines_stride(opts['lines'], allow_zero=True)
@@ -1868,93 +1555,48 @@ def _keep_lines(input_dict, ymlstring):
         raise ValueError("options.lines: options.line_list must list the lines")
 
 
-def _extrema_stride(every, allow_zero=True):
-    low = 0 if allow_zero else 1
-    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
-        raise ValueError(f"extrema: the stride must be an integer >= {low}, got {every!r}")
-    return int(every)
-
-
-def _keep_extrema(input_dict, ymlstring):
-    """`options.extrema: N` (the stride; 0 or absent: off) is this project's own key: read from the YAML text and set beside the
-    sanitised ones, like the integrals' -- only when given, so that every other input's dictionaries stay as they are.  Checked
-    here, on the host."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
-    if opts.get('extrema') is not None:
-        input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
-
-
-def _elastic_series_stride(every, allow_zero=True):
-    low = 0 if allow_zero else 1
-    if isinstance(every, (bool, np.bool_)) or not isinstance(every, (int, np.integer)) or every < low:
-        raise ValueError(f"elastic series: the stride must be an integer >= {low}, got {every!r}")
-    return int(every)
-
-
-def _keep_elastic_series(input_dict, ymlstring):
-    """`options.elastic_series: N` (the stride; 0 or absent: off) is this project's own key: read from the YAML text and set beside
-    the sanitised ones, like the extrema's -- only when given, so that every other input's dictionaries stay as they are.
-    Checked here, on the host."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
-    if opts.get('elastic_series') is not None:
-        input_dict['options']['elastic_series'] = _elastic_series_stride(opts['elastic_series'])
-
-
-def _statistics_stride(v, key, low):
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < low:
-        raise ValueError(f"statistics: {key} must be an integer >= {low}, got {v!r}")
-    return int(v)
-
-
-def _statistics_fields(fields):
-    """The requested fields as a tuple in the library's order; ValueError for anything but a non-empty list of distinct names
-    out of p, rho, jx, jy.  Host only: no library call."""
-    if isinstance(fields, (str, bytes, dict)) or not hasattr(fields, '__len__') or len(fields) < 1 or \
-            not all(isinstance(f, str) and f in _lib.STATS_FIELDS for f in fields) or len(set(fields)) != len(fields):
-        raise ValueError(f"statistics: statistics_fields must be a non-empty list of distinct names out of {list(_lib.STATS_FIELDS)}, got {fields!r}")
-    return tuple(f for f in _lib.STATS_FIELDS if f in fields)
-
-
-def _keep_statistics(input_dict, ymlstring):
-    """`options.statistics: N` (the stride; 0 or absent: off), `options.statistics_fields: [p, rho]` and `options.statistics_after: M`
-    are this project's own keys: read from the YAML text and set beside the sanitised ones, like the integrals' -- only when
-    given, so that every other input's dictionaries stay as they are.  Checked here, on the host."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
-    if opts.get('statistics') is not None:
-        input_dict['options']['statistics'] = _statistics_stride(opts['statistics'], 'statistics', low=0)
-    if opts.get('statistics_fields') is not None:
-        input_dict['options']['statistics_fields'] = list(_statistics_fields(opts['statistics_fields']))
-    if opts.get('statistics_after') is not None:
-        input_dict['options']['statistics_after'] = _statistics_stride(opts['statistics_after'], 'statistics_after', low=0)
-
-
-def _keep_init_from(input_dict, ymlstring, base_dir=None):
-    """`options.init_from: path` (a checkpoint to start from, Problem.init_from) is this project's own key: read from the YAML
-    text and set beside the sanitised ones, like checkpoint_freq -- only when given, so that every other input's dictionaries
-    stay as they are.  A relative path is relative to the YAML file (`base_dir`; a string has none: the working directory)."""
-    import yaml
-    raw = yaml.full_load(ymlstring) or {}
-    opts = raw.get('options') or {}
-    if input_dict.get('options') is None or not isinstance(opts, dict):
-        return
+def _own_init_from(input_dict, opts, base_dir):
+    """`options.init_from: path` (a checkpoint to start from, Problem.init_from).  A relative path is relative to the YAML file
+    (`base_dir`; a string has none: the working directory)."""
     path = opts.get('init_from')
     if path is None:
         return
     if not isinstance(path, str) or not path:
         raise ValueError(f"options.init_from: the path of a checkpoint file is required, got {path!r}")
     input_dict['options']['init_from'] = os.path.normpath(os.path.join(base_dir or os.getcwd(), path))
+
+
+_OWN_KEYS = (_own_checkpoint_freq, _own_probes, _own_integrals, _own_extrema, _own_elastic_series, _own_weighted, _own_statistics,
+             _own_regions, _own_lines, _own_init_from)
+
+
+def _keep(keys, input_dict, ymlstring, base_dir=None):
+    """Parse the YAML text once and apply `keys` to its `options`; nothing where the input has no options section to set them
+    beside, or the text's is no mapping."""
+    import yaml
+    opts = (yaml.full_load(ymlstring) or {}).get('options') or {}
+    if input_dict.get('options') is None or not isinstance(opts, dict):
+        return
+    for key in keys:
+        key(input_dict, opts, base_dir)
+
+
+def _keep_own_options(input_dict, ymlstring, base_dir=None):
+    """All of this project's own keys, in one pass over the text (Problem.from_string, SlabProblem.from_string)."""
+    _keep(_OWN_KEYS, input_dict, ymlstring, base_dir)
+
+
+# one key family at a time
+def _keep_checkpoint_freq(input_dict, ymlstring): _keep([_own_checkpoint_freq], input_dict, ymlstring)
+def _keep_probes(input_dict, ymlstring): _keep([_own_probes], input_dict, ymlstring)
+def _keep_integrals(input_dict, ymlstring): _keep([_own_integrals], input_dict, ymlstring)
+def _keep_extrema(input_dict, ymlstring): _keep([_own_extrema], input_dict, ymlstring)
+def _keep_elastic_series(input_dict, ymlstring): _keep([_own_elastic_series], input_dict, ymlstring)
+def _keep_weighted(input_dict, ymlstring, base_dir=None): _keep([_own_weighted], input_dict, ymlstring, base_dir)
+def _keep_statistics(input_dict, ymlstring): _keep([_own_statistics], input_dict, ymlstring)
+def _keep_regions(input_dict, ymlstring): _keep([_own_regions], input_dict, ymlstring)
+def _keep_lines(input_dict, ymlstring): _keep([_own_lines], input_dict, ymlstring)
+def _keep_init_from(input_dict, ymlstring, base_dir=None): _keep([_own_init_from], input_dict, ymlstring, base_dir)
 
 
 def _in_main_thread():

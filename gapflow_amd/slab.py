@@ -481,24 +481,14 @@ class SlabProblem:
         raise NotImplementedError("init_from: not available on a SlabProblem")
 
     def __init__(self, input_dict, device=0, dist=None):
-        if (input_dict.get('options') or {}).get('init_from'):
-            raise NotImplementedError("init_from: not available on a SlabProblem")   # options.init_from: as init_from
-        if (input_dict.get('options') or {}).get('probes') is not None:
-            raise NotImplementedError("probes: not available on a SlabProblem")      # options.probes: as set_probes
-        if (input_dict.get('options') or {}).get('integrals') is not None:
-            raise NotImplementedError("integrals: not available on a SlabProblem")   # options.integrals: as set_integrals
-        if (input_dict.get('options') or {}).get('weighted_integrals'):              # (0: off, as on a Problem)
-            raise NotImplementedError("weighted integrals: not available on a SlabProblem")   # options.weighted_integrals: as set_weighted_integrals
-        if (input_dict.get('options') or {}).get('regions'):                         # (0: off, as on a Problem)
-            raise NotImplementedError("regions: not available on a SlabProblem")     # options.regions: as set_regions
-        if (input_dict.get('options') or {}).get('lines'):                           # (0: off, as on a Problem)
-            raise NotImplementedError("lines: not available on a SlabProblem")       # options.lines: as set_lines
-        if (input_dict.get('options') or {}).get('extrema'):                         # (0: off, as on a Problem)
-            raise NotImplementedError("extrema: not available on a SlabProblem")     # options.extrema: as set_extrema
-        if (input_dict.get('options') or {}).get('elastic_series'):                  # (0: off, as on a Problem)
-            raise NotImplementedError("elastic series: not available on a SlabProblem")      # options.elastic_series: as set_elastic_series
-        if (input_dict.get('options') or {}).get('statistics'):                      # (0: off, as on a Problem)
-            raise NotImplementedError("statistics: not available on a SlabProblem")  # options.statistics: as set_statistics
+        opts = input_dict.get('options') or {}
+        # the options that arm what the methods above refuse are refused as those are
+        for key, label in (('init_from', 'init_from'), ('probes', 'probes'), ('integrals', 'integrals'),
+                           ('weighted_integrals', 'weighted integrals'), ('regions', 'regions'), ('lines', 'lines'), ('extrema', 'extrema'),
+                           ('elastic_series', 'elastic series'), ('statistics', 'statistics')):
+            given = opts.get(key)
+            if given is not None if key in ('probes', 'integrals') else given:      # (the others: 0 is off, as on a Problem)
+                raise NotImplementedError(f"{label}: not available on a SlabProblem")
         import torch
         if dist is None:
             import torch.distributed as dist
@@ -625,20 +615,10 @@ class SlabProblem:
 
     @classmethod
     def from_string(cls, text, device=0, dist=None, base_dir=None):
-        from .problem import _keep_checkpoint_freq, _keep_probes, _keep_integrals, _keep_extrema, _keep_init_from, _keep_weighted, _keep_statistics, _keep_regions, _keep_lines
-        from .problem import _keep_elastic_series
+        from .problem import _keep_own_options
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
-        _keep_elastic_series(d, text)               # options.elastic_series: refused below
-        _keep_checkpoint_freq(d, text)              # options.checkpoint_freq, as Problem.from_string
-        _keep_probes(d, text)                       # options.probes: refused below
-        _keep_integrals(d, text)                    # options.integrals: refused below
-        _keep_extrema(d, text)                      # options.extrema: refused below
-        _keep_weighted(d, text, base_dir)           # options.weighted_integrals: refused below
-        _keep_statistics(d, text)                   # options.statistics: refused below
-        _keep_regions(d, text)                      # options.regions: refused below
-        _keep_lines(d, text)                        # options.lines: refused below
-        _keep_init_from(d, text, base_dir)          # options.init_from: refused below
+        _keep_own_options(d, text, base_dir)        # options.checkpoint_freq, as Problem.from_string; the series' keys: refused in __init__
         return cls(d, device=device, dist=dist)
 
     @classmethod
