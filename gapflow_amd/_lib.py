@@ -49,6 +49,9 @@ ENSEMBLE_FORCE_WORKSPACE = 1        # gpf_ensemble_create2: flags
 ENSEMBLE_TIERS = ('lds', 'workspace')       # gpf_ensemble_member_info: tier
 EXTREMA_NAMES = ('p_max', 'p_min', 'rho_max', 'rho_min', 'h_min', 'u_max', 'v_max')     # gpf_extrema_*: the record's order
 ELASTIC_SERIES_NAMES = ('d_sum', 'd2_sum', 'p_d', 'h_sum', 'd_max', 'd_min')     # gpf_elastic_series_*: the record's order; cells: d_max's, d_min's
+# gpf_changes_*: the record's order; cells: dmax_rho's, dmax_jx's, dmax_jy's
+CHANGE_NAMES = ('d2_rho', 'd2_jx', 'd2_jy', 'q2_rho', 'q2_jx', 'q2_jy', 'dmass', 'dmax_rho', 'dmax_jx', 'dmax_jy', 'dt')
+CHANGE_MAXIMA = ('dmax_rho', 'dmax_jx', 'dmax_jy')
 INTEGRAL_SUMS = ('load', 'load_x', 'load_y', 'p_hx', 'p_hy', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')
 WEIGHTED_MAX_PLANES = 8             # gpf_weighted_set: weight planes per handle
 WEIGHTED_INTEGRANDS = ('p', 'h', 'rho_h', 'jx_h', 'jy_h', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')    # gpf_weighted_*: the record's order
@@ -192,6 +195,11 @@ SIGNATURES = {
     'gpf_elastic_series_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_elastic_series_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32)]),
     'gpf_elastic_series_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_changes_set': (C.c_int, [C.c_void_p, C.c_int64]),
+    'gpf_changes_clear': (C.c_int, [C.c_void_p]),
+    'gpf_changes_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_changes_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32)]),
+    'gpf_changes_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_stats_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
     'gpf_stats_clear': (C.c_int, [C.c_void_p]),
     'gpf_stats_info': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP, _DP]),

@@ -32,6 +32,7 @@
 #include "line_kernels.hip"
 #include "resample_kernels.hip"
 #include "elastic_series_kernels.hip"
+#include "change_kernels.hip"
 
 using namespace gpf;
 
@@ -67,6 +68,9 @@ static_assert(sizeof(LogEntry) == sizeof(gpf_scalars_t), "LogEntry must mirror g
 static constexpr size_t PLANE_PAD_BYTES = 256;
 static constexpr long long LOG_CAPACITY = 4096;                 // per-step records a handle's device log holds: the longest batch
 static constexpr long long SMALL_GRID_LDS_BYTES = 150 * 1024;   // what k_small_steps may take of a CU's 160 KB of LDS (gpf_ensemble_limits)
+
+// Why the other q buffer does not hold the state before the last committed step (gpf_handle::prev_lost)
+enum { PREV_LOST_NO_STEP = 0, PREV_LOST_CLOSURES, PREV_LOST_STAGEWISE, PREV_LOST_PLAN };
 
 struct gpf_handle {
     gpf_config cfg;
@@ -149,6 +153,11 @@ struct gpf_handle {
     struct { long long every = 0; double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
              bool narrow = false; bool pending = false; long long pending_base = 0;
              std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } eldef;
+    // step-change series (api_changes.inc): recording stride (0: not armed); the device records ([log_cap + 1][11] doubles,
+    // [log_cap + 1][6] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was set then); the records of
+    // the last stepping call on the host
+    struct { long long every = 0; double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
+             bool narrow = false; std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } chg;
     // running field statistics (api_stats.inc): recording stride (0: not armed), the step count records are taken above, the
     // requested fields (bit 0 p, 1 rho, 2 jx, 3 jy) and the step count at which the window began; the accumulator planes
     // ([requested fields][mean m2 min max] planes of this handle's Layout) and the device's record of the window, both allocated by
@@ -205,6 +214,7 @@ struct gpf_handle {
     int open_parity = 0;
     bool has_q = false, has_topo = false, pre_run_done = false;
     bool prev_state_valid = false;          // the OTHER q buffer holds the state before the last committed fused step (gpf_update_closures)
+    int prev_lost = PREV_LOST_NO_STEP;      // while it does not: what took it (gpf_changes_now names the cause)
     long long fields_step = -1;             // the derived fields hold the closures the reference's field objects hold at this step count
                                             // (the corrector stage's: gpf_close_step, gpf_update_closures); -1: something else
     bool fields_restored = false;           // ... and came from a checkpoint: gpf_update_closures keeps them (nothing could recompute them)
@@ -222,6 +232,11 @@ struct gpf_handle {
     char plan2_note[400] = "";              // how the plan was arrived at (gpf_plan_note)
     int step_variant[5] = {-1, -1, -1, 0, -1};  // what the last launch of a step passed to step2_kernel() (gpf_step_variant)
 };
+
+// The other q buffer no longer holds the state before the last committed step, and why (PREV_LOST_*)
+static void prev_state_lost(gpf_handle* h, int why = PREV_LOST_NO_STEP) { h->prev_state_valid = false; h->prev_lost = why; }
+// ... or does, if the batch committed a step and ended valid
+static void prev_state_after(gpf_handle* h, bool committed) { h->prev_state_valid = committed; h->prev_lost = PREV_LOST_NO_STEP; }
 
 static int enter(gpf_handle* h, bool reads_only) {
     HIP_TRY(hipSetDevice(h->cfg.device));
@@ -395,7 +410,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->integ.dev, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->eldef.rec, h->eldef.cell, h->eldef.part, h->eldef.row_val, h->eldef.row_iy, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->integ.dev, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->eldef.rec, h->eldef.cell, h->eldef.part, h->eldef.row_val, h->eldef.row_iy, h->chg.rec, h->chg.cell, h->chg.part, h->chg.row_val, h->chg.row_iy, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -552,7 +567,7 @@ extern "C" int gpf_upload(gpf_handle* h, int field, const double* host, size_t c
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (field == GPF_FIELD_Q) h->has_q = true;
     h->g1_ready = false;
-    h->prev_state_valid = false;
+    prev_state_lost(h);
     h->fields_step = -1;                    // the derived fields belong to what was there before
     if (field == GPF_FIELD_TOPO) h->has_topo = true;
     return GPF_OK;
@@ -676,7 +691,7 @@ extern "C" int gpf_update_closures(gpf_handle* h) {
         hipLaunchKernelGGL(k_bc_y, dim3((L.Nx + 2 + 255) / 256), dim3(256), 0, h->stream, w, L, h->E);
         HIP_TRY(hipGetLastError());
         GPF_TRY(launch_fields(h, w));
-        h->prev_state_valid = false;        // the buffer now holds the predictor's field; the closures stay in the derived fields
+        prev_state_lost(h, PREV_LOST_CLOSURES);     // the buffer now holds the predictor's field; the closures stay in the derived fields
         h->fields_step = s.step;
     } else {
         GPF_TRY(launch_fields(h, h->q[par]));
@@ -789,7 +804,7 @@ extern "C" int gpf_pre_run(gpf_handle* h) {
     GPF_TRY(write_state(h, s));
     h->pre_run_done = true;
     h->g1_ready = false;
-    h->prev_state_valid = false;
+    prev_state_lost(h);
     h->fields_step = -1;
     h->host_step = 0; h->next_step = 0;
     return stats_restart(h, 0);         // the step count starts over: so does the statistics' window
@@ -1089,6 +1104,7 @@ static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long 
 #include "api_weighted.inc"
 #include "api_extrema.inc"
 #include "api_elastic_series.inc"
+#include "api_changes.inc"
 #include "api_regions.inc"
 #include "api_lines.inc"
 #include "api_stats.inc"
@@ -1111,6 +1127,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     GPF_TRY(lines_begin(h));
     GPF_TRY(extrema_begin(h));
     GPF_TRY(stats_begin(h));
+    GPF_TRY(changes_begin(h));
     while (done < n) {
         const long long base = h->host_step;
         const int64_t batch = lines_batch(h, std::min<int64_t>(n - done, h->log_cap), base);        // (lines: no more records than their buffer holds)
@@ -1124,6 +1141,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
             GPF_TRY(lines_launch(h, base + i + 1, base));       // nor without lines, nor off theirs
             GPF_TRY(extrema_launch(h, base + i + 1, base));     // nor without extrema, nor off theirs
             GPF_TRY(stats_launch(h, base + i + 1));             // nor without statistics, nor off theirs
+            GPF_TRY(changes_launch(h, base + i + 1, base));     // nor without changes, nor off theirs; before the next step overwrites q^(n-1)
         }
         StepState s;
         GPF_TRY(read_state(h, s));
@@ -1135,6 +1153,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
         GPF_TRY(lines_collect(h, base, ran));
         GPF_TRY(extrema_collect(h, base, ran));
         GPF_TRY(stats_collect(h, s.step));
+        GPF_TRY(changes_collect(h, base, ran));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);
         if (log && entries > 0) {
             const long long take = std::min<long long>(entries, log_capacity - logged);
@@ -1144,7 +1163,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
             }
         }
         h->host_step = s.step; h->next_step = s.step;
-        h->prev_state_valid = ran >= 1 && !s.invalid;      // the other buffer: the state before the last step of this batch
+        prev_state_after(h, ran >= 1 && !s.invalid);       // the other buffer: the state before the last step of this batch
         done += batch;
         if (ran < batch) break;     // stopped on the device (converged / max_it / invalid)
     }

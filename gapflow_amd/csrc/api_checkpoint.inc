@@ -277,7 +277,7 @@ extern "C" int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes
     // pass 0: the blob as it arrived on the device, digested in the staging buffer -- the handle is not touched;
     // pass 1: into the handle's planes, digested from what stands there afterwards
     // Once pass 1 has begun, any failure leaves the planes half-written: the handle then asks for a fresh upload.
-    auto spoiled = [&](int rc) { h->has_q = false; h->pre_run_done = false; h->prev_state_valid = false; h->fields_step = -1; return rc; };
+    auto spoiled = [&](int rc) { h->has_q = false; h->pre_run_done = false; prev_state_lost(h); h->fields_step = -1; return rc; };
     for (int pass = 0; pass < 2; ++pass) {
         auto run_pass = [&]() -> int {
             HIP_TRY(hipMemsetAsync(S.digest, 0, CKPT_MAX_PLANES * sizeof(unsigned long long), h->stream));
@@ -326,7 +326,7 @@ extern "C" int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->has_q = true; h->has_topo = true;
     h->host_step = s.step; h->next_step = s.step;
-    h->prev_state_valid = (B.flags & CKPT_PREV) != 0;
+    prev_state_after(h, (B.flags & CKPT_PREV) != 0);
     h->g1_ready = false;
     h->gp_state_mean_valid = false;
     h->fields_step = (B.flags & CKPT_DERIVED) ? s.step : -1;

@@ -162,6 +162,6 @@ extern "C" int gpf_elastic_series_time(gpf_handle* h, int64_t n, int mode, doubl
                                    });
                                },
                                [&](long long, long long) { h->eldef.host.swap(host); h->eldef.cells.swap(cells); h->eldef.steps.swap(steps); return (int)GPF_OK; }, ms);
-    h->prev_state_valid = false;        // (series_resync speaks of fused steps: a closed step leaves its working field in the other buffer)
+    prev_state_lost(h, PREV_LOST_STAGEWISE);    // (series_resync speaks of fused steps: a closed step leaves its working field in the other buffer)
     return rc;
 }

@@ -65,6 +65,7 @@ static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first, int
     if (h->lines.every) return "lines are armed on it (they cut the batch per member; gpf_lines_clear, or step it alone)";
     if (h->probes.n) return "probes are armed on it (their records need per-member slots; gpf_probes_clear, or step it alone)";
     if (h->extr.every) return "extrema are armed on it (their records need per-member slots; gpf_extrema_clear, or step it alone)";
+    if (h->chg.every) return "changes are armed on it (they cut the batch per member; gpf_changes_clear, or step it alone)";
     return "";
 }
 
@@ -238,7 +239,7 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
             }
         }
         h->host_step = st.step; h->next_step = st.step;
-        h->prev_state_valid = ran >= 1 && !st.invalid;
+        prev_state_after(h, ran >= 1 && !st.invalid);
         h->g1_ready = false;
     }
     if (n_executed)

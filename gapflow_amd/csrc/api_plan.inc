@@ -41,7 +41,7 @@ static void fill_step2_args(gpf_handle* h, Step2Args& a2, int D, int honor_stop,
 static int plan_trial(gpf_handle* h, int D, float* us, int reps = 6, bool both = false) {
     static const int parity_value[2] = {0, 1};
     if (!h->st_trial) HIP_TRY(hipMalloc(&h->st_trial, sizeof(StepState)));
-    h->prev_state_valid = false;            // the launches below overwrite the other buffer
+    prev_state_lost(h, PREV_LOST_PLAN);     // the launches below overwrite the other buffer
     both = both && h->plan_master != nullptr;
     int par = 0;
     if (both) GPF_TRY(current_parity(h, &par));

@@ -85,7 +85,7 @@ extern "C" int gpf_resample(gpf_handle* dst, const gpf_handle* src) {
     // what gpf_upload of the same field leaves
     dst->has_q = true;
     dst->g1_ready = false;
-    dst->prev_state_valid = false;
+    prev_state_lost(dst);
     dst->fields_step = -1;
     return stats_restart(dst, dst->host_step);      // another state: armed statistics begin a new window
 }
@@ -103,7 +103,7 @@ extern "C" int gpf_resample_time(gpf_handle* dst, const gpf_handle* src, int mod
     GPF_TRY(enter(dst));
     int par = 0;
     GPF_TRY(current_parity(dst, &par));
-    dst->prev_state_valid = false;
+    prev_state_lost(dst);
     const ResampleArgs a = resample_args(dst, src, par ^ 1, ss.parity);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipEventCreate(&e0);

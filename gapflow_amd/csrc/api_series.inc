@@ -1,5 +1,5 @@
 // Part of api.hip (included there, not compiled on its own): what the per-step recorders of a handle -- probes, film integrals,
-// weighted integrals, regions, lines, extrema, statistics, an elastic handle's deformation series (api_<name>.inc, included
+// weighted integrals, regions, lines, extrema, statistics, an elastic handle's deformation series, step changes (api_<name>.inc, included
 // behind this file) -- have in common: the
 // arithmetic of a stride's records, their way to the host and out of it, the alignment test of the 16-byte loads, the arguments
 // and the two launches of the row-reduced series (device side: series_rows.hpp), the cases the film reductions refuse, how
@@ -116,17 +116,17 @@ static int series_refusal(const gpf_handle* h, const std::string& who, const cha
 }
 
 // ---- series put aside for a call ---------------------------------------------------------------------------------------------
-// What arms each of the eight series -- the probes' count and the seven strides -- remembered, and all of them disarmed except
+// What arms each of the nine series -- the probes' count and the eight strides -- remembered, and all of them disarmed except
 // `keep` (the address of one of these fields, or null: none).  restore() puts the values back; the destructor does if nobody
 // asked.  Every recorder returns at once while its series is disarmed, so this is all it takes to step without it.
 struct SeriesAside {
     gpf_handle* const h;
     const void* const keep;
     const int probes;
-    long long every[7];
+    long long every[8];
     bool restored = false;
-    std::array<long long*, 7> strides() const {
-        return {&h->integ.every, &h->weighted.every, &h->regions.every, &h->lines.every, &h->extr.every, &h->stats.every, &h->eldef.every};
+    std::array<long long*, 8> strides() const {
+        return {&h->integ.every, &h->weighted.every, &h->regions.every, &h->lines.every, &h->extr.every, &h->stats.every, &h->eldef.every, &h->chg.every};
     }
     SeriesAside(gpf_handle* handle, const void* keep_armed) : h(handle), keep(keep_armed), probes(handle->probes.n) {
         if (keep != &h->probes.n) h->probes.n = 0;
@@ -159,13 +159,14 @@ static void series_forget_records(gpf_handle* h) {
     h->lines.host.clear(); h->lines.steps.clear();
     h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
     h->eldef.host.clear(); h->eldef.cells.clear(); h->eldef.steps.clear();
+    h->chg.host.clear(); h->chg.cells.clear(); h->chg.steps.clear();
 }
 
 // ---- the gpf_*_time diagnostics ----------------------------------------------------------------------------------------------
 // A call stepped from step count `base` outside gpf_step's loop: the host's counters follow the device's
 static int series_resync(gpf_handle* h, long long base, StepState& s) {
     GPF_TRY(read_state(h, s));
-    h->prev_state_valid = s.step > base && !s.invalid;
+    prev_state_after(h, s.step > base && !s.invalid);
     h->host_step = s.step; h->next_step = s.step;
     return GPF_OK;
 }
@@ -253,17 +254,18 @@ static int weighted_launch(gpf_handle* h, long long expect, long long base);
 static int regions_launch(gpf_handle* h, long long expect, long long base);
 static int lines_launch(gpf_handle* h, long long expect, long long base);
 static int stats_launch(gpf_handle* h, long long expect);
+static int changes_launch(gpf_handle* h, long long expect, long long base);
 static long long stats_floor(const gpf_handle* h);
 
 // A batch of the small-grid kernel, cut at the union of the steps that the series which cut it record (weighted integrals,
-// regions, lines, statistics), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
+// regions, lines, statistics, changes), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
 // batch in pieces is bitwise the batch in one: every piece starts from the state and the run state the piece before left.
 // With none of them armed this is the one launch.  Probes, extrema and film integrals do not cut: k_small_steps records them.
 static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base) {
     const long long end = base + batch;
     for (long long at = base; at < end;) {
         long long next = end;
-        for (long long every : {h->weighted.every, h->regions.every, h->lines.every})
+        for (long long every : {h->weighted.every, h->regions.every, h->lines.every, h->chg.every})
             if (every) next = std::min(next, (at / every + 1) * every);
         if (h->stats.every) next = std::min(next, (std::max(at, stats_floor(h)) / h->stats.every + 1) * h->stats.every);
         GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
@@ -271,6 +273,7 @@ static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long 
         GPF_TRY(regions_launch(h, next, base));
         GPF_TRY(lines_launch(h, next, base));
         GPF_TRY(stats_launch(h, next));
+        GPF_TRY(changes_launch(h, next, base));     // (k_small_steps' exit has left q^(n-1) in the other buffer)
         at = next;
     }
     return GPF_OK;

@@ -19,7 +19,7 @@ extern "C" int gpf_open_step(gpf_handle* h) {
         hipLaunchKernelGGL(k_copy3, dim3(blocks_for(2 * L.pitch)), dim3(256), 0, h->stream, h->beyond, h->beyond + 2 * L.pitch, 2ll * L.pitch);
     HIP_TRY(hipGetLastError());
     h->step_open = true;
-    h->prev_state_valid = false;            // the other buffer becomes the working field
+    prev_state_lost(h, PREV_LOST_STAGEWISE);        // the other buffer becomes the working field
     h->open_first_closures = true;
     h->g1_ready = false;
     h->host_step = s.step; h->next_step = s.step;

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import _lib
 from .problem import Problem, _film_series, _in_main_thread, _termination_signals
-from .series import SERIES, _Series, _integral_sections, _integral_stride
+from .series import ALL_SERIES, _Series, _integral_sections, _integral_stride
 
 
 def member_tier(nx, ny):
@@ -63,7 +63,7 @@ def _refusal(p):
                                      f"({_lib.SMALL_GRID_DOUBLES_PER_CELL} doubles per cell, ghost cells included, in "
                                      f"{_lib.SMALL_GRID_LDS_BYTES // 1024} KB) nor the workspace tier (at most "
                                      f"{_lib.MID_GRID_MAX_CELLS} cells, ghost cells included)")
-    for row in sorted((r for r in SERIES if r.refusal), key=lambda r: r.refusal[0]):
+    for row in sorted((r for r in ALL_SERIES if r.refusal), key=lambda r: r.refusal[0]):
         if getattr(p, row.marker, None) is not None:            # (getattr: a Problem made without __init__ may lack the attribute)
             return NotImplementedError, f"{row.noun} are armed on it ({row.refusal[1]}): {row.clear}(), or run it alone"
     return None

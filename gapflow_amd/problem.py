@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from . import __version__
 from .io import read_yaml_input, write_yaml, create_output_directory, history_to_csv
-from .series import (SERIES, _Series, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
+from .series import (ALL_SERIES, SERIES, _Series, _changes_stride, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
                      _integral_stride, _line_centre, _line_entries, _line_span, _lines_stride, _probe_cells, _region_entries,
                      _regions_stride, _statistics_fields, _statistics_stride, _stride, _weight_planes, _weighted_stride)
 from .topography import Topography
@@ -44,6 +44,8 @@ FieldExtrema = namedtuple('FieldExtrema', ('step', 'time') + _lib.EXTREMA_NAMES 
 FieldExtrema.__doc__ = """Time series of Problem.extrema: step, time and the seven values (nrecords,), cells (nrecords, 7, 2) -- (ix, iy) of each value in the ghosted index space --, index: name -> position along the cells' second axis."""
 ElasticSeries = namedtuple('ElasticSeries', ('step', 'time') + _lib.ELASTIC_SERIES_NAMES + ('cells',))
 ElasticSeries.__doc__ = """Time series of Problem.elastic_series: step, time, the four sums and d_max, d_min (nrecords,), cells (nrecords, 2, 2) -- (ix, iy) of d_max, then of d_min, in the ghosted index space."""
+StepChanges = namedtuple('StepChanges', ('step', 'time') + _lib.CHANGE_NAMES + ('cells', 'index'))
+StepChanges.__doc__ = """Time series of Problem.changes: step, time and the eleven values (nrecords,), cells (nrecords, 3, 2) -- (ix, iy) of dmax_rho, dmax_jx, dmax_jy in the ghosted index space --, index: name of a maximum -> position along the cells' second axis."""
 
 
 def _film_series(rec, sx, sy):
@@ -157,6 +159,9 @@ class Problem:
         self._elastic_series_every = None
         if options.get('elastic_series'):           # options.elastic_series (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_elastic_series(options['elastic_series'])
+        self._changes_every = None
+        if options.get('changes'):                  # options.changes (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
+            self.set_changes(options['changes'])
         self._stats_every = None
         if options.get('statistics'):               # options.statistics (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_statistics(options['statistics'], options.get('statistics_fields', _lib.STATS_FIELDS), options.get('statistics_after', 0))
@@ -1122,6 +1127,83 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'elastic_series.npz'), **self.elastic_series._asdict())
 
     # -------------------------------------------------------------------------------------
+    # step changes (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _changes_refusal(self):
+        if self._gp_models or self._cfg.thinning or self._elastic:
+            raise NotImplementedError("changes: surrogate, shear-thinning and elastic problems step stage-wise, which keeps no "
+                                      "previous state on the device")
+
+    def set_changes(self, every=1):
+        """Record how far each conserved field moved in every step whose count is a multiple of `every`, on the device, behind
+        the fused step, whichever way the steps are taken (`update()`, `run()`, batches of any length).
+
+        Per record, over the interior cells 1..Nx x 1..Ny, with d = q(step n) - q(step n - 1) per field: d2_rho, d2_jx, d2_jy
+        (sum of d d, times dx dy), q2_rho, q2_jx, q2_jy (sum of q q of the new state, times dx dy: the relative L2 change of a
+        field is sqrt(d2 / q2), its rate that over `dt`), dmass (sum of d_rho h dx dy with the gap the device holds: the mass
+        defect of the step, well conditioned because d_rho is an (almost always) exact difference), dmax_rho, dmax_jx, dmax_jy
+        (the largest |d|, each with its cell (ix, iy) of the ghosted index space, ties going to the smallest ix, then the
+        smallest iy) and dt, the step size of that step.  No sign convention, no normalisation; ghost cells never contribute.
+        The state before the step is the device's other buffer: nothing is downloaded and batches stay whole; on grids small
+        enough for the one-workgroup kernel the batch is cut at every recorded step.  The same two states give the same bits
+        whatever the batch size or stride.  A step that is rolled back as invalid leaves no record.  Starts a new series (see
+        ``changes``).  Checkpoints do not carry the series: a problem restored from one whose options hold `changes` has it
+        armed again and its series begins at the restart step.  Not available on problems that step stage-wise (surrogate
+        closures, shear thinning, an elastic gap)."""
+        self._changes_refusal()
+        every = _changes_stride(every, allow_zero=False)
+        _lib.check(self._lib.gpf_changes_set(self._h, every))
+        self._changes_every, self._changes_rec = every, _Series('changes', every)
+
+    def clear_changes(self):
+        """Stop recording and drop the series."""
+        if self._changes_every is not None:
+            _lib.check(self._lib.gpf_changes_clear(self._h))
+        self._changes_every = None
+
+    @property
+    def changes(self):
+        """StepChanges(step, time, d2_rho, ..., dt, cells, index) of every recorded step since set_changes (or _pre_run), across
+        `update()` and `run()` calls; None when the series is not armed.  cells[n, index[name]] is the (ix, iy) of `name`."""
+        if self._changes_every is None:
+            return None
+        rec, nq, nm = self._changes_rec, len(_lib.CHANGE_NAMES), len(_lib.CHANGE_MAXIMA)
+        vals = rec.stacked(0, (nq,))
+        return StepChanges(rec.step_array(), rec.time_array(), *[vals[:, k] for k in range(nq)], rec.stacked(1, (nm, 2), np.int32),
+                           {name: k for k, name in enumerate(_lib.CHANGE_MAXIMA)})
+
+    def step_change(self):
+        """The same record for the current state against the state before the last step, as a dict: the eleven names of
+        ``changes`` and `dmax_rho_cell`, `dmax_jx_cell`, `dmax_jy_cell` = (ix, iy).  Bit for bit what that step recorded or
+        would have.  Armed or not.  Reads only.  The library's state error (GapflowHipError) when the previous state is not
+        on the device: before the first step, after `q` was assigned or `init_from`, after the closures were re-evaluated
+        (reading `pressure.pressure` redoes the predictor into that buffer); the next `update()` brings it back."""
+        self._changes_refusal()
+        self._sync_to_device()
+        vals = np.empty(len(_lib.CHANGE_NAMES))
+        cells = np.zeros((len(_lib.CHANGE_MAXIMA), 2), dtype=np.int32)
+        _lib.check(self._lib.gpf_changes_now(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32))))
+        res = {name: np.float64(vals[k]) for k, name in enumerate(_lib.CHANGE_NAMES)}
+        for k, name in enumerate(_lib.CHANGE_MAXIMA):
+            res[name + '_cell'] = (int(cells[k, 0]), int(cells[k, 1]))
+        return res
+
+    def _collect_changes(self, entries, before):
+        """The records of the stepping call that took the step count from `before` through `entries` (its committed steps)."""
+        if self._changes_every is None:
+            return
+        nq, nm = len(_lib.CHANGE_NAMES), len(_lib.CHANGE_MAXIMA)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_changes_read(self._h, _lib.as_dp(b[0]), b[1].ctypes.data_as(C.POINTER(C.c_int32)), n, steps, have))
+        self._changes_rec.collect(read, entries, before, [((nq,), np.float64), ((nm, 2), np.int32)])
+
+    def _write_changes(self):
+        s = self.changes._asdict()
+        index = s.pop('index')
+        np.savez(os.path.join(self.outdir, 'changes.npz'), names=np.array(sorted(index, key=index.get)), **s)
+
+    # -------------------------------------------------------------------------------------
     # running field statistics (no reference counterpart; DESIGN.md 3.3j)
     # -------------------------------------------------------------------------------------
     def set_statistics(self, every=1, fields=_lib.STATS_FIELDS, after=0):
@@ -1205,7 +1287,7 @@ class Problem:
         self.dt = sc.dt
         self.tol = self.numerics['tol']
         self.max_it = self.numerics['max_it']
-        for row in SERIES:                          # the step count starts over: so does every armed series
+        for row in ALL_SERIES:                      # the step count starts over: so does every armed series
             if row.recorder is not None and getattr(self, row.marker) is not None:
                 getattr(self, row.recorder).reset()
 
@@ -1234,7 +1316,7 @@ class Problem:
         log: its n per-step records, zero where none was written (shared with Ensemble, whose members' batches run in one launch)."""
         entries = [log[i] for i in range(ran)]
         self._absorb(entries)
-        for row in SERIES:
+        for row in ALL_SERIES:
             if row.fused:
                 getattr(self, row.collect)(entries, before)
         if ran > 0:
@@ -1389,7 +1471,7 @@ class Problem:
         print(33 * '=')
         if not silent:
             history_to_csv(os.path.join(self.outdir, 'history.csv'), self.history)
-            for row in SERIES:                      # (the statistics last)
+            for row in ALL_SERIES:                  # (the statistics last of SERIES, the later series behind them)
                 if getattr(self, row.marker) is not None:
                     getattr(self, row.write)()
             for name, m in self._gp_models.items():  # problem.py:490-503
@@ -1501,6 +1583,12 @@ def _own_extrema(input_dict, opts, base_dir):
         input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
 
 
+def _own_changes(input_dict, opts, base_dir):
+    """`options.changes: N` (the stride; 0 or absent: off)."""
+    if opts.get('changes') is not None:
+        input_dict['options']['changes'] = _changes_stride(opts['changes'])
+
+
 def _own_elastic_series(input_dict, opts, base_dir):
     """`options.elastic_series: N` (the stride; 0 or absent: off)."""
     if opts.get('elastic_series') is not None:
@@ -1567,7 +1655,7 @@ def _own_init_from(input_dict, opts, base_dir):
 
 
 _OWN_KEYS = (_own_checkpoint_freq, _own_probes, _own_integrals, _own_extrema, _own_elastic_series, _own_weighted, _own_statistics,
-             _own_regions, _own_lines, _own_init_from)
+             _own_regions, _own_lines, _own_changes, _own_init_from)
 
 
 def _keep(keys, input_dict, ymlstring, base_dir=None):
@@ -1596,6 +1684,7 @@ def _keep_weighted(input_dict, ymlstring, base_dir=None): _keep([_own_weighted],
 def _keep_statistics(input_dict, ymlstring): _keep([_own_statistics], input_dict, ymlstring)
 def _keep_regions(input_dict, ymlstring): _keep([_own_regions], input_dict, ymlstring)
 def _keep_lines(input_dict, ymlstring): _keep([_own_lines], input_dict, ymlstring)
+def _keep_changes(input_dict, ymlstring): _keep([_own_changes], input_dict, ymlstring)
 def _keep_init_from(input_dict, ymlstring, base_dir=None): _keep([_own_init_from], input_dict, ymlstring, base_dir)
 
 

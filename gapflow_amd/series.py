@@ -1,7 +1,7 @@
 """Host side of the recorded series: the one recorder, `_Series`; the one table of the series' lifecycle,
 `SERIES`; the one stride check; and the validators of what the `set_*` methods and the YAML keys are given.  Nothing here
-touches a device, and nothing here imports `problem`: a new series is one row of `SERIES`, one `_Series` in its `set_*` and a
-two-line `read` closure in its `_collect_*`.
+touches a device, and nothing here imports `problem`: a new series is one row of `SERIES_MORE` (Problem and Ensemble walk
+`ALL_SERIES`), one `_Series` in its `set_*` and a two-line `read` closure in its `_collect_*`.
 """
 import ctypes as C
 from collections import namedtuple
@@ -95,6 +95,11 @@ SERIES = (
          'clear_elastic_series', None, False),
     _Row('_stats_every', None, None, '_write_statistics', 'statistics', 'clear_statistics', (2, CUTS), False),
 )
+# The series added since: behind SERIES in the arming, collecting, writing and refusal order
+SERIES_MORE = (
+    _Row('_changes_every', '_changes_rec', '_collect_changes', '_write_changes', 'changes', 'clear_changes', (7, CUTS), True),
+)
+ALL_SERIES = SERIES + SERIES_MORE
 
 
 def _stride(label, value, low, what='the stride'):
@@ -110,6 +115,7 @@ def _regions_stride(every, allow_zero=False): return _stride('regions', every, 0
 def _lines_stride(every, allow_zero=False): return _stride('lines', every, 0 if allow_zero else 1)
 def _extrema_stride(every, allow_zero=True): return _stride('extrema', every, 0 if allow_zero else 1)
 def _elastic_series_stride(every, allow_zero=True): return _stride('elastic series', every, 0 if allow_zero else 1)
+def _changes_stride(every, allow_zero=True): return _stride('changes', every, 0 if allow_zero else 1)
 def _statistics_stride(v, key, low): return _stride('statistics', v, low, key)
 
 

@@ -467,6 +467,14 @@ class SlabProblem:
         """The deformation series is taken on unsliced problems only."""
         raise NotImplementedError("elastic series: not available on a SlabProblem")
 
+    def set_changes(self, *args, **kwargs):
+        """Step changes are recorded on unsliced problems only."""
+        raise NotImplementedError("changes: not available on a SlabProblem")
+
+    def step_change(self, *args, **kwargs):
+        """Step changes are taken on unsliced problems only."""
+        raise NotImplementedError("changes: not available on a SlabProblem")
+
     def set_statistics(self, *args, **kwargs):
         """Running field statistics are kept on unsliced problems only."""
         raise NotImplementedError("statistics: not available on a SlabProblem")
@@ -485,7 +493,7 @@ class SlabProblem:
         # the options that arm what the methods above refuse are refused as those are
         for key, label in (('init_from', 'init_from'), ('probes', 'probes'), ('integrals', 'integrals'),
                            ('weighted_integrals', 'weighted integrals'), ('regions', 'regions'), ('lines', 'lines'), ('extrema', 'extrema'),
-                           ('elastic_series', 'elastic series'), ('statistics', 'statistics')):
+                           ('elastic_series', 'elastic series'), ('statistics', 'statistics'), ('changes', 'changes')):
             given = opts.get(key)
             if given is not None if key in ('probes', 'integrals') else given:      # (the others: 0 is off, as on a Problem)
                 raise NotImplementedError(f"{label}: not available on a SlabProblem")

@@ -405,10 +405,10 @@ int gpf_checkpoint_load(gpf_handle* h, const void* host, size_t bytes);
 int gpf_checkpoint_pack_probe(gpf_handle* h, int reps, double* ms_per_pass);
 
 /* ---- the per-step series and their gpf_*_time diagnostics ------------------------------------------------------------------ */
-/* A handle records up to eight series behind its committed steps: point probes, film integrals, weighted film integrals,
- * regions, line profiles, field extrema, running statistics and, with an elastic gap, the deformation series (the sections
+/* A handle records up to nine series behind its committed steps: point probes, film integrals, weighted film integrals,
+ * regions, line profiles, field extrema, running statistics, step changes and, with an elastic gap, the deformation series (the sections
  * below).  Each has a diagnostic gpf_<series>_time that enqueues n steps as gpf_step does (an elastic handle's: as its host
- * does, stage-wise) and reports the time on the handle's stream.  ONE RULE holds for all eight:
+ * does, stage-wise) and reports the time on the handle's stream.  ONE RULE holds for all nine:
  *   - the call puts aside every series but the one it times, and that one too in the modes that do not record: nothing else
  *     is launched behind the steps, and what was armed is armed again, unchanged, when the call returns (also on an error);
  *   - it leaves no records of any other series for their _read calls (0 records; probes: 0 steps): it is a stepping call in
@@ -638,6 +638,50 @@ int gpf_elastic_series_now(gpf_handle* h, double values[6], int32_t cells[4]);
  * gpf_integrals_time steps an elastic handle the same way.  The other series: the one rule of the gpf_*_time diagnostics
  * (before the point probes). */
 int gpf_elastic_series_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
+/* ---- step changes (no reference counterpart: its users download q after every step and subtract on the host) --------------- */
+/* How far the committed step n moved each conserved field, reduced on the device.  With d = q^n - q^(n-1) per field (rho, jx,
+ * jy) over the interior cells 1..Nx x 1..Ny, a record is eleven doubles and three cells:
+ *   0 d2_rho, 1 d2_jx, 2 d2_jy        sum of d d, times dx dy
+ *   3 q2_rho, 4 q2_jx, 5 q2_jy        sum of q^n q^n, times dx dy: the relative L2 change is sqrt(d2 / q2), its rate that over dt
+ *   6 dmass                           sum of d_rho h, times dx dy; h is plane 0 of the gap the handle holds
+ *   7 dmax_rho, 8 dmax_jx, 9 dmax_jy  the largest |d|, each with its cell (ix, iy) of the ghosted index space
+ *   10 dt                             the step size of that step (the device's dt_last)
+ * Host layout: values [record][11] doubles, cells [record][3][2] int32.  No sign convention, no normalisation; ghost cells never
+ * contribute.  q^n is the current q buffer and q^(n-1) the OTHER one: a fused step reads one and writes the other, the
+ * one-workgroup kernel leaves both on exit, a checkpoint carries both.  d of neighbouring states is a difference of nearly equal
+ * numbers and hence (almost always) exact, which makes dmass a well-conditioned measure of one step's mass defect where the
+ * difference of two masses is not.  The sums are added in the film integrals' order (pair walk, fold tree, row loop), every
+ * product rounded on its own, and multiplied by dx dy once; the maxima are ordered by the field extrema's one comparison (the
+ * larger value, then the smaller ix, then the smaller iy).  A record is a pure function of (q^n, q^(n-1), h, dt): no
+ * floating-point atomics, the same bits whatever the batch size or the stride, behind a step or from gpf_changes_now.  Recording
+ * only reads: q and all scalars of a run are bitwise those of the same run without it, and with nothing armed no launch differs.
+ *   gpf_changes_set    arms recording after every committed step whose new step count is a multiple of `every` (>= 1, else
+ *                      GPF_ERR_INVALID) and starts with empty records.  GPF_ERR_STATE on a slab and while a stage-wise step is
+ *                      open; GPF_ERR_INVALID on handles that step stage-wise -- surrogate closures, shear thinning, an elastic gap.
+ *   gpf_changes_clear  disarms and frees the buffers.
+ *   gpf_changes_read   the records of the LAST gpf_step call and the step count of each in steps_out (values, cells, steps_out may
+ *                      be NULL); *n_records how many the call left, min(*n_records, capacity_records) are copied.  A step that
+ *                      did not run or was rolled back leaves none.  GPF_ERR_STATE unless armed.
+ *   gpf_changes_now    the same record for the current state against the state before the last step, armed or not.
+ *                      GPF_ERR_STATE, naming the cause, when that state is not on the device: no step committed since gpf_pre_run,
+ *                      an upload, a resampled start or a checkpoint without it; gpf_update_closures has reused the buffer; the last
+ *                      step was stage-wise; the step plan's timing launches used it.  GPF_ERR_STATE on an invalid run state.
+ * Where they are written: k_change_partial (one workgroup per interior row, 7 planes read: 56 B per cell) + k_change_fold
+ * (csrc/change_kernels.hip) behind every due step of a gpf_step batch, in stream order before the next step overwrites q^(n-1),
+ * guarded by the device's run state like every recording kernel.  A handle that steps through the one-workgroup kernel has its
+ * batch cut at every recorded step, as for the weighted integrals.  gpf_close_step, gpf_step_timed, ensembles and the slab calls
+ * record nothing.  Buffers ((log_cap + 1) records and a row scratch) are allocated on first use and freed by gpf_changes_clear /
+ * gpf_destroy once the stream is idle.  16-byte pair loads where the planes are aligned for them, 8-byte loads otherwise;
+ * GPF_FILM_NARROW (read when the buffers are allocated) asks for the 8-byte loads regardless -- a test switch; same bits. */
+int gpf_changes_set(gpf_handle* h, int64_t every);
+int gpf_changes_clear(gpf_handle* h);
+int gpf_changes_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_changes_now(gpf_handle* h, double values[11], int32_t cells[6]);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording, 1 recording at the armed stride (tools/changes_time.py).  The other series: the one rule of the
+ * gpf_*_time diagnostics (before the point probes). */
+int gpf_changes_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
 /* ---- running field statistics (no reference counterpart: its users download q after every step and average on the host) ---- */
 /* WHERE on the film something happened over a run: per cell of the GHOSTED grid (Nx+2) x (Ny+2) -- the shape q has -- and per
