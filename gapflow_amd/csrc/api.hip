@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -72,6 +73,22 @@ static constexpr long long SMALL_GRID_LDS_BYTES = 150 * 1024;   // what k_small_
 // Why the other q buffer does not hold the state before the last committed step (gpf_handle::prev_lost)
 enum { PREV_LOST_NO_STEP = 0, PREV_LOST_CLOSURES, PREV_LOST_STAGEWISE, PREV_LOST_PLAN };
 
+// What every strided series of a handle keeps (gpf_handle: the per-series structs derive from it): the recording stride that arms
+// it; the records of the last stepping call on the host -- doubles, for some a second channel of int32 (`cells`) or int64
+// (`ints`) -- with their step counts; and, for the series an elastic handle records behind gpf_elastic_update, whether a closed
+// step waits for that call and the step count it began at (api_series.inc: series_close_*).
+struct SeriesStore {
+    long long every = 0;                    // 0: not armed
+    std::vector<double> host;
+    std::vector<int32_t> cells;
+    std::vector<long long> ints, steps;
+    bool pending = false;
+    long long pending_base = 0;
+    bool armed() const { return every != 0; }
+    void forget() { host.clear(); cells.clear(); ints.clear(); steps.clear(); }
+    void disarm() { every = 0; pending = false; forget(); }
+};
+
 struct gpf_handle {
     gpf_config cfg;
     Layout L;
@@ -109,59 +126,53 @@ struct gpf_handle {
     int nspart = 0;
     LogEntry* log = nullptr;
     long long log_cap = 0;
-    // point probes (api_probes.inc): n cells, nv values per record; the device records of the batch in flight ([log_cap][n][nv],
-    // allocated by the first stepping call after gpf_probes_set); the records of the last stepping call on the host
+    // The per-step recorders (api_series.inc: the table SERIES walks them; api_<name>.inc: each one's kernels' arguments, buffers and
+    // entry points).  Every struct below holds its series' own device buffers and shapes; what they all keep -- the stride that
+    // arms them, the records of the last stepping call on the host -- is the SeriesStore they derive from.
+    // point probes (api_probes.inc): n cells (0: not armed), nv values per record; the device records of the batch in flight
+    // ([log_cap][n][nv], allocated by the first stepping call after gpf_probes_set); the records of the last stepping call on the
+    // host, one per step from `first_step` (no SeriesStore: they are armed by their count and keep no strided step list)
     // `dev`: the ProbeArgs of these buffers in device memory, for k_small_steps
-    struct { int n = 0, nv = 0; int* cells = nullptr; double* buf = nullptr; ProbeArgs* dev = nullptr; std::vector<double> host;
+    struct { long long n = 0; int nv = 0; int* cells = nullptr; double* buf = nullptr; ProbeArgs* dev = nullptr; std::vector<double> host;
              long long first_step = 0; } probes;
-    // film integrals (api_integrals.inc): recording stride (0: not armed), sections (nsx 0: not chosen yet), the device records of
-    // the batch in flight ([log_cap + 1][9 + nsx + nsy]) and the row scratch ([Nx][FILM_NV]), both allocated on first use (`narrow`:
-    // GPF_FILM_NARROW was set then, 8-byte loads); the records of the last stepping call and their step counts on the host
+    // film integrals (api_integrals.inc): sections (nsx 0: not chosen yet), the device records of the batch in flight
+    // ([log_cap + 1][9 + nsx + nsy]) and the row scratch ([Nx][FILM_NV]), both allocated on first use (`narrow`: GPF_FILM_NARROW
+    // was set then, 8-byte loads)
     // `dev`: the FilmBlockArgs of the record buffer in device memory, for k_small_steps (written with the buffers, freed with them)
-    // `pending`: an elastic handle's closed step waits for gpf_elastic_update to record it, `pending_base` the count it began at
-    struct { long long every = 0; int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
-             double* rec = nullptr; double* part = nullptr; FilmBlockArgs* dev = nullptr; bool narrow = false; bool pending = false;
-             long long pending_base = 0; std::vector<double> host; std::vector<long long> steps; } integ;
-    // weighted film integrals (api_weighted.inc): recording stride (0: not armed) and number of weight planes K; the planes on the
-    // device in this handle's Layout ([K] planes, pitch and offset as topo's, ghost cells zero), the row scratch ([K][Nx][9]) and the
-    // device records of the batch in flight ([log_cap + 1][K][9]), all allocated by gpf_weighted_set (`narrow`: GPF_FILM_NARROW was
-    // set then, 8-byte loads); the records of the last stepping call and their step counts on the host
-    struct { long long every = 0; int K = 0; double* w = nullptr; double* part = nullptr; double* rec = nullptr; bool narrow = false;
-             std::vector<double> host; std::vector<long long> steps; } weighted;
-    // region series (api_regions.inc): recording stride (0: not armed) and number of regions K; the region list on the device
-    // ([K] Region), the row scratch ([K][Nx][9] doubles, [K][Nx][3] int32) and the device records of the batch in flight
-    // ([log_cap + 1][K][9] doubles, [log_cap + 1][K][5] int64), all allocated by gpf_regions_set (`narrow`: GPF_FILM_NARROW was set
-    // then, 8-byte loads); the records of the last stepping call and their step counts on the host
-    struct { long long every = 0; int K = 0; Region* defs = nullptr; double* part = nullptr; int* ipart = nullptr; double* rec = nullptr;
-             long long* irec = nullptr; bool narrow = false; std::vector<double> host; std::vector<long long> ihost, steps; } regions;
-    // line profiles (api_lines.inc): recording stride (0: not armed), number of lines K and the lines as the kernels read them;
-    // doubles per record and records the device buffer holds (a batch never leaves more: lines_batch); the device records of the
-    // batch in flight ([capacity + 1][rec_doubles]) and the chunk sums of the bands along y, both allocated by gpf_lines_set; the
-    // records of the last stepping call and their step counts on the host
-    struct { long long every = 0; int K = 0; Line defs[LINE_MAX_K] = {}; long long rec_doubles = 0, capacity = 0; double* rec = nullptr;
-             double* scratch = nullptr; std::vector<double> host; std::vector<long long> steps; } lines;
-    // field extrema (api_extrema.inc): recording stride (0: not armed); the device records of the batch in flight ([log_cap + 1][7]
-    // doubles, [log_cap + 1][14] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was set then);
-    // `dev`: the ExtremaArgs of these buffers in device memory, for k_small_steps; the records of the last stepping call on the host.
-    // `pending`: an elastic handle's closed step waits for gpf_elastic_update to record it, `pending_base` the count it began at
-    struct { long long every = 0; ExtremaArgs a = {}; ExtremaArgs* dev = nullptr; bool narrow = false; bool pending = false; long long pending_base = 0;
-             std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } extr;
-    // deformation series of an elastic handle (api_elastic_series.inc): recording stride (0: not armed); the device records
-    // ([log_cap + 1][6] doubles, [log_cap + 1][4] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was
-    // set then); the records of the last stepping call on the host.  `pending`, `pending_base`: as the extrema's -- every record
-    // is written behind gpf_elastic_update
-    struct { long long every = 0; double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
-             bool narrow = false; bool pending = false; long long pending_base = 0;
-             std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } eldef;
-    // step-change series (api_changes.inc): recording stride (0: not armed); the device records ([log_cap + 1][11] doubles,
-    // [log_cap + 1][6] int32) and the row scratch, allocated on first use (`narrow`: GPF_FILM_NARROW was set then); the records of
-    // the last stepping call on the host
-    struct { long long every = 0; double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
-             bool narrow = false; std::vector<double> host; std::vector<int32_t> cells; std::vector<long long> steps; } chg;
+    struct : SeriesStore { int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
+             double* rec = nullptr; double* part = nullptr; FilmBlockArgs* dev = nullptr; bool narrow = false; } integ;
+    // weighted film integrals (api_weighted.inc): number of weight planes K; the planes on the device in this handle's Layout
+    // ([K] planes, pitch and offset as topo's, ghost cells zero), the row scratch ([K][Nx][9]) and the device records of the batch
+    // in flight ([log_cap + 1][K][9]), all allocated by gpf_weighted_set (`narrow`: GPF_FILM_NARROW was set then, 8-byte loads)
+    struct : SeriesStore { int K = 0; double* w = nullptr; double* part = nullptr; double* rec = nullptr; bool narrow = false; } weighted;
+    // region series (api_regions.inc): number of regions K; the region list on the device ([K] Region), the row scratch
+    // ([K][Nx][9] doubles, [K][Nx][3] int32) and the device records of the batch in flight ([log_cap + 1][K][9] doubles,
+    // [log_cap + 1][K][5] int64 -> the store's `ints`), all allocated by gpf_regions_set (`narrow`: as above)
+    struct : SeriesStore { int K = 0; Region* defs = nullptr; double* part = nullptr; int* ipart = nullptr; double* rec = nullptr;
+             long long* irec = nullptr; bool narrow = false; } regions;
+    // line profiles (api_lines.inc): number of lines K and the lines as the kernels read them; doubles per record and records the
+    // device buffer holds (a batch never leaves more: lines_batch); the device records of the batch in flight
+    // ([capacity + 1][rec_doubles]) and the chunk sums of the bands along y, both allocated by gpf_lines_set
+    struct : SeriesStore { int K = 0; Line defs[LINE_MAX_K] = {}; long long rec_doubles = 0, capacity = 0; double* rec = nullptr;
+             double* scratch = nullptr; } lines;
+    // field extrema (api_extrema.inc): the device records of the batch in flight ([log_cap + 1][7] doubles, [log_cap + 1][14] int32
+    // -> the store's `cells`) and the row scratch, allocated on first use (`narrow`: as above)
+    // `dev`: the ExtremaArgs of these buffers in device memory, for k_small_steps
+    struct : SeriesStore { ExtremaArgs a = {}; ExtremaArgs* dev = nullptr; bool narrow = false; } extr;
+    // deformation series of an elastic handle (api_elastic_series.inc): the device records ([log_cap + 1][6] doubles,
+    // [log_cap + 1][4] int32) and the row scratch, allocated on first use (`narrow`: as above); every record is written behind
+    // gpf_elastic_update (the store's `pending`)
+    struct : SeriesStore { double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
+             bool narrow = false; } eldef;
+    // step-change series (api_changes.inc): the device records ([log_cap + 1][11] doubles, [log_cap + 1][6] int32) and the row
+    // scratch, allocated on first use (`narrow`: as above)
+    struct : SeriesStore { double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
+             bool narrow = false; } chg;
     // running field statistics (api_stats.inc): recording stride (0: not armed), the step count records are taken above, the
     // requested fields (bit 0 p, 1 rho, 2 jx, 3 jy) and the step count at which the window began; the accumulator planes
     // ([requested fields][mean m2 min max] planes of this handle's Layout) and the device's record of the window, both allocated by
     // gpf_stats_set (`narrow`: GPF_FILM_NARROW was set then, 8-byte accesses); that record as the last stepping call left it
+    // (no SeriesStore: a window, not a call's records)
     struct { long long every = 0, after = 0, arm_step = 0; int mask = 0; double* acc = nullptr; StatsRecord* rec = nullptr; bool narrow = false;
              StatsRecord host = {}; } stats;
     double* stage = nullptr;                // contiguous staging for upload/download
@@ -404,13 +415,16 @@ extern "C" int gpf_create(const gpf_config* cfg, gpf_handle** out) {
     return GPF_OK;
 }
 
+static void series_destroy(gpf_handle* h);
+
 extern "C" int gpf_destroy(gpf_handle* h) {
     if (!h) return GPF_OK;
     hipSetDevice(h->cfg.device);
     // work may still be queued against the buffers below (transforms, a step a failing rank left behind): let it drain first
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
-    void* ptrs[] = {h->probes.cells, h->probes.buf, h->probes.dev, h->integ.rec, h->integ.part, h->integ.dev, h->weighted.w, h->weighted.part, h->weighted.rec, h->regions.defs, h->regions.part, h->regions.ipart, h->regions.rec, h->regions.irec, h->lines.rec, h->lines.scratch, h->extr.a.val, h->extr.a.cell, h->extr.a.row_val, h->extr.a.row_iy, h->extr.dev, h->eldef.rec, h->eldef.cell, h->eldef.part, h->eldef.row_val, h->eldef.row_iy, h->chg.rec, h->chg.cell, h->chg.part, h->chg.row_val, h->chg.row_iy, h->stats.acc, h->stats.rec, h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
+    series_destroy(h);      // the series' buffers (api_series.inc)
+    void* ptrs[] = {h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
                     h->gp[2].Z, h->gp[2].alpha, h->gp[2].L, h->gp[0].Linv, h->gp[1].Linv, h->gp[2].Linv, h->gp[0].W, h->gp[1].W, h->gp[2].W};
@@ -1078,8 +1092,8 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
     a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
     a.log = h->log; a.log_base = log_base; a.log_cap = h->log_cap; a.L = L; a.E = h->E; a.nsteps = nsteps; a.honor_stop = honor_stop;
     a.probe = h->probes.n ? h->probes.dev : nullptr;
-    a.extrema = h->extr.every ? h->extr.dev : nullptr;
-    a.film = h->integ.every ? h->integ.dev : nullptr;       // (null while armed: a diagnostic that did not go through integrals_begin; it records none)
+    a.extrema = h->extr.armed() ? h->extr.dev : nullptr;
+    a.film = h->integ.armed() ? h->integ.dev : nullptr;       // (null while armed: a diagnostic that did not go through integrals_begin; it records none)
     const size_t lds = (size_t)(L.Nx + 2) * (L.Ny + 2) * SMALL_DOUBLES_PER_CELL * 8;
     EOS_DISPATCH(h->cfg.eos, {
         if (h->Ls) {
@@ -1095,8 +1109,6 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
     h->g1_ready = false;
     return GPF_OK;
 }
-
-static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base);
 
 #include "api_series.inc"
 #include "api_probes.inc"
@@ -1120,40 +1132,22 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
     GPF_TRY(enter(h));
     int64_t done = 0, logged = 0;
     const bool small = small_grid_eligible(h);
-    GPF_TRY(probes_begin(h));
-    GPF_TRY(integrals_begin(h));
-    GPF_TRY(weighted_begin(h));
-    GPF_TRY(regions_begin(h));
-    GPF_TRY(lines_begin(h));
-    GPF_TRY(extrema_begin(h));
-    GPF_TRY(stats_begin(h));
-    GPF_TRY(changes_begin(h));
+    for (const Series& r : SERIES)
+        if (r.fused) GPF_TRY(r.begin(h));
     while (done < n) {
         const long long base = h->host_step;
         const int64_t batch = lines_batch(h, std::min<int64_t>(n - done, h->log_cap), base);        // (lines: no more records than their buffer holds)
         if (small) GPF_TRY(small_batch_cut(h, batch, honor_stop, base));       // the batch, cut at the union of the armed series' steps
         else for (int64_t i = 0; i < batch; ++i) {
             GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));
-            GPF_TRY(probes_launch(h, base + i + 1, base));      // no launch without probes
-            GPF_TRY(integrals_launch(h, base + i + 1, base));   // nor without integrals, nor off their stride
-            GPF_TRY(weighted_launch(h, base + i + 1, base));    // nor without weighted integrals, nor off theirs
-            GPF_TRY(regions_launch(h, base + i + 1, base));     // nor without regions, nor off theirs
-            GPF_TRY(lines_launch(h, base + i + 1, base));       // nor without lines, nor off theirs
-            GPF_TRY(extrema_launch(h, base + i + 1, base));     // nor without extrema, nor off theirs
-            GPF_TRY(stats_launch(h, base + i + 1));             // nor without statistics, nor off theirs
-            GPF_TRY(changes_launch(h, base + i + 1, base));     // nor without changes, nor off theirs; before the next step overwrites q^(n-1)
+            for (const Series& r : SERIES)      // no launch without the series armed, nor off its stride; the changes' before the next step overwrites q^(n-1)
+                if (r.fused) GPF_TRY(r.launch(h, base + i + 1, base));
         }
         StepState s;
         GPF_TRY(read_state(h, s));
         const long long ran = s.step - base;
-        GPF_TRY(probes_collect(h, ran));
-        GPF_TRY(integrals_collect(h, base, ran));
-        GPF_TRY(weighted_collect(h, base, ran));
-        GPF_TRY(regions_collect(h, base, ran));
-        GPF_TRY(lines_collect(h, base, ran));
-        GPF_TRY(extrema_collect(h, base, ran));
-        GPF_TRY(stats_collect(h, s.step));
-        GPF_TRY(changes_collect(h, base, ran));
+        for (const Series& r : SERIES)
+            if (r.fused) GPF_TRY(r.collect(h, base, ran));
         const long long entries = ran + ((s.invalid && ran < batch) ? 1 : 0);
         if (log && entries > 0) {
             const long long take = std::min<long long>(entries, log_capacity - logged);

@@ -43,9 +43,9 @@ static int changes_buffers(gpf_handle* h) {
 
 // A stepping call begins: its records replace those of the call before
 static int changes_begin(gpf_handle* h) {
-    if (!h->chg.every) return GPF_OK;
+    if (!h->chg.armed()) return GPF_OK;
     GPF_TRY(changes_refusal(h, "gpf_step with changes armed"));
-    h->chg.host.clear(); h->chg.cells.clear(); h->chg.steps.clear();
+    h->chg.forget();
     return changes_buffers(h);
 }
 
@@ -78,47 +78,39 @@ static int changes_collect(gpf_handle* h, long long base, long long ran) {
                           series_channel(h->chg.cells, h->chg.cell, (size_t)2 * CHANGE_NMAX));
 }
 
+static SeriesBuffers changes_owned(gpf_handle* h) {
+    return {(void**)&h->chg.rec, (void**)&h->chg.cell, (void**)&h->chg.part, (void**)&h->chg.row_val, (void**)&h->chg.row_iy};
+}
+
 static int changes_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    GPF_TRY(series_free({(void**)&h->chg.rec, (void**)&h->chg.cell, (void**)&h->chg.part, (void**)&h->chg.row_val, (void**)&h->chg.row_iy}));
-    h->chg.every = 0;
-    h->chg.host.clear(); h->chg.cells.clear(); h->chg.steps.clear();
+    GPF_TRY(series_free(changes_owned(h)));
+    h->chg.disarm();
     return GPF_OK;
 }
 
 extern "C" int gpf_changes_set(gpf_handle* h, int64_t every) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(changes_refusal(h, "gpf_changes_set"));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_changes_set: every >= 1 required (gpf_changes_clear disarms), got " + std::to_string(every));
-    GPF_TRY(enter(h, true));
-    GPF_TRY(changes_release(h));
+    GPF_TRY(series_set_checks(h, SERIES[S_CHANGES], every, changes_refusal));
+    GPF_TRY(series_disarm(h, SERIES[S_CHANGES]));
     h->chg.every = every;
     return GPF_OK;
 }
 
-extern "C" int gpf_changes_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_changes_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return changes_release(h);
-}
+extern "C" int gpf_changes_clear(gpf_handle* h) { return series_clear(h, SERIES[S_CHANGES]); }
 
 extern "C" int gpf_changes_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (!h->chg.every) return fail(GPF_ERR_STATE, "gpf_changes_read: no changes are armed (gpf_changes_set)");
+    if (!h->chg.armed()) return fail(GPF_ERR_STATE, "gpf_changes_read: no changes are armed (gpf_changes_set)");
     series_read(h->chg.steps, capacity_records, steps_out, n_records, series_channel(h->chg.host, values, (size_t)CHANGE_NREC),
                 series_channel(h->chg.cells, cells, (size_t)2 * CHANGE_NMAX));
     return GPF_OK;
 }
 
 extern "C" int gpf_changes_now(gpf_handle* h, double values[11], int32_t cells[6]) {
-    if (!h || !values || !cells) return fail(GPF_ERR_INVALID, "gpf_changes_now: null argument");
-    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_changes_now: upload q and topography first");
-    GPF_TRY(changes_refusal(h, "gpf_changes_now"));
+    GPF_TRY(series_now_checks(h, SERIES[S_CHANGES], values && cells, changes_refusal));
     GPF_TRY(enter(h, true));
     StepState s;
-    GPF_TRY(read_state(h, s));
-    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_changes_now: the run state is flagged invalid (the last step was rolled back)");
+    GPF_TRY(series_now_state(h, SERIES[S_CHANGES], s));
     if (!h->prev_state_valid) {
         const char* why = h->prev_lost == PREV_LOST_CLOSURES ? "gpf_update_closures has reused the buffer for the predictor's field"
                         : h->prev_lost == PREV_LOST_STAGEWISE ? "the last step was stage-wise"
@@ -137,16 +129,6 @@ extern "C" int gpf_changes_now(gpf_handle* h, double values[11], int32_t cells[6
 // Diagnostic (tools/changes_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed changes are put aside
 // for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_changes_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_changes_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_changes_time: call gpf_pre_run first");
-    GPF_TRY(changes_refusal(h, "gpf_changes_time"));
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
-        return fail(GPF_ERR_INVALID, "gpf_changes_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
-    if (mode == 1 && !h->chg.every) return fail(GPF_ERR_STATE, "gpf_changes_time: mode 1 needs armed changes (gpf_changes_set)");
-    GPF_TRY(enter(h));
-    GPF_TRY(changes_begin(h));          // (the buffers, while the stride is still the armed one)
-    SeriesAside aside(h, mode == 1 ? &h->chg.every : nullptr);
-    return series_time(h, "gpf_changes_time", aside,
-                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return changes_launch(h, expect, base); }); },
-                       [&](long long base, long long ran) { return changes_collect(h, base, ran); }, ms);
+    GPF_TRY(series_time_checks(h, SERIES[S_CHANGES], n, mode, 1, ms, "armed changes (gpf_changes_set)", changes_refusal));
+    return series_time_fused(h, SERIES[S_CHANGES], n, mode, ms);
 }

@@ -56,7 +56,7 @@ extern "C" int gpf_elastic_update(gpf_handle* h) {
                        h->topo + L.plane, h->topo + 2 * L.plane);
     HIP_TRY(hipGetLastError());
     h->g1_ready = false;
-    GPF_TRY(extrema_after_elastic_update(h));   // an armed handle's closed step is recorded with the gap it now holds
-    GPF_TRY(integrals_after_elastic_update(h));
-    return eldef_after_elastic_update(h);
+    for (int k : SERIES_STAGEWISE)              // an armed handle's closed step is recorded with the gap it now holds
+        if (SERIES[k].store) GPF_TRY(series_after_elastic_update(h, SERIES[k]));
+    return GPF_OK;
 }

@@ -2,8 +2,8 @@
 // squared deflection, p d, film volume, the largest and smallest deflection with their cells -- reduced on the device behind the
 // gpf_elastic_update that follows a committed step whose count is a multiple of the armed stride, and handed out once per call.
 // Kernels: elastic_series_kernels.hip.  The gap deforms after the step closes, so a record written at gpf_close_step would pair
-// the new state with the gap of the step before: every record waits for the update (`pending`, as the extrema's and the film
-// integrals' on such a handle) and holds the state, the gap and the deformation the handle then holds.
+// the new state with the gap of the step before: every record waits for the update (SERIES_BEHIND_UPDATE, as the extrema's and
+// the film integrals' on such a handle) and holds the state, the gap and the deformation the handle then holds.
 
 // The cases the series does not cover
 static int eldef_refusal(const gpf_handle* h, const std::string& who) {
@@ -36,9 +36,9 @@ static int eldef_buffers(gpf_handle* h) {
 // A stepping call begins: its records replace those of the call before
 static int eldef_begin(gpf_handle* h) {
     h->eldef.pending = false;
-    if (!h->eldef.every) return GPF_OK;
+    if (!h->eldef.armed()) return GPF_OK;
     GPF_TRY(eldef_refusal(h, "a stepping call with the deformation series armed"));
-    h->eldef.host.clear(); h->eldef.cells.clear(); h->eldef.steps.clear();
+    h->eldef.forget();
     return eldef_buffers(h);
 }
 
@@ -58,78 +58,52 @@ static int eldef_enqueue(gpf_handle* h, long long expect, long long slot) {
     return GPF_OK;
 }
 
+// Behind gpf_elastic_update's launches (series_after_elastic_update): the record of the step that took the count to `expect`
+static int eldef_launch(gpf_handle* h, long long expect, long long base) {
+    if (!series_due(h->eldef.every, expect)) return GPF_OK;
+    return eldef_enqueue(h, expect, series_slot(base, expect, h->eldef.every));
+}
+
 static int eldef_collect(gpf_handle* h, long long base, long long ran) {
     return series_collect(h->eldef.every, h->eldef.steps, base, ran, series_channel(h->eldef.host, h->eldef.rec, (size_t)ELDEF_NREC),
                           series_channel(h->eldef.cells, h->eldef.cell, (size_t)2 * ELDEF_NEXT));
 }
 
-// gpf_close_step: the closed step's record waits for gpf_elastic_update
-static int eldef_close_step_launch(gpf_handle* h) {
-    GPF_TRY(eldef_begin(h));
-    if (!h->eldef.every) return GPF_OK;
-    h->eldef.pending = true; h->eldef.pending_base = h->host_step;
-    return GPF_OK;
-}
-
-// ... the step did not commit: nothing to wait for
-static void eldef_close_step_collect(gpf_handle* h, long long ran) {
-    if (ran < 1) h->eldef.pending = false;
-}
-
-// gpf_elastic_update, behind its launches: the record of the step gpf_close_step committed just before, at the armed stride
-static int eldef_after_elastic_update(gpf_handle* h) {
-    if (!h->eldef.pending) return GPF_OK;
-    h->eldef.pending = false;
-    const long long base = h->eldef.pending_base;
-    if (h->host_step != base + 1 || !series_due(h->eldef.every, h->host_step)) return GPF_OK;
-    GPF_TRY(eldef_enqueue(h, h->host_step, series_slot(base, h->host_step, h->eldef.every)));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return eldef_collect(h, base, 1);
+static SeriesBuffers eldef_owned(gpf_handle* h) {
+    auto& d = h->eldef;
+    return {(void**)&d.rec, (void**)&d.cell, (void**)&d.part, (void**)&d.row_val, (void**)&d.row_iy};
 }
 
 static int eldef_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    auto& d = h->eldef;
-    GPF_TRY(series_free({(void**)&d.rec, (void**)&d.cell, (void**)&d.part, (void**)&d.row_val, (void**)&d.row_iy}));
-    d.every = 0; d.pending = false;
-    d.host.clear(); d.cells.clear(); d.steps.clear();
+    GPF_TRY(series_free(eldef_owned(h)));
+    h->eldef.disarm();
     return GPF_OK;
 }
 
 extern "C" int gpf_elastic_series_set(gpf_handle* h, int64_t every) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(eldef_refusal(h, "gpf_elastic_series_set"));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_elastic_series_set: every >= 1 required (gpf_elastic_series_clear disarms), got " + std::to_string(every));
-    GPF_TRY(enter(h, true));
-    GPF_TRY(eldef_release(h));
+    GPF_TRY(series_set_checks(h, SERIES[S_ELDEF], every, eldef_refusal));
+    GPF_TRY(series_disarm(h, SERIES[S_ELDEF]));
     h->eldef.every = every;
     return GPF_OK;
 }
 
-extern "C" int gpf_elastic_series_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_elastic_series_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return eldef_release(h);
-}
+extern "C" int gpf_elastic_series_clear(gpf_handle* h) { return series_clear(h, SERIES[S_ELDEF]); }
 
 extern "C" int gpf_elastic_series_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (!h->eldef.every) return fail(GPF_ERR_STATE, "gpf_elastic_series_read: the deformation series is not armed (gpf_elastic_series_set)");
+    if (!h->eldef.armed()) return fail(GPF_ERR_STATE, "gpf_elastic_series_read: the deformation series is not armed (gpf_elastic_series_set)");
     series_read(h->eldef.steps, capacity_records, steps_out, n_records, series_channel(h->eldef.host, values, (size_t)ELDEF_NREC),
                 series_channel(h->eldef.cells, cells, (size_t)2 * ELDEF_NEXT));
     return GPF_OK;
 }
 
 extern "C" int gpf_elastic_series_now(gpf_handle* h, double values[6], int32_t cells[4]) {
-    if (!h || !values || !cells) return fail(GPF_ERR_INVALID, "gpf_elastic_series_now: null argument");
-    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_elastic_series_now: upload q and topography first");
-    GPF_TRY(eldef_refusal(h, "gpf_elastic_series_now"));
+    GPF_TRY(series_now_checks(h, SERIES[S_ELDEF], values && cells, eldef_refusal));
     GPF_TRY(enter(h, true));
     GPF_TRY(eldef_buffers(h));
     StepState s;
-    GPF_TRY(read_state(h, s));
-    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_elastic_series_now: the run state is flagged invalid (the last step was rolled back)");
+    GPF_TRY(series_now_state(h, SERIES[S_ELDEF], s));
     GPF_TRY(eldef_enqueue(h, s.step, h->log_cap));              // the slot behind a batch's
     HIP_TRY(hipMemcpyAsync(values, h->eldef.rec + (size_t)h->log_cap * ELDEF_NREC, ELDEF_NREC * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(cells, h->eldef.cell + (size_t)h->log_cap * 2 * ELDEF_NEXT, 2 * ELDEF_NEXT * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -142,12 +116,7 @@ extern "C" int gpf_elastic_series_now(gpf_handle* h, double values[6], int32_t c
 // recording at the armed stride; *ms = first launch to last on the handle's stream, the host's share of such steps included
 // (series_time).
 extern "C" int gpf_elastic_series_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_elastic_series_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_elastic_series_time: call gpf_pre_run first");
-    GPF_TRY(eldef_refusal(h, "gpf_elastic_series_time"));
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
-        return fail(GPF_ERR_INVALID, "gpf_elastic_series_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
-    if (mode == 1 && !h->eldef.every) return fail(GPF_ERR_STATE, "gpf_elastic_series_time: mode 1 needs the armed series (gpf_elastic_series_set)");
+    GPF_TRY(series_time_checks(h, SERIES[S_ELDEF], n, mode, 1, ms, "the armed series (gpf_elastic_series_set)", eldef_refusal));
     GPF_TRY(enter(h));
     SeriesAside aside(h, mode == 1 ? &h->eldef.every : nullptr);
     std::vector<double> host;

@@ -44,9 +44,9 @@ static int extrema_buffers(gpf_handle* h) {
 // A stepping call begins: its records replace those of the call before
 static int extrema_begin(gpf_handle* h) {
     h->extr.pending = false;
-    if (!h->extr.every) return GPF_OK;
+    if (!h->extr.armed()) return GPF_OK;
     GPF_TRY(extrema_refusal(h, "a stepping call with extrema armed"));
-    h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
+    h->extr.forget();
     return extrema_buffers(h);
 }
 
@@ -77,75 +77,42 @@ static int extrema_collect(gpf_handle* h, long long base, long long ran) {
                           series_channel(h->extr.cells, h->extr.a.cell, (size_t)2 * EXTREMA_NQ));
 }
 
-// gpf_close_step: the closed step's record, if it commits.  An elastic handle's gap deforms after the step closes
-// (gpf_elastic_update); its record waits for that call, so that it holds the gap the handle holds with that state.
-static int extrema_close_step_launch(gpf_handle* h) {
-    GPF_TRY(extrema_begin(h));
-    if (!h->extr.every) return GPF_OK;
-    if (h->el.on) { h->extr.pending = true; h->extr.pending_base = h->host_step; return GPF_OK; }
-    return extrema_launch(h, h->host_step + 1, h->host_step);
-}
-
-static int extrema_close_step_collect(gpf_handle* h, long long ran) {
-    if (h->extr.pending) { if (ran < 1) h->extr.pending = false; return GPF_OK; }
-    return extrema_collect(h, h->host_step, ran);
-}
-
-// gpf_elastic_update, behind its launches: the record of the step gpf_close_step committed just before
-static int extrema_after_elastic_update(gpf_handle* h) {
-    if (!h->extr.pending) return GPF_OK;
-    h->extr.pending = false;
-    const long long base = h->extr.pending_base;
-    if (!h->extr.every || h->host_step != base + 1) return GPF_OK;
-    GPF_TRY(extrema_launch(h, h->host_step, base));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return extrema_collect(h, base, 1);
+static SeriesBuffers extrema_owned(gpf_handle* h) {
+    ExtremaArgs& a = h->extr.a;
+    return {(void**)&a.val, (void**)&a.cell, (void**)&a.row_val, (void**)&a.row_iy, (void**)&h->extr.dev};
 }
 
 static int extrema_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    ExtremaArgs& a = h->extr.a;
-    GPF_TRY(series_free({(void**)&a.val, (void**)&a.cell, (void**)&a.row_val, (void**)&a.row_iy, (void**)&h->extr.dev}));
-    a.every = 0; a.cap = 0;
-    h->extr.every = 0; h->extr.pending = false;
-    h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
+    GPF_TRY(series_free(extrema_owned(h)));
+    h->extr.a.every = 0; h->extr.a.cap = 0;
+    h->extr.disarm();
     return GPF_OK;
 }
 
 extern "C" int gpf_extrema_set(gpf_handle* h, int64_t every) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(extrema_refusal(h, "gpf_extrema_set"));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_extrema_set: every >= 1 required (gpf_extrema_clear disarms), got " + std::to_string(every));
-    GPF_TRY(enter(h, true));
-    GPF_TRY(extrema_release(h));
+    GPF_TRY(series_set_checks(h, SERIES[S_EXTREMA], every, extrema_refusal));
+    GPF_TRY(series_disarm(h, SERIES[S_EXTREMA]));
     h->extr.every = every;
     return GPF_OK;
 }
 
-extern "C" int gpf_extrema_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_extrema_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return extrema_release(h);
-}
+extern "C" int gpf_extrema_clear(gpf_handle* h) { return series_clear(h, SERIES[S_EXTREMA]); }
 
 extern "C" int gpf_extrema_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (!h->extr.every) return fail(GPF_ERR_STATE, "gpf_extrema_read: no extrema are armed (gpf_extrema_set)");
+    if (!h->extr.armed()) return fail(GPF_ERR_STATE, "gpf_extrema_read: no extrema are armed (gpf_extrema_set)");
     series_read(h->extr.steps, capacity_records, steps_out, n_records, series_channel(h->extr.host, values, (size_t)EXTREMA_NQ),
                 series_channel(h->extr.cells, cells, (size_t)2 * EXTREMA_NQ));
     return GPF_OK;
 }
 
 extern "C" int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14]) {
-    if (!h || !values || !cells) return fail(GPF_ERR_INVALID, "gpf_extrema_now: null argument");
-    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_extrema_now: upload q and topography first");
-    GPF_TRY(extrema_refusal(h, "gpf_extrema_now"));
+    GPF_TRY(series_now_checks(h, SERIES[S_EXTREMA], values && cells, extrema_refusal));
     GPF_TRY(enter(h, true));
     GPF_TRY(extrema_buffers(h));
     StepState s;
-    GPF_TRY(read_state(h, s));
-    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_extrema_now: the run state is flagged invalid (the last step was rolled back)");
+    GPF_TRY(series_now_state(h, SERIES[S_EXTREMA], s));
     GPF_TRY(extrema_enqueue(h, s.step, h->log_cap));            // the slot behind a batch's
     HIP_TRY(hipMemcpyAsync(values, h->extr.a.val + (size_t)h->log_cap * EXTREMA_NQ, EXTREMA_NQ * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(cells, h->extr.a.cell + (size_t)h->log_cap * 2 * EXTREMA_NQ, 2 * EXTREMA_NQ * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -156,18 +123,11 @@ extern "C" int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14
 // Diagnostic (tools/extrema_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed extrema are put aside
 // for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_extrema_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_extrema_time: call gpf_pre_run first");
-    GPF_TRY(extrema_refusal(h, "gpf_extrema_time"));
-    if (h->cfg.thinning != GPF_THINNING_NONE || h->el.on || h->gp[1].set || h->gp[2].set)
-        return fail(GPF_ERR_STATE, "gpf_extrema_time: handles that gpf_step advances only (this one steps stage-wise)");
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
-        return fail(GPF_ERR_INVALID, "gpf_extrema_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
-    if (mode == 1 && !h->extr.every) return fail(GPF_ERR_STATE, "gpf_extrema_time: mode 1 needs armed extrema (gpf_extrema_set)");
-    GPF_TRY(enter(h));
-    GPF_TRY(extrema_begin(h));          // (buffers and the device copy of the arguments while the stride is still the armed one)
-    SeriesAside aside(h, mode == 1 ? &h->extr.every : nullptr);
-    return series_time(h, "gpf_extrema_time", aside,
-                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return extrema_launch(h, expect, base); }); },
-                       [&](long long base, long long ran) { return extrema_collect(h, base, ran); }, ms);
+    GPF_TRY(series_time_checks(h, SERIES[S_EXTREMA], n, mode, 1, ms, "armed extrema (gpf_extrema_set)", [](const gpf_handle* h, const std::string& who) {
+        GPF_TRY(extrema_refusal(h, who));
+        if (h->cfg.thinning != GPF_THINNING_NONE || h->el.on || h->gp[1].set || h->gp[2].set)
+            return fail(GPF_ERR_STATE, who + ": handles that gpf_step advances only (this one steps stage-wise)");
+        return (int)GPF_OK;
+    }));
+    return series_time_fused(h, SERIES[S_EXTREMA], n, mode, ms);
 }

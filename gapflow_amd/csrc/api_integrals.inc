@@ -7,8 +7,9 @@
 static int integrals_nrec(const gpf_handle* h) { return FILM_NSUM + h->integ.nsx + h->integ.nsy; }
 
 // The cases the reduction does not cover: series_refusal's, with its classes and texts, except the elastic gap of one handle
-// (el.on).  Its gap is h->topo, the planes the kernels read anyway; only the moment of the record differs
-// (integrals_close_step_launch).  An elastic slab is refused as a slab.
+// (el.on).  Its gap is h->topo, the planes the kernels read anyway; only the moment of the record differs: it waits for
+// gpf_elastic_update (SERIES_BEHIND_UPDATE), and other handles' closed steps leave no film-integral record.  An elastic slab is
+// refused as a slab.
 static int integrals_refusal(const gpf_handle* h, const std::string& who) { return series_refusal(h, who, "film integrals", "the film integrals", true); }
 
 // First and last interior row / column; a direction of extent 1 has the one section
@@ -52,9 +53,9 @@ static int integrals_buffers(gpf_handle* h) {
 // A stepping call begins: its records replace those of the call before
 static int integrals_begin(gpf_handle* h) {
     h->integ.pending = false;
-    if (!h->integ.every) return GPF_OK;
+    if (!h->integ.armed()) return GPF_OK;
     GPF_TRY(integrals_refusal(h, "gpf_step with film integrals armed"));
-    h->integ.host.clear(); h->integ.steps.clear();
+    h->integ.forget();
     return integrals_buffers(h);
 }
 
@@ -82,46 +83,17 @@ static int integrals_collect(gpf_handle* h, long long base, long long ran) {
     return series_collect(h->integ.every, h->integ.steps, base, ran, series_channel(h->integ.host, h->integ.rec, (size_t)integrals_nrec(h)));
 }
 
-// gpf_close_step of an elastic handle (el.on): its gap deforms after the step closes (gpf_elastic_update), so the closed step's
-// record waits for that call, as the extrema's does (extrema_close_step_launch), and holds the gap the handle holds with that
-// state.  Other handles' closed steps leave no film-integral record, as before.
-static int integrals_close_step_launch(gpf_handle* h) {
-    h->integ.pending = false;
-    if (!h->integ.every || !h->el.on) return GPF_OK;
-    GPF_TRY(integrals_begin(h));
-    h->integ.pending = true; h->integ.pending_base = h->host_step;
-    return GPF_OK;
-}
-
-// ... the step did not commit: nothing to wait for
-static void integrals_close_step_collect(gpf_handle* h, long long ran) {
-    if (ran < 1) h->integ.pending = false;
-}
-
-// gpf_elastic_update, behind its launches: the record of the step gpf_close_step committed just before, at the armed stride
-static int integrals_after_elastic_update(gpf_handle* h) {
-    if (!h->integ.pending) return GPF_OK;
-    h->integ.pending = false;
-    const long long base = h->integ.pending_base;
-    if (!h->integ.every || h->host_step != base + 1) return GPF_OK;
-    if (!series_due(h->integ.every, h->host_step)) return GPF_OK;
-    GPF_TRY(integrals_launch(h, h->host_step, base));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return integrals_collect(h, base, 1);
-}
+static SeriesBuffers integrals_owned(gpf_handle* h) { return {(void**)&h->integ.rec, (void**)&h->integ.part, (void**)&h->integ.dev}; }
 
 static int integrals_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    GPF_TRY(series_free({(void**)&h->integ.rec, (void**)&h->integ.part, (void**)&h->integ.dev}));
-    h->integ.every = 0; h->integ.nsx = h->integ.nsy = 0; h->integ.pending = false;
-    h->integ.host.clear(); h->integ.steps.clear();
+    GPF_TRY(series_free(integrals_owned(h)));
+    h->integ.disarm(); h->integ.nsx = h->integ.nsy = 0;
     return GPF_OK;
 }
 
 extern "C" int gpf_integrals_set(gpf_handle* h, int64_t every, int nsx, const int32_t* ix, int nsy, const int32_t* iy) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(integrals_refusal(h, "gpf_integrals_set"));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_integrals_set: every >= 1 required (gpf_integrals_clear disarms), got " + std::to_string(every));
+    GPF_TRY(series_set_checks(h, SERIES[S_INTEGRALS], every, integrals_refusal));
     if (nsx > FILM_MAX_SECTIONS || nsy > FILM_MAX_SECTIONS)
         return fail(GPF_ERR_INVALID, "gpf_integrals_set: section " + std::to_string(FILM_MAX_SECTIONS) + " is one too many (" +
                                      std::to_string(std::max(nsx, nsy)) + " given, at most " + std::to_string(FILM_MAX_SECTIONS) + " per direction)");
@@ -133,8 +105,7 @@ extern "C" int gpf_integrals_set(gpf_handle* h, int64_t every, int nsx, const in
         if (iy[k] < 1 || iy[k] > h->L.Ny)
             return fail(GPF_ERR_INVALID, "gpf_integrals_set: y-section " + std::to_string(k) + " at column " + std::to_string(iy[k]) +
                                          " lies outside the interior columns 1.." + std::to_string(h->L.Ny));
-    GPF_TRY(enter(h, true));
-    GPF_TRY(integrals_release(h));
+    GPF_TRY(series_disarm(h, SERIES[S_INTEGRALS]));
     integrals_default_sections(h);
     if (ix && nsx > 0) { h->integ.nsx = nsx; for (int k = 0; k < nsx; ++k) h->integ.sx[k] = ix[k]; }
     if (iy && nsy > 0) { h->integ.nsy = nsy; for (int k = 0; k < nsy; ++k) h->integ.sy[k] = iy[k]; }
@@ -142,37 +113,29 @@ extern "C" int gpf_integrals_set(gpf_handle* h, int64_t every, int nsx, const in
     return GPF_OK;
 }
 
-extern "C" int gpf_integrals_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_integrals_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return integrals_release(h);
-}
+extern "C" int gpf_integrals_clear(gpf_handle* h) { return series_clear(h, SERIES[S_INTEGRALS]); }
 
 extern "C" int gpf_integrals_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (!h->integ.every) return fail(GPF_ERR_STATE, "gpf_integrals_read: no integrals are armed (gpf_integrals_set)");
+    if (!h->integ.armed()) return fail(GPF_ERR_STATE, "gpf_integrals_read: no integrals are armed (gpf_integrals_set)");
     series_read(h->integ.steps, capacity_records, steps_out, n_records, series_channel(h->integ.host, out, (size_t)integrals_nrec(h)));
     return GPF_OK;
 }
 
 extern "C" int gpf_integrals_in_batch(gpf_handle* h, int* yes) {
     if (!h || !yes) return fail(GPF_ERR_INVALID, "gpf_integrals_in_batch: null argument");
-    *yes = h->integ.every && small_grid_eligible(h) ? 1 : 0;
+    *yes = h->integ.armed() && small_grid_eligible(h) ? 1 : 0;
     return GPF_OK;
 }
 
 extern "C" int gpf_integrals_now(gpf_handle* h, double* out, int64_t count) {
-    if (!h || !out) return fail(GPF_ERR_INVALID, "gpf_integrals_now: null argument");
-    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_integrals_now: upload q and topography first");
-    GPF_TRY(integrals_refusal(h, "gpf_integrals_now"));
+    GPF_TRY(series_now_checks(h, SERIES[S_INTEGRALS], out != nullptr, integrals_refusal));
     GPF_TRY(enter(h, true));
     GPF_TRY(integrals_buffers(h));
     const int nrec = integrals_nrec(h);
     if (count < nrec) return fail(GPF_ERR_INVALID, "gpf_integrals_now: room for " + std::to_string(nrec) + " doubles required, " + std::to_string(count) + " given");
     StepState s;
-    GPF_TRY(read_state(h, s));
-    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_integrals_now: the run state is flagged invalid (the last step was rolled back)");
+    GPF_TRY(series_now_state(h, SERIES[S_INTEGRALS], s));
     GPF_TRY(integrals_enqueue(h, s.step, h->log_cap));          // the slot behind a batch's
     HIP_TRY(hipMemcpyAsync(out, h->integ.rec + (size_t)h->log_cap * nrec, (size_t)nrec * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -182,15 +145,10 @@ extern "C" int gpf_integrals_now(gpf_handle* h, double* out, int64_t count) {
 // Diagnostic (tools/integrals_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed integrals are put
 // aside for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_integrals_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_integrals_time: call gpf_pre_run first");
-    GPF_TRY(integrals_refusal(h, "gpf_integrals_time"));
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
-        return fail(GPF_ERR_INVALID, "gpf_integrals_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
-    if (mode == 1 && !h->integ.every) return fail(GPF_ERR_STATE, "gpf_integrals_time: mode 1 needs armed integrals (gpf_integrals_set)");
-    GPF_TRY(enter(h));
-    SeriesAside aside(h, mode == 1 ? &h->integ.every : nullptr);
+    GPF_TRY(series_time_checks(h, SERIES[S_INTEGRALS], n, mode, 1, ms, "armed integrals (gpf_integrals_set)", integrals_refusal));
     if (h->el.on) {         // an elastic handle: n stage-wise steps, each with its gpf_elastic_update and the record behind it
+        GPF_TRY(enter(h));
+        SeriesAside aside(h, mode == 1 ? &h->integ.every : nullptr);
         std::vector<double> host;
         std::vector<long long> steps;
         const int rc = series_time(h, "gpf_integrals_time", aside,
@@ -199,8 +157,5 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
         prev_state_lost(h, PREV_LOST_STAGEWISE);    // (series_resync speaks of fused steps: a closed step leaves its working field in the other buffer)
         return rc;
     }
-    GPF_TRY(integrals_begin(h));
-    return series_time(h, "gpf_integrals_time", aside,
-                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return integrals_launch(h, expect, base); }); },
-                       [&](long long base, long long ran) { return integrals_collect(h, base, ran); }, ms);
+    return series_time_fused(h, SERIES[S_INTEGRALS], n, mode, ms);
 }

@@ -33,9 +33,9 @@ static int lines_parse(const gpf_handle* h, const std::string& who, int K, const
 
 // A stepping call begins: its records replace those of the call before
 static int lines_begin(gpf_handle* h) {
-    if (!h->lines.every) return GPF_OK;
+    if (!h->lines.armed()) return GPF_OK;
     GPF_TRY(lines_refusal(h, "gpf_step with lines armed"));
-    h->lines.host.clear(); h->lines.steps.clear();
+    h->lines.forget();
     return GPF_OK;
 }
 
@@ -91,7 +91,7 @@ static int lines_enqueue(gpf_handle* h, long long expect, long long slot) {
 // The longest batch a stepping call may enqueue from step count `base`: with lines armed, no more steps than leave `capacity`
 // records (lines.hpp: lines_batch_limit); unchanged without
 static long long lines_batch(const gpf_handle* h, long long batch, long long base) {
-    if (!h->lines.every) return batch;
+    if (!h->lines.armed()) return batch;
     return std::min(batch, lines_batch_limit(base, h->lines.every, h->lines.capacity));
 }
 
@@ -110,18 +110,17 @@ static int lines_collect(gpf_handle* h, long long base, long long ran) {
     return series_collect(h->lines.every, h->lines.steps, base, ran, series_channel(h->lines.host, h->lines.rec, (size_t)h->lines.rec_doubles));
 }
 
+static SeriesBuffers lines_owned(gpf_handle* h) { return {(void**)&h->lines.rec, (void**)&h->lines.scratch}; }
+
 static int lines_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    GPF_TRY(series_free({(void**)&h->lines.rec, (void**)&h->lines.scratch}));
-    h->lines.every = 0; h->lines.K = 0; h->lines.capacity = 0; h->lines.rec_doubles = 0;
-    h->lines.host.clear(); h->lines.steps.clear();
+    GPF_TRY(series_free(lines_owned(h)));
+    h->lines.disarm(); h->lines.K = 0; h->lines.capacity = 0; h->lines.rec_doubles = 0;
     return GPF_OK;
 }
 
 extern "C" int gpf_lines_set(gpf_handle* h, int64_t every, int K, const gpf_line* lines, int64_t capacity) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(lines_refusal(h, "gpf_lines_set"));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_lines_set: every >= 1 required (gpf_lines_clear disarms), got " + std::to_string(every));
+    GPF_TRY(series_set_checks(h, SERIES[S_LINES], every, lines_refusal));
     if (capacity < 0) return fail(GPF_ERR_INVALID, "gpf_lines_set: capacity >= 1 required (0: the default), got " + std::to_string(capacity));
     Line defs[LINE_MAX_K];
     long long rec_doubles = 0, scratch_doubles = 0;
@@ -130,8 +129,7 @@ extern "C" int gpf_lines_set(gpf_handle* h, int64_t every, int K, const gpf_line
     if (const char* s = std::getenv("GPF_LINES_MB")) mb = std::max<long long>(1, std::atoll(s));
     const long long most = (h->log_cap + every - 1) / every;        // what the longest batch can leave: more is never used
     const long long cap = capacity ? std::min<long long>(capacity, most) : lines_default_capacity(mb << 20, rec_doubles, h->log_cap, every);
-    GPF_TRY(enter(h, true));
-    GPF_TRY(lines_release(h));
+    GPF_TRY(series_disarm(h, SERIES[S_LINES]));
     hipError_t e = hipMalloc(&h->lines.rec, (size_t)(cap + 1) * rec_doubles * sizeof(double));       // + the slot of gpf_lines_now
     if (e == hipSuccess && scratch_doubles) e = hipMalloc(&h->lines.scratch, (size_t)scratch_doubles * sizeof(double));
     if (e != hipSuccess) {
@@ -144,34 +142,26 @@ extern "C" int gpf_lines_set(gpf_handle* h, int64_t every, int K, const gpf_line
     return GPF_OK;
 }
 
-extern "C" int gpf_lines_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_lines_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return lines_release(h);
-}
+extern "C" int gpf_lines_clear(gpf_handle* h) { return series_clear(h, SERIES[S_LINES]); }
 
 extern "C" int gpf_lines_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (!h->lines.every) return fail(GPF_ERR_STATE, "gpf_lines_read: no lines are armed (gpf_lines_set)");
+    if (!h->lines.armed()) return fail(GPF_ERR_STATE, "gpf_lines_read: no lines are armed (gpf_lines_set)");
     series_read(h->lines.steps, capacity_records, steps_out, n_records, series_channel(h->lines.host, out, (size_t)h->lines.rec_doubles));
     return GPF_OK;
 }
 
 extern "C" int gpf_lines_now(gpf_handle* h, int K, const gpf_line* lines, double* out, int64_t count) {
-    if (!h || !out) return fail(GPF_ERR_INVALID, "gpf_lines_now: null argument");
-    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_lines_now: upload q and topography first");
-    GPF_TRY(lines_refusal(h, "gpf_lines_now"));
+    GPF_TRY(series_now_checks(h, SERIES[S_LINES], out != nullptr, lines_refusal));
     const bool armed = K == 0 && !lines;            // the armed lines, into the slot behind a batch's
-    if (armed && !h->lines.every) return fail(GPF_ERR_STATE, "gpf_lines_now: no lines are armed (gpf_lines_set), and none are given");
+    if (armed && !h->lines.armed()) return fail(GPF_ERR_STATE, "gpf_lines_now: no lines are armed (gpf_lines_set), and none are given");
     Line defs[LINE_MAX_K];
     long long rec_doubles = h->lines.rec_doubles, scratch_doubles = 0;
     if (!armed) GPF_TRY(lines_parse(h, "gpf_lines_now", K, lines, defs, &rec_doubles, &scratch_doubles));
     if (count < rec_doubles) return fail(GPF_ERR_INVALID, "gpf_lines_now: room for " + std::to_string(rec_doubles) + " doubles required, " + std::to_string(count) + " given");
     GPF_TRY(enter(h, true));
     StepState s;
-    GPF_TRY(read_state(h, s));
-    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_lines_now: the run state is flagged invalid (the last step was rolled back)");
+    GPF_TRY(series_now_state(h, SERIES[S_LINES], s));
     if (armed) {
         GPF_TRY(lines_enqueue(h, s.step, h->lines.capacity));
         HIP_TRY(hipMemcpyAsync(out, h->lines.rec + (size_t)h->lines.capacity * rec_doubles, (size_t)rec_doubles * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -197,19 +187,9 @@ extern "C" int gpf_lines_now(gpf_handle* h, int K, const gpf_line* lines, double
 // call), 1 recording at the armed stride (n at most what one batch may hold: lines_batch); *ms = first launch to last on the
 // handle's stream (series_time).
 extern "C" int gpf_lines_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_lines_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_lines_time: call gpf_pre_run first");
-    GPF_TRY(lines_refusal(h, "gpf_lines_time"));
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
-        return fail(GPF_ERR_INVALID, "gpf_lines_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
-    if (mode == 1 && !h->lines.every) return fail(GPF_ERR_STATE, "gpf_lines_time: mode 1 needs armed lines (gpf_lines_set)");
+    GPF_TRY(series_time_checks(h, SERIES[S_LINES], n, mode, 1, ms, "armed lines (gpf_lines_set)", lines_refusal));
     if (mode == 1 && n > lines_batch(h, n, h->host_step))
         return fail(GPF_ERR_INVALID, "gpf_lines_time: " + std::to_string(n) + " steps leave more records than the buffer holds (" + std::to_string(h->lines.capacity) +
                                      " at stride " + std::to_string(h->lines.every) + ")");
-    GPF_TRY(enter(h));
-    SeriesAside aside(h, mode == 1 ? &h->lines.every : nullptr);
-    GPF_TRY(lines_begin(h));
-    return series_time(h, "gpf_lines_time", aside,
-                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return lines_launch(h, expect, base); }); },
-                       [&](long long base, long long ran) { return lines_collect(h, base, ran); }, ms);
+    return series_time_fused(h, SERIES[S_LINES], n, mode, ms);
 }

@@ -44,7 +44,7 @@ static int probes_launch(gpf_handle* h, long long expect, long long base) {
 }
 
 // After the batch's state has been read (the stream is idle): the records of its `ran` committed steps -> host
-static int probes_collect(gpf_handle* h, long long ran) {
+static int probes_collect(gpf_handle* h, long long, long long ran) {
     if (!h->probes.n || ran <= 0) return GPF_OK;
     const size_t add = (size_t)ran * h->probes.n * h->probes.nv, at = h->probes.host.size();
     h->probes.host.resize(at + add);
@@ -52,9 +52,11 @@ static int probes_collect(gpf_handle* h, long long ran) {
     return GPF_OK;
 }
 
+static SeriesBuffers probes_owned(gpf_handle* h) { return {(void**)&h->probes.cells, (void**)&h->probes.buf, (void**)&h->probes.dev}; }
+
 static int probes_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    GPF_TRY(series_free({(void**)&h->probes.cells, (void**)&h->probes.buf, (void**)&h->probes.dev}));
+    GPF_TRY(series_free(probes_owned(h)));
     h->probes.n = 0; h->probes.nv = 0;
     h->probes.host.clear(); h->probes.first_step = 0;
     return GPF_OK;
@@ -78,20 +80,14 @@ extern "C" int gpf_probes_set(gpf_handle* h, int n, const int32_t* ix, const int
     }
     if (with_pressure && h->gp[0].set)
         return fail(GPF_ERR_INVALID, "gpf_probes_set: probe 0: no EOS pressure to record, this handle's pressure comes from a surrogate");
-    GPF_TRY(enter(h, true));
-    GPF_TRY(probes_release(h));
+    GPF_TRY(series_disarm(h, SERIES[S_PROBES]));
     HIP_TRY(hipMalloc(&h->probes.cells, cells.size() * sizeof(int)));
     HIP_TRY(hipMemcpy(h->probes.cells, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice));
     h->probes.n = n; h->probes.nv = with_pressure ? 4 : 3;
     return GPF_OK;
 }
 
-extern "C" int gpf_probes_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_probes_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return probes_release(h);
-}
+extern "C" int gpf_probes_clear(gpf_handle* h) { return series_clear(h, SERIES[S_PROBES]); }
 
 extern "C" int gpf_probes_read(gpf_handle* h, double* out, int64_t capacity_steps, int64_t* first_step, int64_t* n_steps) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
@@ -109,12 +105,10 @@ extern "C" int gpf_probes_read(gpf_handle* h, double* out, int64_t capacity_step
 // be set), 2 an empty kernel behind every step; *ms = first launch to last on the handle's stream.  Small grids take
 // k_small_steps, where mode 2 has no meaning and is refused.
 extern "C" int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_probes_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_probes_time: call gpf_pre_run first");
-    if (h->E.halo[0] || h->E.halo[1] || h->cfg.thinning != GPF_THINNING_NONE) return fail(GPF_ERR_STATE, "gpf_probes_time: fused, unsliced handles only");
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 2)
-        return fail(GPF_ERR_INVALID, "gpf_probes_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..2 required");
-    if (mode == 1 && !h->probes.n) return fail(GPF_ERR_STATE, "gpf_probes_time: mode 1 needs probes (gpf_probes_set)");
+    GPF_TRY(series_time_checks(h, SERIES[S_PROBES], n, mode, 2, ms, "probes (gpf_probes_set)", [](const gpf_handle* h, const std::string& who) {
+        if (h->E.halo[0] || h->E.halo[1] || h->cfg.thinning != GPF_THINNING_NONE) return fail(GPF_ERR_STATE, who + ": fused, unsliced handles only");
+        return (int)GPF_OK;
+    }));
     if (small_grid_eligible(h) && mode == 2) return fail(GPF_ERR_INVALID, "gpf_probes_time: the small-grid kernel has no launch per step to stand in for");
     GPF_TRY(enter(h));
     // mode 0 and 2 must not record: the probes are put aside for the call
@@ -127,5 +121,5 @@ extern "C" int gpf_probes_time(gpf_handle* h, int64_t n, int mode, double* ms) {
                                return probes_launch(h, expect, base);
                            });
                        },
-                       [&](long long, long long ran) { return probes_collect(h, ran); }, ms);
+                       [&](long long base, long long ran) { return probes_collect(h, base, ran); }, ms);
 }

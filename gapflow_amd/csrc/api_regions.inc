@@ -15,9 +15,9 @@ static bool regions_wide_ok(const gpf_handle* h) { return series_wide_ok(h, h->r
 
 // A stepping call begins: its records replace those of the call before
 static int regions_begin(gpf_handle* h) {
-    if (!h->regions.every) return GPF_OK;
+    if (!h->regions.armed()) return GPF_OK;
     GPF_TRY(regions_refusal(h, "gpf_step with regions armed"));
-    h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
+    h->regions.forget();
     return GPF_OK;
 }
 
@@ -42,22 +42,23 @@ static int regions_launch(gpf_handle* h, long long expect, long long base) {
 // After the batch's state has been read (the stream is idle): the records of its `ran` committed steps -> host
 static int regions_collect(gpf_handle* h, long long base, long long ran) {
     return series_collect(h->regions.every, h->regions.steps, base, ran, series_channel(h->regions.host, h->regions.rec, regions_nsum(h)),
-                          series_channel(h->regions.ihost, h->regions.irec, regions_nint(h)));
+                          series_channel(h->regions.ints, h->regions.irec, regions_nint(h)));
+}
+
+static SeriesBuffers regions_owned(gpf_handle* h) {
+    return {(void**)&h->regions.defs, (void**)&h->regions.part, (void**)&h->regions.ipart, (void**)&h->regions.rec, (void**)&h->regions.irec};
 }
 
 static int regions_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    GPF_TRY(series_free({(void**)&h->regions.defs, (void**)&h->regions.part, (void**)&h->regions.ipart, (void**)&h->regions.rec, (void**)&h->regions.irec}));
-    h->regions.every = 0; h->regions.K = 0;
-    h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
+    GPF_TRY(series_free(regions_owned(h)));
+    h->regions.disarm(); h->regions.K = 0;
     return GPF_OK;
 }
 
 extern "C" int gpf_regions_set(gpf_handle* h, int64_t every, int K, const gpf_region* regions) {
     static const char* const field_names = "0 (p), 1 (rho), 2 (h), 3 (jx), 4 (jy)";
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(regions_refusal(h, "gpf_regions_set"));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_regions_set: every >= 1 required (gpf_regions_clear disarms), got " + std::to_string(every));
+    GPF_TRY(series_set_checks(h, SERIES[S_REGIONS], every, regions_refusal));
     if (K < 1 || K > REGION_MAX_K)
         return fail(GPF_ERR_INVALID, "gpf_regions_set: 1 to " + std::to_string(REGION_MAX_K) + " regions required, got " + std::to_string(K));
     if (!regions) return fail(GPF_ERR_INVALID, "gpf_regions_set: null regions");
@@ -80,8 +81,7 @@ extern "C" int gpf_regions_set(gpf_handle* h, int64_t every, int K, const gpf_re
                                                   std::to_string(L.Ny) + " (inclusive interior indices; all zeros: the whole interior)");
         }
     }
-    GPF_TRY(enter(h, true));
-    GPF_TRY(regions_release(h));
+    GPF_TRY(series_disarm(h, SERIES[S_REGIONS]));
     auto undo = [&](int code) { (void)regions_release(h); return code; };
 #define HIP_TRY_R(expr)                                                                                 \
     do {                                                                                                \
@@ -103,31 +103,23 @@ extern "C" int gpf_regions_set(gpf_handle* h, int64_t every, int K, const gpf_re
     return GPF_OK;
 }
 
-extern "C" int gpf_regions_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_regions_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return regions_release(h);
-}
+extern "C" int gpf_regions_clear(gpf_handle* h) { return series_clear(h, SERIES[S_REGIONS]); }
 
 extern "C" int gpf_regions_read(gpf_handle* h, double* sums, int64_t* ints, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (!h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_read: no regions are armed (gpf_regions_set)");
+    if (!h->regions.armed()) return fail(GPF_ERR_STATE, "gpf_regions_read: no regions are armed (gpf_regions_set)");
     series_read(h->regions.steps, capacity_records, steps_out, n_records, series_channel(h->regions.host, sums, regions_nsum(h)),
-                series_channel(h->regions.ihost, (long long*)ints, regions_nint(h)));
+                series_channel(h->regions.ints, (long long*)ints, regions_nint(h)));
     return GPF_OK;
 }
 
 extern "C" int gpf_regions_now(gpf_handle* h, double* sums, int64_t* ints, int64_t count) {
-    if (!h || !sums || !ints) return fail(GPF_ERR_INVALID, "gpf_regions_now: null argument");
-    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_regions_now: upload q and topography first");
-    GPF_TRY(regions_refusal(h, "gpf_regions_now"));
-    if (!h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_now: no regions are armed (gpf_regions_set holds the region list)");
+    GPF_TRY(series_now_checks(h, SERIES[S_REGIONS], sums && ints, regions_refusal));
+    if (!h->regions.armed()) return fail(GPF_ERR_STATE, "gpf_regions_now: no regions are armed (gpf_regions_set holds the region list)");
     GPF_TRY(enter(h, true));
     if (count < h->regions.K) return fail(GPF_ERR_INVALID, "gpf_regions_now: room for " + std::to_string(h->regions.K) + " regions required, " + std::to_string(count) + " given");
     StepState s;
-    GPF_TRY(read_state(h, s));
-    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_regions_now: the run state is flagged invalid (the last step was rolled back)");
+    GPF_TRY(series_now_state(h, SERIES[S_REGIONS], s));
     const size_t ns = regions_nsum(h), ni = regions_nint(h);
     GPF_TRY(regions_enqueue(h, s.step, h->log_cap));            // the slot behind a batch's
     HIP_TRY(hipMemcpyAsync(sums, h->regions.rec + (size_t)h->log_cap * ns, ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -139,16 +131,6 @@ extern "C" int gpf_regions_now(gpf_handle* h, double* sums, int64_t* ints, int64
 // Diagnostic (tools/regions_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed regions are put aside for
 // the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_regions_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_regions_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_regions_time: call gpf_pre_run first");
-    GPF_TRY(regions_refusal(h, "gpf_regions_time"));
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
-        return fail(GPF_ERR_INVALID, "gpf_regions_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
-    if (mode == 1 && !h->regions.every) return fail(GPF_ERR_STATE, "gpf_regions_time: mode 1 needs armed regions (gpf_regions_set)");
-    GPF_TRY(enter(h));
-    SeriesAside aside(h, mode == 1 ? &h->regions.every : nullptr);
-    GPF_TRY(regions_begin(h));
-    return series_time(h, "gpf_regions_time", aside,
-                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return regions_launch(h, expect, base); }); },
-                       [&](long long base, long long ran) { return regions_collect(h, base, ran); }, ms);
+    GPF_TRY(series_time_checks(h, SERIES[S_REGIONS], n, mode, 1, ms, "armed regions (gpf_regions_set)", regions_refusal));
+    return series_time_fused(h, SERIES[S_REGIONS], n, mode, ms);
 }

@@ -1,9 +1,12 @@
 // Part of api.hip (included there, not compiled on its own): what the per-step recorders of a handle -- probes, film integrals,
-// weighted integrals, regions, lines, extrema, statistics, an elastic handle's deformation series, step changes (api_<name>.inc, included
-// behind this file) -- have in common: the
-// arithmetic of a stride's records, their way to the host and out of it, the alignment test of the 16-byte loads, the arguments
-// and the two launches of the row-reduced series (device side: series_rows.hpp), the cases the film reductions refuse, how
-// series are put aside for a call, the frame of the gpf_*_time diagnostics, and the cut of a small-grid batch.  A new series is named here in SeriesAside, series_forget_records and, if it cuts, small_batch_cut.
+// weighted integrals, regions, lines, extrema, statistics, step changes, an elastic handle's deformation series (api_<name>.inc,
+// included behind this file) -- have in common: the arithmetic of a stride's records, their way to the host and out of it, the
+// alignment test of the 16-byte loads, the arguments and the two launches of the row-reduced series (device side:
+// series_rows.hpp), the cases the film reductions refuse, the table of the series (SERIES) and every walk over it -- the records
+// forgotten, the buffers freed, the series put aside for a call, the cut of a small-grid batch, the closed stage-wise step and the
+// records that wait for gpf_elastic_update --, the shared checks of the gpf_<name>_set / _clear / _now / _time entry points and
+// the frame of the gpf_*_time diagnostics.  A new series is its api_<name>.inc, its struct in gpf_handle and a row of SERIES:
+// add a row (DESIGN.md 3.3n).
 
 // ---- records of a stride -----------------------------------------------------------------------------------------------------
 // Records a stepping call leaves for the steps (base, base + ran]: the multiples of `every` among them.
@@ -56,9 +59,13 @@ template <class... T> static void series_read(const std::vector<long long>& step
     for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = steps[(size_t)k];
 }
 
+// The device buffers a series owns, by address (null: unused entry)
+using SeriesBuffers = std::array<void**, 5>;
+
 // hipFree what is there and forget it (the *_release of a series, once the stream is idle)
-static int series_free(std::initializer_list<void**> buffers) {
+static int series_free(const SeriesBuffers& buffers) {
     for (void** p : buffers) {
+        if (!p) continue;
         if (*p) HIP_TRY(hipFree(*p));
         *p = nullptr;
     }
@@ -115,25 +122,101 @@ static int series_refusal(const gpf_handle* h, const std::string& who, const cha
     return GPF_OK;
 }
 
+// ---- the table of the series ---------------------------------------------------------------------------------------------------
+// When a series records a closed stage-wise step (gpf_close_step): not at all; behind the close's launches; there unless the
+// handle's gap is elastic, behind gpf_elastic_update then (the gap deforms after the step closes: the record holds the gap the
+// handle holds with that state); or behind gpf_elastic_update alone (no record on other handles)
+enum { SERIES_NOT_STAGEWISE = 0, SERIES_AT_CLOSE, SERIES_AT_CLOSE_UNLESS_ELASTIC, SERIES_BEHIND_UPDATE };
+
+// One row per series.  name: as the entry points spell it (gpf_<name>_set, ...).  arming: the word that arms it, 0 while it is
+// not.  forget: the records the host holds for _read go (null: it keeps none per call).  store: its SeriesStore (null: none).
+// begin, launch, collect, release, owned: its api_<name>.inc's -- a stepping call begins; behind the launches of the step that
+// takes the count to `expect` in a batch that began at `base`; after the batch's state has been read, `ran` steps committed; the
+// series disarmed, the stream drained, its buffers freed; those buffers.  Each returns at once while the series is not armed.
+// fused: gpf_step records it.  next_record: the next step after `at` it records, for the series that cut a one-workgroup batch
+// there (null: k_small_steps records it itself, or it is not fused).  stagewise: SERIES_* above.
+struct Series {
+    const char* name;
+    long long* (*arming)(gpf_handle*);
+    void (*forget)(gpf_handle*);
+    SeriesStore* (*store)(gpf_handle*);
+    int (*begin)(gpf_handle*);
+    int (*launch)(gpf_handle*, long long expect, long long base);
+    int (*collect)(gpf_handle*, long long base, long long ran);
+    int (*release)(gpf_handle*);
+    SeriesBuffers (*owned)(gpf_handle*);
+    bool fused;
+    long long (*next_record)(gpf_handle*, const Series&, long long at);
+    int stagewise;
+};
+
+// The next multiple of the armed stride after `at` (never, while not armed)
+static long long series_next_record(gpf_handle* h, const Series& r, long long at) {
+    const long long every = *r.arming(h);
+    return every ? (at / every + 1) * every : LLONG_MAX;
+}
+static long long stats_next_record(gpf_handle* h, const Series& r, long long at);
+
+#define SERIES_HOOKS(x)                                                                                                          \
+    static int x##_begin(gpf_handle*); static int x##_launch(gpf_handle*, long long, long long);                                \
+    static int x##_collect(gpf_handle*, long long, long long); static int x##_release(gpf_handle*); static SeriesBuffers x##_owned(gpf_handle*);
+SERIES_HOOKS(probes) SERIES_HOOKS(integrals) SERIES_HOOKS(weighted) SERIES_HOOKS(regions) SERIES_HOOKS(lines) SERIES_HOOKS(extrema)
+SERIES_HOOKS(stats) SERIES_HOOKS(changes) SERIES_HOOKS(eldef)
+#undef SERIES_HOOKS
+// The first columns of a row whose struct in gpf_handle derives from SeriesStore; the hooks' columns
+#define SERIES_STORE(field) [](gpf_handle* h) { return &h->field.every; }, [](gpf_handle* h) { h->field.forget(); }, [](gpf_handle* h) -> SeriesStore* { return &h->field; }
+#define SERIES_HOOKS(x) x##_begin, x##_launch, x##_collect, x##_release, x##_owned
+
+// In gpf_step's order -- of the refusals a caller sees first, and of the recording launches on the stream --, the deformation
+// series, which gpf_step does not record, behind them
+enum { S_PROBES, S_INTEGRALS, S_WEIGHTED, S_REGIONS, S_LINES, S_EXTREMA, S_STATS, S_CHANGES, S_ELDEF };
+static const Series SERIES[] = {
+    {"probes", [](gpf_handle* h) { return &h->probes.n; }, [](gpf_handle* h) { h->probes.host.clear(); h->probes.first_step = h->host_step + 1; }, nullptr,
+     SERIES_HOOKS(probes), true, nullptr, SERIES_AT_CLOSE},
+    {"integrals", SERIES_STORE(integ), SERIES_HOOKS(integrals), true, nullptr, SERIES_BEHIND_UPDATE},
+    {"weighted", SERIES_STORE(weighted), SERIES_HOOKS(weighted), true, series_next_record, SERIES_NOT_STAGEWISE},
+    {"regions", SERIES_STORE(regions), SERIES_HOOKS(regions), true, series_next_record, SERIES_NOT_STAGEWISE},
+    {"lines", SERIES_STORE(lines), SERIES_HOOKS(lines), true, series_next_record, SERIES_NOT_STAGEWISE},
+    {"extrema", SERIES_STORE(extr), SERIES_HOOKS(extrema), true, nullptr, SERIES_AT_CLOSE_UNLESS_ELASTIC},
+    // (the statistics hold a window, not a call's records: stats_restart; their floor decides where they cut)
+    {"stats", [](gpf_handle* h) { return &h->stats.every; }, nullptr, nullptr, SERIES_HOOKS(stats), true, stats_next_record, SERIES_AT_CLOSE},
+    {"changes", SERIES_STORE(chg), SERIES_HOOKS(changes), true, series_next_record, SERIES_NOT_STAGEWISE},
+    {"elastic_series", SERIES_STORE(eldef), SERIES_HOOKS(eldef), false, nullptr, SERIES_BEHIND_UPDATE},
+};
+#undef SERIES_STORE
+#undef SERIES_HOOKS
+// gpf_close_step's order, and gpf_elastic_update's: extrema before film integrals, where gpf_step has them the other way round
+// (kept apart: the order decides which of two refusals a caller sees)
+static const int SERIES_STAGEWISE[] = {S_PROBES, S_EXTREMA, S_INTEGRALS, S_ELDEF, S_STATS};
+
+// The records every series holds on the host for _read go: a stepping call in which a series records nothing leaves none
+static void series_forget_records(gpf_handle* h) {
+    for (const Series& r : SERIES)
+        if (r.forget) r.forget(h);
+}
+
+// gpf_destroy: the series' device buffers (the stream has been drained; errors are not reported there)
+static void series_destroy(gpf_handle* h) {
+    for (const Series& r : SERIES)
+        for (void** p : r.owned(h))
+            if (p && *p) (void)hipFree(*p);
+}
+
 // ---- series put aside for a call ---------------------------------------------------------------------------------------------
-// What arms each of the nine series -- the probes' count and the eight strides -- remembered, and all of them disarmed except
-// `keep` (the address of one of these fields, or null: none).  restore() puts the values back; the destructor does if nobody
-// asked.  Every recorder returns at once while its series is disarmed, so this is all it takes to step without it.
+// What arms each series remembered, and all of them disarmed except `keep` (the address of one's arming word, or null: none).
+// restore() puts the values back; the destructor does if nobody asked.  Every recorder returns at once while its series is
+// disarmed, so this is all it takes to step without it.
 struct SeriesAside {
     gpf_handle* const h;
-    const void* const keep;
-    const int probes;
-    long long every[8];
+    const long long* const keep;
+    long long armed[sizeof(SERIES) / sizeof(SERIES[0])];
     bool restored = false;
-    std::array<long long*, 8> strides() const {
-        return {&h->integ.every, &h->weighted.every, &h->regions.every, &h->lines.every, &h->extr.every, &h->stats.every, &h->eldef.every, &h->chg.every};
-    }
-    SeriesAside(gpf_handle* handle, const void* keep_armed) : h(handle), keep(keep_armed), probes(handle->probes.n) {
-        if (keep != &h->probes.n) h->probes.n = 0;
+    SeriesAside(gpf_handle* handle, const long long* keep_armed) : h(handle), keep(keep_armed) {
         int k = 0;
-        for (long long* e : strides()) {
-            every[k++] = *e;
-            if (e != keep) *e = 0;
+        for (const Series& r : SERIES) {
+            long long* word = r.arming(h);
+            armed[k++] = *word;
+            if (word != keep) *word = 0;
         }
     }
     SeriesAside(const SeriesAside&) = delete;
@@ -142,24 +225,125 @@ struct SeriesAside {
     void restore() {
         if (restored) return;
         restored = true;
-        h->probes.n = probes;
         int k = 0;
-        for (long long* e : strides()) *e = every[k++];
+        for (const Series& r : SERIES) *r.arming(h) = armed[k++];
     }
-    bool keeps_statistics() const { return keep == &h->stats.every; }
+    bool keeps_statistics() const { return keep == SERIES[S_STATS].arming(h); }
 };
 
-// The records every series holds on the host for _read go: a stepping call in which a series records nothing leaves none.
-// (The statistics hold a window, not a call's records: stats_restart.)
-static void series_forget_records(gpf_handle* h) {
-    h->probes.host.clear(); h->probes.first_step = h->host_step + 1;
-    h->integ.host.clear(); h->integ.steps.clear();
-    h->weighted.host.clear(); h->weighted.steps.clear();
-    h->regions.host.clear(); h->regions.ihost.clear(); h->regions.steps.clear();
-    h->lines.host.clear(); h->lines.steps.clear();
-    h->extr.host.clear(); h->extr.cells.clear(); h->extr.steps.clear();
-    h->eldef.host.clear(); h->eldef.cells.clear(); h->eldef.steps.clear();
-    h->chg.host.clear(); h->chg.cells.clear(); h->chg.steps.clear();
+// ---- a small grid's batch ----------------------------------------------------------------------------------------------------
+// A batch of the small-grid kernel, cut at the union of the steps that the series which cut it record (the rows with a
+// next_record), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a batch in
+// pieces is bitwise the batch in one: every piece starts from the state and the run state the piece before left.  With none of
+// them armed this is the one launch.  Probes, extrema and film integrals do not cut: k_small_steps records them.
+static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base) {
+    const long long end = base + batch;
+    for (long long at = base; at < end;) {
+        long long next = end;
+        for (const Series& r : SERIES)
+            if (r.next_record) next = std::min(next, r.next_record(h, r, at));
+        GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
+        for (const Series& r : SERIES)      // (the changes': k_small_steps' exit has left q^(n-1) in the other buffer)
+            if (r.next_record) GPF_TRY(r.launch(h, next, base));
+        at = next;
+    }
+    return GPF_OK;
+}
+
+// ---- the closed stage-wise step --------------------------------------------------------------------------------------------------
+// Does the record of a closed step of this handle wait for gpf_elastic_update?
+static bool series_waits_for_update(const gpf_handle* h, const Series& r) {
+    return r.stagewise == SERIES_BEHIND_UPDATE || (r.stagewise == SERIES_AT_CLOSE_UNLESS_ELASTIC && h->el.on);
+}
+
+// gpf_close_step, behind its launches: the closed step's record, if it commits -- or, where the record waits, the note that it
+// does (`pending`) and of the step count the step began at.  Only an elastic handle has the update to wait for.
+static int series_close_launch(gpf_handle* h, const Series& r) {
+    const long long base = h->host_step;
+    if (!series_waits_for_update(h, r)) {
+        GPF_TRY(r.begin(h));
+        return r.launch(h, base + 1, base);
+    }
+    SeriesStore& s = *r.store(h);
+    s.pending = false;
+    if (!h->el.on) return GPF_OK;
+    GPF_TRY(r.begin(h));
+    s.pending = s.armed(); s.pending_base = base;
+    return GPF_OK;
+}
+
+// ... after the state has been read: the record to the host; a step that did not commit leaves nothing to wait for
+static int series_close_collect(gpf_handle* h, const Series& r, long long ran) {
+    if (!series_waits_for_update(h, r)) return r.collect(h, h->host_step, ran);
+    if (ran < 1) r.store(h)->pending = false;
+    return GPF_OK;
+}
+
+// gpf_elastic_update, behind its launches: the record of the step gpf_close_step committed just before, at the armed stride, with
+// the gap the handle now holds
+static int series_after_elastic_update(gpf_handle* h, const Series& r) {
+    SeriesStore& s = *r.store(h);
+    if (!s.pending) return GPF_OK;
+    s.pending = false;
+    const long long base = s.pending_base;
+    if (h->host_step != base + 1 || !series_due(s.every, h->host_step)) return GPF_OK;
+    GPF_TRY(r.launch(h, h->host_step, base));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return r.collect(h, base, 1);
+}
+
+// ---- what the entry points of the series share -------------------------------------------------------------------------------
+// Each takes the series' row and builds the caller's name from it, "gpf_<name>_<call>"; `refusal(h, who)` is the series' own.
+static std::string series_entry(const Series& r, const char* call) { return std::string("gpf_") + r.name + "_" + call; }
+
+// gpf_<name>_set up to the series' own arguments: the handle, the series' refusal, the stride
+template <class Refusal> static int series_set_checks(gpf_handle* h, const Series& r, int64_t every, Refusal&& refusal) {
+    if (!h) return fail(GPF_ERR_INVALID, "null handle");
+    const std::string who = series_entry(r, "set");
+    GPF_TRY(refusal(h, who));
+    if (every < 1) return fail(GPF_ERR_INVALID, who + ": every >= 1 required (" + series_entry(r, "clear") + " disarms), got " + std::to_string(every));
+    return GPF_OK;
+}
+
+// ... and once they have passed: what was armed goes, with its buffers and records (the caller arms last, when all is in place)
+static int series_disarm(gpf_handle* h, const Series& r) {
+    GPF_TRY(enter(h, true));
+    return r.release(h);
+}
+
+// gpf_<name>_clear
+static int series_clear(gpf_handle* h, const Series& r) {
+    if (!h) return fail(GPF_ERR_INVALID, "null handle");
+    if (h->step_open) return fail(GPF_ERR_STATE, series_entry(r, "clear") + ": a stage-wise step is open; close it first");
+    return series_disarm(h, r);
+}
+
+// gpf_<name>_now up to the series' own arguments (`have_args`: none of the caller's pointers is null)
+template <class Refusal> static int series_now_checks(gpf_handle* h, const Series& r, bool have_args, Refusal&& refusal) {
+    const std::string who = series_entry(r, "now");
+    if (!h || !have_args) return fail(GPF_ERR_INVALID, who + ": null argument");
+    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, who + ": upload q and topography first");
+    return refusal(h, who);
+}
+
+// ... and the run state whose step count the record is taken at: a rolled-back one has no record
+static int series_now_state(gpf_handle* h, const Series& r, StepState& s) {
+    GPF_TRY(read_state(h, s));
+    if (s.invalid) return fail(GPF_ERR_STATE, series_entry(r, "now") + ": the run state is flagged invalid (the last step was rolled back)");
+    return GPF_OK;
+}
+
+// gpf_<name>_time up to the series' own checks: modes 0..max_mode, of which mode 1 records and `needs` the series armed (the end
+// of that sentence; null: the caller says it)
+template <class Refusal> static int series_time_checks(gpf_handle* h, const Series& r, int64_t n, int mode, int max_mode, double* ms, const char* needs, Refusal&& refusal) {
+    const std::string who = series_entry(r, "time");
+    if (!h || !ms) return fail(GPF_ERR_INVALID, who + ": null argument");
+    if (!h->pre_run_done) return fail(GPF_ERR_STATE, who + ": call gpf_pre_run first");
+    GPF_TRY(refusal(h, who));
+    if (n < 1 || n > h->log_cap || mode < 0 || mode > max_mode)
+        return fail(GPF_ERR_INVALID, who + ": 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0.." + std::to_string(max_mode) + " required");
+    if (needs && mode == 1 && !*r.arming(h)) return fail(GPF_ERR_STATE, who + ": mode 1 needs " + needs);
+    return GPF_OK;
 }
 
 // ---- the gpf_*_time diagnostics ----------------------------------------------------------------------------------------------
@@ -249,32 +433,13 @@ static void series_time_keep(std::vector<double>& from, std::vector<long long>& 
     from.clear(); from_steps.clear();
 }
 
-// ---- a small grid's batch ----------------------------------------------------------------------------------------------------
-static int weighted_launch(gpf_handle* h, long long expect, long long base);
-static int regions_launch(gpf_handle* h, long long expect, long long base);
-static int lines_launch(gpf_handle* h, long long expect, long long base);
-static int stats_launch(gpf_handle* h, long long expect);
-static int changes_launch(gpf_handle* h, long long expect, long long base);
-static long long stats_floor(const gpf_handle* h);
-
-// A batch of the small-grid kernel, cut at the union of the steps that the series which cut it record (weighted integrals,
-// regions, lines, statistics, changes), each series' kernels launched at its own steps.  k_small_steps itself knows nothing of them, and a
-// batch in pieces is bitwise the batch in one: every piece starts from the state and the run state the piece before left.
-// With none of them armed this is the one launch.  Probes, extrema and film integrals do not cut: k_small_steps records them.
-static int small_batch_cut(gpf_handle* h, long long batch, int honor_stop, long long base) {
-    const long long end = base + batch;
-    for (long long at = base; at < end;) {
-        long long next = end;
-        for (long long every : {h->weighted.every, h->regions.every, h->lines.every, h->chg.every})
-            if (every) next = std::min(next, (at / every + 1) * every);
-        if (h->stats.every) next = std::min(next, (std::max(at, stats_floor(h)) / h->stats.every + 1) * h->stats.every);
-        GPF_TRY(enqueue_small_steps(h, (int)(next - at), honor_stop, base));
-        GPF_TRY(weighted_launch(h, next, base));
-        GPF_TRY(regions_launch(h, next, base));
-        GPF_TRY(lines_launch(h, next, base));
-        GPF_TRY(stats_launch(h, next));
-        GPF_TRY(changes_launch(h, next, base));     // (k_small_steps' exit has left q^(n-1) in the other buffer)
-        at = next;
-    }
-    return GPF_OK;
+// The rest of a gpf_<name>_time whose modes are 0 -- nothing recorded, the armed series put aside for the call -- and 1 --
+// recording at the armed stride --: n steps as gpf_step enqueues them with the row's hooks
+static int series_time_fused(gpf_handle* h, const Series& r, int64_t n, int mode, double* ms) {
+    GPF_TRY(enter(h));
+    SeriesAside aside(h, mode == 1 ? r.arming(h) : nullptr);
+    GPF_TRY(r.begin(h));        // (returns at once in mode 0)
+    return series_time(h, series_entry(r, "time").c_str(), aside,
+                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return r.launch(h, expect, base); }); },
+                       [&](long long base, long long ran) { return r.collect(h, base, ran); }, ms);
 }

@@ -78,20 +78,10 @@ extern "C" int gpf_close_step(gpf_handle* h, gpf_scalars_t* out) {
     hipLaunchKernelGGL(k_commit_unfused, dim3(1), dim3(1), 0, h->stream, h->st, pre, post);
     HIP_TRY(hipGetLastError());
     h->step_open = false;
-    GPF_TRY(probes_begin(h));
-    GPF_TRY(probes_launch(h, h->host_step + 1, h->host_step));      // the closed step's record, if it commits
-    GPF_TRY(extrema_close_step_launch(h));                          // likewise, at the armed stride
-    GPF_TRY(integrals_close_step_launch(h));                        // an elastic handle's film integrals and its deformation series:
-    GPF_TRY(eldef_close_step_launch(h));                            // pending until gpf_elastic_update
-    GPF_TRY(stats_begin(h));
-    GPF_TRY(stats_launch(h, h->host_step + 1));                     // likewise; the statistics do not read the gap: an elastic handle's need not wait
+    for (int k : SERIES_STAGEWISE) GPF_TRY(series_close_launch(h, SERIES[k]));      // the closed step's records, if it commits
     StepState s;
     GPF_TRY(read_state(h, s));
-    GPF_TRY(probes_collect(h, s.step - h->host_step));
-    GPF_TRY(extrema_close_step_collect(h, s.step - h->host_step));
-    integrals_close_step_collect(h, s.step - h->host_step);
-    eldef_close_step_collect(h, s.step - h->host_step);
-    GPF_TRY(stats_collect(h, s.step));
+    for (int k : SERIES_STAGEWISE) GPF_TRY(series_close_collect(h, SERIES[k], s.step - h->host_step));
     // the committed state is the field the sound-speed pass ran on (a rolled-back step keeps the old state instead)
     if (h->gp_state_mean_fresh && !s.invalid && s.step == h->host_step + 1) {
         h->gp_state_mean_valid = true;

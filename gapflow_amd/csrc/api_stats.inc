@@ -57,16 +57,17 @@ static int stats_enqueue(gpf_handle* h, long long expect, long long n) {
 
 // Behind the launches of one step: record it if it takes the count to a multiple of the stride above the floor.  No launch
 // otherwise, and none without statistics armed.
-static int stats_launch(gpf_handle* h, long long expect) {
+static int stats_launch(gpf_handle* h, long long expect, long long) {
     const long long every = h->stats.every;
     if (!every || expect % every != 0 || expect <= stats_floor(h)) return GPF_OK;
     return stats_enqueue(h, expect, stats_rank(expect, every, stats_floor(h)));
 }
 
-// After the state has been read (the stream is idle; the step count stands at `step`): the device's record of the window, held
-// against the host's own count -- the records applied are a prefix, so the two can differ only if a launch was lost
-static int stats_collect(gpf_handle* h, long long step) {
+// After the state has been read (the stream is idle; the step count stands at `step` = base + ran): the device's record of the
+// window, held against the host's own count -- the records applied are a prefix, so the two can differ only if a launch was lost
+static int stats_collect(gpf_handle* h, long long base, long long ran) {
     if (!h->stats.every) return GPF_OK;
+    const long long step = base + ran;
     HIP_TRY(hipMemcpy(&h->stats.host, h->stats.rec, sizeof(StatsRecord), hipMemcpyDeviceToHost));
     const long long want = stats_count(h, step);
     if (h->stats.host.count != want)
@@ -87,24 +88,29 @@ static int stats_restart(gpf_handle* h, long long step) {
     return GPF_OK;
 }
 
+// Where the statistics cut a one-workgroup batch: at the next step after `at` they record, which lies above their floor
+static long long stats_next_record(gpf_handle* h, const Series&, long long at) {
+    const long long every = h->stats.every;
+    return every ? (std::max(at, stats_floor(h)) / every + 1) * every : LLONG_MAX;
+}
+
+static SeriesBuffers stats_owned(gpf_handle* h) { return {(void**)&h->stats.acc, (void**)&h->stats.rec}; }
+
 static int stats_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    GPF_TRY(series_free({(void**)&h->stats.acc, (void**)&h->stats.rec}));
+    GPF_TRY(series_free(stats_owned(h)));
     h->stats.every = 0; h->stats.after = 0; h->stats.mask = 0; h->stats.arm_step = 0;
     h->stats.host = StatsRecord{};
     return GPF_OK;
 }
 
 extern "C" int gpf_stats_set(gpf_handle* h, int64_t every, int64_t after, int field_mask) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(stats_refusal(h, "gpf_stats_set", field_mask));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_stats_set: every >= 1 required (gpf_stats_clear disarms), got " + std::to_string(every));
+    GPF_TRY(series_set_checks(h, SERIES[S_STATS], every, [&](const gpf_handle* h, const std::string& who) { return stats_refusal(h, who, field_mask); }));
     if (after < 0) return fail(GPF_ERR_INVALID, "gpf_stats_set: after >= 0 required, got " + std::to_string(after));
     if (field_mask < 1 || field_mask >= (1 << STATS_NF))
         return fail(GPF_ERR_INVALID, "gpf_stats_set: the field mask must hold at least one of the bits 1 (p), 2 (rho), 4 (jx), 8 (jy) and no other, got " +
                                      std::to_string(field_mask));
-    GPF_TRY(enter(h, true));
-    GPF_TRY(stats_release(h));
+    GPF_TRY(series_disarm(h, SERIES[S_STATS]));
     auto undo = [&](int code) { (void)stats_release(h); return code; };
     hipError_t e = hipMalloc(&h->stats.acc, (size_t)stats_nfields(field_mask) * STATS_NQ * h->L.plane * sizeof(double) + PLANE_PAD_BYTES);
     if (e == hipSuccess) e = hipMalloc(&h->stats.rec, sizeof(StatsRecord));
@@ -118,12 +124,7 @@ extern "C" int gpf_stats_set(gpf_handle* h, int64_t every, int64_t after, int fi
     return GPF_OK;
 }
 
-extern "C" int gpf_stats_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_stats_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return stats_release(h);
-}
+extern "C" int gpf_stats_clear(gpf_handle* h) { return series_clear(h, SERIES[S_STATS]); }
 
 extern "C" int gpf_stats_info(gpf_handle* h, int64_t* count, int64_t* first_step, int64_t* last_step, double* t_first, double* t_last) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
@@ -164,19 +165,18 @@ extern "C" int gpf_stats_read(gpf_handle* h, int field, int quantity, double* ou
 // k_stats_stream, the elementwise kernel that moves a record's bytes over the same planes, and no step (the window restarts:
 // its accumulators have been written over).  *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_stats_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_stats_time: call gpf_pre_run first");
-    GPF_TRY(stats_refusal(h, "gpf_stats_time", h->stats.mask));
-    if (h->cfg.thinning != GPF_THINNING_NONE || h->el.on || h->gp[0].set || h->gp[1].set || h->gp[2].set)
-        return fail(GPF_ERR_STATE, "gpf_stats_time: handles that gpf_step advances only (this one steps stage-wise)");
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 2)
-        return fail(GPF_ERR_INVALID, "gpf_stats_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..2 required");
+    GPF_TRY(series_time_checks(h, SERIES[S_STATS], n, mode, 2, ms, nullptr, [](const gpf_handle* h, const std::string& who) {
+        GPF_TRY(stats_refusal(h, who, h->stats.mask));
+        if (h->cfg.thinning != GPF_THINNING_NONE || h->el.on || h->gp[0].set || h->gp[1].set || h->gp[2].set)
+            return fail(GPF_ERR_STATE, who + ": handles that gpf_step advances only (this one steps stage-wise)");
+        return (int)GPF_OK;
+    }));
     if (mode >= 1 && !h->stats.every) return fail(GPF_ERR_STATE, "gpf_stats_time: modes 1 and 2 need armed statistics (gpf_stats_set)");
     GPF_TRY(enter(h));
     SeriesAside aside(h, mode == 1 ? &h->stats.every : nullptr);
     return series_time(h, "gpf_stats_time", aside,
                        [&](long long base) {
-                           if (mode != 2) return series_time_steps(h, n, base, [&](long long expect) { return stats_launch(h, expect); });
+                           if (mode != 2) return series_time_steps(h, n, base, [&](long long expect) { return stats_launch(h, expect, base); });
                            int par = 0;
                            GPF_TRY(current_parity(h, &par));
                            const int mask = h->stats.mask, nin = ((mask & 3) ? 1 : 0) + ((mask >> 2) & 1) + ((mask >> 3) & 1);
@@ -185,5 +185,5 @@ extern "C" int gpf_stats_time(gpf_handle* h, int64_t n, int mode, double* ms) {
                                                   stats_nfields(mask));
                            return (int)GPF_OK;
                        },
-                       [&](long long base, long long ran) { return stats_collect(h, base + ran); }, ms);
+                       [&](long long base, long long ran) { return stats_collect(h, base, ran); }, ms);
 }

@@ -13,9 +13,9 @@ static bool weighted_wide_ok(const gpf_handle* h) { return series_wide_ok(h, h->
 
 // A stepping call begins: its records replace those of the call before
 static int weighted_begin(gpf_handle* h) {
-    if (!h->weighted.every) return GPF_OK;
+    if (!h->weighted.armed()) return GPF_OK;
     GPF_TRY(weighted_refusal(h, "gpf_step with weighted integrals armed"));
-    h->weighted.host.clear(); h->weighted.steps.clear();
+    h->weighted.forget();
     return GPF_OK;
 }
 
@@ -41,18 +41,17 @@ static int weighted_collect(gpf_handle* h, long long base, long long ran) {
     return series_collect(h->weighted.every, h->weighted.steps, base, ran, series_channel(h->weighted.host, h->weighted.rec, weighted_nrec(h)));
 }
 
+static SeriesBuffers weighted_owned(gpf_handle* h) { return {(void**)&h->weighted.w, (void**)&h->weighted.part, (void**)&h->weighted.rec}; }
+
 static int weighted_release(gpf_handle* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));       // a recording launch may still be queued
-    GPF_TRY(series_free({(void**)&h->weighted.w, (void**)&h->weighted.part, (void**)&h->weighted.rec}));
-    h->weighted.every = 0; h->weighted.K = 0;
-    h->weighted.host.clear(); h->weighted.steps.clear();
+    GPF_TRY(series_free(weighted_owned(h)));
+    h->weighted.disarm(); h->weighted.K = 0;
     return GPF_OK;
 }
 
 extern "C" int gpf_weighted_set(gpf_handle* h, int64_t every, int K, const double* weights) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    GPF_TRY(weighted_refusal(h, "gpf_weighted_set"));
-    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_weighted_set: every >= 1 required (gpf_weighted_clear disarms), got " + std::to_string(every));
+    GPF_TRY(series_set_checks(h, SERIES[S_WEIGHTED], every, weighted_refusal));
     if (K < 1 || K > WFILM_MAX_K)
         return fail(GPF_ERR_INVALID, "gpf_weighted_set: 1 to " + std::to_string(WFILM_MAX_K) + " weight planes required, got " + std::to_string(K));
     if (!weights) return fail(GPF_ERR_INVALID, "gpf_weighted_set: null weights");
@@ -65,8 +64,7 @@ extern "C" int gpf_weighted_set(gpf_handle* h, int64_t every, int K, const doubl
                 if (!std::isfinite(weights[(size_t)k * ncell + (size_t)ix * ny + iy]))
                     return fail(GPF_ERR_INVALID, "gpf_weighted_set: weight plane " + std::to_string(k) + " is not finite at cell (" +
                                                  std::to_string(ix) + ", " + std::to_string(iy) + ")");
-    GPF_TRY(enter(h, true));
-    GPF_TRY(weighted_release(h));
+    GPF_TRY(series_disarm(h, SERIES[S_WEIGHTED]));
     auto undo = [&](int code) { (void)weighted_release(h); return code; };
 #define HIP_TRY_W(expr)                                                                                 \
     do {                                                                                                \
@@ -100,31 +98,23 @@ extern "C" int gpf_weighted_set(gpf_handle* h, int64_t every, int K, const doubl
     return GPF_OK;
 }
 
-extern "C" int gpf_weighted_clear(gpf_handle* h) {
-    if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_weighted_clear: a stage-wise step is open; close it first");
-    GPF_TRY(enter(h, true));
-    return weighted_release(h);
-}
+extern "C" int gpf_weighted_clear(gpf_handle* h) { return series_clear(h, SERIES[S_WEIGHTED]); }
 
 extern "C" int gpf_weighted_read(gpf_handle* h, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (!h->weighted.every) return fail(GPF_ERR_STATE, "gpf_weighted_read: no weighted integrals are armed (gpf_weighted_set)");
+    if (!h->weighted.armed()) return fail(GPF_ERR_STATE, "gpf_weighted_read: no weighted integrals are armed (gpf_weighted_set)");
     series_read(h->weighted.steps, capacity_records, steps_out, n_records, series_channel(h->weighted.host, out, weighted_nrec(h)));
     return GPF_OK;
 }
 
 extern "C" int gpf_weighted_now(gpf_handle* h, double* out, int64_t count) {
-    if (!h || !out) return fail(GPF_ERR_INVALID, "gpf_weighted_now: null argument");
-    if (!h->has_q || !h->has_topo) return fail(GPF_ERR_STATE, "gpf_weighted_now: upload q and topography first");
-    GPF_TRY(weighted_refusal(h, "gpf_weighted_now"));
-    if (!h->weighted.every) return fail(GPF_ERR_STATE, "gpf_weighted_now: no weighted integrals are armed (gpf_weighted_set holds the weights)");
+    GPF_TRY(series_now_checks(h, SERIES[S_WEIGHTED], out != nullptr, weighted_refusal));
+    if (!h->weighted.armed()) return fail(GPF_ERR_STATE, "gpf_weighted_now: no weighted integrals are armed (gpf_weighted_set holds the weights)");
     GPF_TRY(enter(h, true));
     const size_t nrec = weighted_nrec(h);
     if (count < (int64_t)nrec) return fail(GPF_ERR_INVALID, "gpf_weighted_now: room for " + std::to_string(nrec) + " doubles required, " + std::to_string(count) + " given");
     StepState s;
-    GPF_TRY(read_state(h, s));
-    if (s.invalid) return fail(GPF_ERR_STATE, "gpf_weighted_now: the run state is flagged invalid (the last step was rolled back)");
+    GPF_TRY(series_now_state(h, SERIES[S_WEIGHTED], s));
     GPF_TRY(weighted_enqueue(h, s.step, h->log_cap));           // the slot behind a batch's
     HIP_TRY(hipMemcpyAsync(out, h->weighted.rec + (size_t)h->log_cap * nrec, nrec * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -134,16 +124,6 @@ extern "C" int gpf_weighted_now(gpf_handle* h, double* out, int64_t count) {
 // Diagnostic (tools/weighted_time.py): n steps as gpf_step enqueues them, with `mode` 0 nothing (armed weighted integrals are
 // put aside for the call), 1 recording at the armed stride; *ms = first launch to last on the handle's stream (series_time).
 extern "C" int gpf_weighted_time(gpf_handle* h, int64_t n, int mode, double* ms) {
-    if (!h || !ms) return fail(GPF_ERR_INVALID, "gpf_weighted_time: null argument");
-    if (!h->pre_run_done) return fail(GPF_ERR_STATE, "gpf_weighted_time: call gpf_pre_run first");
-    GPF_TRY(weighted_refusal(h, "gpf_weighted_time"));
-    if (n < 1 || n > h->log_cap || mode < 0 || mode > 1)
-        return fail(GPF_ERR_INVALID, "gpf_weighted_time: 1 <= n <= " + std::to_string(h->log_cap) + " and mode in 0..1 required");
-    if (mode == 1 && !h->weighted.every) return fail(GPF_ERR_STATE, "gpf_weighted_time: mode 1 needs armed weighted integrals (gpf_weighted_set)");
-    GPF_TRY(enter(h));
-    SeriesAside aside(h, mode == 1 ? &h->weighted.every : nullptr);
-    GPF_TRY(weighted_begin(h));
-    return series_time(h, "gpf_weighted_time", aside,
-                       [&](long long base) { return series_time_steps(h, n, base, [&](long long expect) { return weighted_launch(h, expect, base); }); },
-                       [&](long long base, long long ran) { return weighted_collect(h, base, ran); }, ms);
+    GPF_TRY(series_time_checks(h, SERIES[S_WEIGHTED], n, mode, 1, ms, "armed weighted integrals (gpf_weighted_set)", weighted_refusal));
+    return series_time_fused(h, SERIES[S_WEIGHTED], n, mode, ms);
 }
