@@ -6,7 +6,9 @@ Several GPUs of one node: start one process per GPU,
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m gapflow_amd -i input.yaml
 
 and the problem is cut into x-slabs (gapflow_amd/slab.py); rank 0 writes the output.  GPF_SLAB_TRANSPORT=p2p selects the
-peer-to-peer mailbox transport instead of one all-gather per step.
+peer-to-peer mailbox transport instead of one all-gather per step.  `options.domain_series: {integrals: N, extrema: M}` in the
+YAML file records the film integrals and the field extrema of the whole domain during such a run (all-gather transport;
+integrals.npz / extrema.npz from rank 0); a single-process run ignores the key (its own: options.integrals, options.extrema).
 
 ``python -m gapflow_amd -i a.yaml b.yaml c.yaml`` runs several small problems together as an ensemble, one workgroup of one
 launch each (gapflow_amd/ensemble.py); every one of them writes what it would write run alone.

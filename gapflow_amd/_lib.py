@@ -190,6 +190,17 @@ SIGNATURES = {
     'gpf_extrema_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_extrema_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32)]),
     'gpf_extrema_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_slab_series_set': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32),
+                                      C.c_int64]),
+    'gpf_slab_series_clear': (C.c_int, [C.c_void_p]),
+    'gpf_slab_series_message': (C.c_int, [C.c_void_p, _VPP, C.POINTER(C.c_size_t)]),
+    'gpf_slab_series_begin': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    'gpf_slab_series_local': (C.c_int, [C.c_void_p, C.c_int64]),
+    'gpf_slab_series_fold': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64]),
+    'gpf_slab_series_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    'gpf_slab_series_read': (C.c_int, [C.c_void_p, C.c_int, _DP, C.POINTER(C.c_int32), _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_slab_series_now_local': (C.c_int, [C.c_void_p]),
+    'gpf_slab_series_now_fold': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _DP, C.c_int64, _DP, C.POINTER(C.c_int32)]),
     'gpf_elastic_series_set': (C.c_int, [C.c_void_p, C.c_int64]),
     'gpf_elastic_series_clear': (C.c_int, [C.c_void_p]),
     'gpf_elastic_series_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

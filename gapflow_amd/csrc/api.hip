@@ -34,6 +34,7 @@
 #include "resample_kernels.hip"
 #include "elastic_series_kernels.hip"
 #include "change_kernels.hip"
+#include "slab_series_kernels.hip"
 
 using namespace gpf;
 
@@ -175,6 +176,16 @@ struct gpf_handle {
     // (no SeriesStore: a window, not a call's records)
     struct { long long every = 0, after = 0, arm_step = 0; int mask = 0; double* acc = nullptr; StatsRecord* rec = nullptr; bool narrow = false;
              StatsRecord host = {}; } stats;
+    // domain series of an x-slab (api_slab_series.inc): the cut -- global rows below this slab's first, the domain's rows, the ranks,
+    // the rows of the longest slab (nranks 0: not set) --, the film integrals' GLOBAL sections, and one SeriesStore per series (its
+    // stride, its records of the last stepping call), each with the records' simulated times; `base`: the step count that call
+    // began at, `now_step` the one gpf_slab_series_now_local took its partials at (-1: none waits for its fold).  Device: this
+    // rank's message ([max_nx][SLAB_SERIES_W]) and the records ([log_cap + 1] slots each), allocated by gpf_slab_series_set
+    // (`narrow`: GPF_FILM_NARROW was set then, 8-byte loads)
+    struct { int row0 = 0, nx_global = 0, nranks = 0, max_nx = 0; int nsx = 0, nsy = 0; int sx[FILM_MAX_SECTIONS] = {}, sy[FILM_MAX_SECTIONS] = {};
+             SeriesStore film, ext; std::vector<double> film_time, ext_time; long long base = 0, now_step = -1;
+             double* msg = nullptr; double* rec = nullptr; double* film_t = nullptr; double* val = nullptr; int* cell = nullptr; double* ext_t = nullptr;
+             bool narrow = false; } sser;
     double* stage = nullptr;                // contiguous staging for upload/download
     size_t stage_doubles = 0;
     // unfused pipeline scratch (lazy)
@@ -416,6 +427,7 @@ extern "C" int gpf_create(const gpf_config* cfg, gpf_handle** out) {
 }
 
 static void series_destroy(gpf_handle* h);
+static void slab_series_destroy(gpf_handle* h);
 
 extern "C" int gpf_destroy(gpf_handle* h) {
     if (!h) return GPF_OK;
@@ -424,6 +436,7 @@ extern "C" int gpf_destroy(gpf_handle* h) {
     hipStreamSynchronize(h->stream);
     for (void* p : {(void*)h->q[0], (void*)h->q[1], (void*)h->topo, (void*)h->plan_master}) field_free(p);
     series_destroy(h);      // the series' buffers (api_series.inc)
+    slab_series_destroy(h); // a slab's domain series (api_slab_series.inc)
     void* ptrs[] = {h->topo_line, h->rowcoef, h->Ls, h->g1, h->seam, h->halo, h->beyond, h->st, h->partials, h->arrive, h->block_partials, h->spart,
                     h->log, h->stage, h->fields, h->work, h->st_trial, h->gpvar, h->gp_state_mean, h->gpscratch, h->gptile,
                     h->gp[0].Z, h->gp[0].alpha, h->gp[0].L, h->gp[1].Z, h->gp[1].alpha, h->gp[1].L,
@@ -1199,6 +1212,7 @@ extern "C" int gpf_step_timed(gpf_handle* h, int64_t n, double* kernel_ms, doubl
 #include "api_unfused_step.inc"
 #include "api_operators.inc"
 #include "api_slab_allgather.inc"
+#include "api_slab_series.inc"
 #include "api_elastic.inc"
 #include "api_slab_p2p.inc"
 #include "api_gp.inc"

@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from . import __version__
 from .io import read_yaml_input, write_yaml, create_output_directory, history_to_csv
-from .series import (ALL_SERIES, SERIES, _Series, _changes_stride, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
+from .series import (ALL_SERIES, SERIES, _Series, _changes_stride, _domain_series_entry, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
                      _integral_stride, _line_centre, _line_entries, _line_span, _lines_stride, _probe_cells, _region_entries,
                      _regions_stride, _statistics_fields, _statistics_stride, _stride, _weight_planes, _weighted_stride)
 from .topography import Topography
@@ -54,6 +54,26 @@ def _film_series(rec, sx, sy):
     data = rec.stacked(0, (ns + len(sx) + len(sy),))
     return FilmIntegrals(rec.step_array(), rec.time_array(), *[data[:, k] for k in range(ns)], data[:, ns:ns + len(sx)],
                          data[:, ns + len(sx):], np.array(sx, dtype=np.int64), np.array(sy, dtype=np.int64))
+
+
+def _extrema_series(rec):
+    """FieldExtrema of the records the _Series `rec` holds (Problem's and a SlabProblem's domain series)."""
+    nq = len(_lib.EXTREMA_NAMES)
+    vals = rec.stacked(0, (nq,))
+    return FieldExtrema(rec.step_array(), rec.time_array(), *[vals[:, k] for k in range(nq)], rec.stacked(1, (nq, 2), np.int32),
+                        {name: k for k, name in enumerate(_lib.EXTREMA_NAMES)})
+
+
+def _save_film_series(outdir, series):
+    """integrals.npz of a FilmIntegrals"""
+    np.savez(os.path.join(outdir, 'integrals.npz'), **series._asdict())
+
+
+def _save_extrema_series(outdir, series):
+    """extrema.npz of a FieldExtrema: its arrays and `names`, the order along the cells' second axis"""
+    s = series._asdict()
+    index = s.pop('index')
+    np.savez(os.path.join(outdir, 'extrema.npz'), names=np.array(sorted(index, key=index.get)), **s)
 
 
 def _termination_signals():
@@ -691,7 +711,7 @@ class Problem:
         self._integral_rec.collect(read, entries, before, [((len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy),), np.float64)])
 
     def _write_integrals(self):
-        np.savez(os.path.join(self.outdir, 'integrals.npz'), **self.integrals._asdict())
+        _save_film_series(self.outdir, self.integrals)
 
     # -------------------------------------------------------------------------------------
     # weighted film integrals (no reference counterpart)
@@ -1023,10 +1043,7 @@ class Problem:
         across `update()` and `run()` calls; None when no extrema are armed.  cells[n, index[name]] is the (ix, iy) of `name`."""
         if self._extrema_every is None:
             return None
-        rec, nq = self._extrema_rec, len(_lib.EXTREMA_NAMES)
-        vals = rec.stacked(0, (nq,))
-        return FieldExtrema(rec.step_array(), rec.time_array(), *[vals[:, k] for k in range(nq)], rec.stacked(1, (nq, 2), np.int32),
-                            {name: k for k, name in enumerate(_lib.EXTREMA_NAMES)})
+        return _extrema_series(self._extrema_rec)
 
     def field_extrema(self):
         """The same record for the current state, as a dict: the seven names of ``extrema`` and, for each, `<name>_cell` =
@@ -1053,9 +1070,7 @@ class Problem:
         self._extrema_rec.collect(read, entries, before, [((nq,), np.float64), ((nq, 2), np.int32)])
 
     def _write_extrema(self):
-        s = self.extrema._asdict()
-        index = s.pop('index')
-        np.savez(os.path.join(self.outdir, 'extrema.npz'), names=np.array(sorted(index, key=index.get)), **s)
+        _save_extrema_series(self.outdir, self.extrema)
 
     # -------------------------------------------------------------------------------------
     # deformation series of an elastic gap (no reference counterpart)
@@ -1583,6 +1598,16 @@ def _own_extrema(input_dict, opts, base_dir):
         input_dict['options']['extrema'] = _extrema_stride(opts['extrema'])
 
 
+def _own_domain_series(input_dict, opts, base_dir):
+    """`options.domain_series: {integrals: N, extrema: M, sections_x: [...], sections_y: [...]}`: the series a SlabProblem records
+    over the whole domain (SlabProblem.set_domain_series); the sections are checked against the grid, when the input has one.  A
+    Problem stores the key and never arms it, so that one file serves both."""
+    if opts.get('domain_series') is not None:
+        grid = input_dict.get('grid') or {}
+        input_dict['options']['domain_series'] = _domain_series_entry(opts['domain_series'], grid.get('Nx'), grid.get('Ny'),
+                                                                      where='options.domain_series')
+
+
 def _own_changes(input_dict, opts, base_dir):
     """`options.changes: N` (the stride; 0 or absent: off)."""
     if opts.get('changes') is not None:
@@ -1655,7 +1680,7 @@ def _own_init_from(input_dict, opts, base_dir):
 
 
 _OWN_KEYS = (_own_checkpoint_freq, _own_probes, _own_integrals, _own_extrema, _own_elastic_series, _own_weighted, _own_statistics,
-             _own_regions, _own_lines, _own_changes, _own_init_from)
+             _own_regions, _own_lines, _own_changes, _own_domain_series, _own_init_from)
 
 
 def _keep(keys, input_dict, ymlstring, base_dir=None):
@@ -1685,6 +1710,7 @@ def _keep_statistics(input_dict, ymlstring): _keep([_own_statistics], input_dict
 def _keep_regions(input_dict, ymlstring): _keep([_own_regions], input_dict, ymlstring)
 def _keep_lines(input_dict, ymlstring): _keep([_own_lines], input_dict, ymlstring)
 def _keep_changes(input_dict, ymlstring): _keep([_own_changes], input_dict, ymlstring)
+def _keep_domain_series(input_dict, ymlstring): _keep([_own_domain_series], input_dict, ymlstring)
 def _keep_init_from(input_dict, ymlstring, base_dir=None): _keep([_own_init_from], input_dict, ymlstring, base_dir)
 
 

@@ -160,6 +160,34 @@ def _integral_sections(sections, n, what):
     return out
 
 
+DOMAIN_SERIES_KEYS = ('integrals', 'extrema', 'sections_x', 'sections_y')
+
+
+def _domain_series_entry(given, nx=None, ny=None, where='domain series'):
+    """What SlabProblem.set_domain_series / options.domain_series is given, checked and completed: {integrals, extrema, sections_x,
+    sections_y} with the two strides as ints (0 or absent: that series is off) and the sections as _integral_sections leaves them
+    (None: the first and last of the domain), checked against the domain's nx, ny where given.  ValueError for an unknown key and,
+    with the film integrals' and the extrema's own messages, for a bad stride or section.  Host only: no library call."""
+    if not isinstance(given, dict) or set(given) - set(DOMAIN_SERIES_KEYS):
+        raise ValueError(f"{where}: a mapping with the keys {list(DOMAIN_SERIES_KEYS)} is required, got {given!r}")
+    out = {'integrals': _stride('integrals', 0 if given.get('integrals') is None else given['integrals'], 0),
+           'extrema': _extrema_stride(0 if given.get('extrema') is None else given['extrema'])}
+    for key, n in (('sections_x', nx), ('sections_y', ny)):
+        s = given.get(key)
+        out[key] = None if s is None else _integral_sections(s, 2**31 - 1 if n is None else int(n), key)
+    return out
+
+
+def _domain_chunk(base, n, strides, cap):
+    """The most of `n` steps a stepping call that begins at step count `base` may take so that no series (its stride in `strides`,
+    0: off) leaves more than `cap` records, _integral_records(base, ., every) <= cap: SlabProblem.advance splits a longer call
+    there, and the next piece's slots start at 0 again.  At least 1 for cap >= 1."""
+    for every in strides:
+        if every:
+            n = min(n, (base // every + cap + 1) * every - 1 - base)
+    return n
+
+
 def _weight_planes(weights, names, nx, ny):
     """(planes (K, nx, ny) float64, names) of what set_weighted_integrals is given; ValueError for a shape other than (K, nx, ny) /
     (nx, ny), K outside 1..8, a weight that is not finite (plane and cell named, the cell in the ghosted index space as the library

@@ -12,6 +12,13 @@ kernel, before the dt/residual commit:
     gpf_step_commit  (scatter the neighbours' rows, reduce records in rank order, advance dt/residual)
 
 Everything is enqueued on one stream; there is no host synchronisation inside `advance`.
+With domain series armed (SlabProblem.set_domain_series: the film integrals and the field extrema of the whole domain, on every
+rank) a step that takes the count to a due multiple is followed, on the same stream, by
+
+    gpf_slab_series_local   (this rank's rows reduced to one vector each, into the series message)
+    all_gather_into_tensor(series gathered, series message)
+    gpf_slab_series_fold    (all rows folded in the undivided order: every rank holds the undivided problem's record)
+
 Reductions are combined in rank order on every rank, so all ranks hold bit-identical dt.
 
 Kinds of a slab's outer rows (gpf_config.halo_lo/hi): 0 physical ghost row (local rule),
@@ -31,6 +38,7 @@ import numpy as np
 
 from . import _lib
 from .io import read_yaml_input
+from .series import _Series, _domain_chunk, _domain_series_entry, _integral_sections
 from .topography import Topography, topography_rows
 
 HALO_PHYSICAL, HALO_NEIGHBOUR, HALO_SEAM = 0, 1, 2
@@ -291,6 +299,7 @@ class SlabDriver:
         self.graph_honor = None
         self.use_graph = os.environ.get('GPF_SLAB_GRAPH', '0') == '1' and self.message.is_cuda
         self.p2p = False                # True: the step's own kernels exchange rows and records (gpf_step_p2p)
+        self.series = None              # armed domain series (SlabProblem.set_domain_series): begin / chunk / due / local / fold / end
 
     def _eager(self, n, honor_stop):
         for _ in range(n):
@@ -298,6 +307,29 @@ class SlabDriver:
             self.dist.all_gather_into_tensor(self.gathered, self.message)
             self.engine.commit(self.gathered, honor_stop, self.rank_lo, self.rank_hi)
         self.enqueued += n
+
+    def _recording(self, n, honor_stop):
+        """n eager steps with the domain series armed: behind the commit of a step that takes the count to a due multiple, the
+        partials of the series due, ONE all-gather of the series message and the folds, all on the stream of the step and
+        without host synchronisation in between.  The series' begin / end bracket each piece (they read the state, before the
+        first launch and after the last); a call that would leave more records than the device buffers hold is taken in pieces,
+        and a run that stopped on the device ends the call."""
+        s, done = self.series, 0
+        while done < n:
+            base = s.begin()
+            piece = s.chunk(base, n - done)
+            for i in range(piece):
+                self.engine.step_local(honor_stop)
+                self.dist.all_gather_into_tensor(self.gathered, self.message)
+                self.engine.commit(self.gathered, honor_stop, self.rank_lo, self.rank_hi)
+                if s.due(base + i + 1):
+                    s.local(base + i + 1)
+                    self.dist.all_gather_into_tensor(s.gathered, s.message)
+                    s.fold(base + i + 1)
+            self.enqueued += piece
+            done += piece
+            if s.end() < piece:
+                break
 
     def _capture(self, honor_stop):
         """Record two consecutive steps (an even and an odd one: MC_order 0 alternates the sweep direction,
@@ -323,6 +355,10 @@ class SlabDriver:
     def advance(self, n, honor_stop=False):
         """n time steps; with GPF_SLAB_GRAPH=1 pairs of steps are replayed from a captured hipGraph, which takes
         the per-step host dispatch (two library calls and one collective) off the critical path."""
+        if self.series is not None:             # eager, whatever GPF_SLAB_GRAPH says: a captured pair of steps has no room for a record
+            if self.p2p:
+                raise NotImplementedError("domain series: not recorded over the peer-to-peer transport (its batches have no host between steps)")
+            return self._recording(n, honor_stop)
         if self.p2p:
             self.engine.step_p2p(n, honor_stop)
             self.enqueued += n
@@ -407,6 +443,101 @@ class _DomainFeatures:
         return out
 
 
+class _CommittedSteps:
+    """What _Series.collect asks of a stepping call's scalar records -- how many steps it committed and the simulated time of the
+    recorded ones -- for a slab, which keeps no per-step log on the host: the times come with the records (gpf_slab_series_read),
+    and the read fills them in here."""
+
+    class _Entry:
+        def __init__(self, simtime):
+            self.simtime = simtime
+
+    def __init__(self, before, ran):
+        self.before, self.ran, self.times = before, ran, {}
+
+    def __len__(self):
+        return self.ran
+
+    def __getitem__(self, k):
+        return self._Entry(self.times[self.before + k + 1])
+
+
+class _DomainSeries:
+    """One rank's half of the armed domain series (SlabProblem.set_domain_series): the library's recorder (gpf_slab_series_*), its
+    message and the gathered messages as torch tensors, and the host's records -- one series._Series per armed series.  The
+    driver calls begin / chunk / due / local / fold / end (SlabDriver._recording); `now` is the record of the current state."""
+
+    def __init__(self, slab, integrals, extrema, sx, sy):
+        self.lib, self.h, L, t = slab.lib, slab._h, slab.layout, slab.torch
+        self.strides, self.sections = (integrals, extrema), (sx, sy)
+        i32p = C.POINTER(C.c_int32)
+        ax, ay = np.array(sx, dtype=np.int32), np.array(sy, dtype=np.int32)
+        _lib.check(self.lib.gpf_slab_series_set(self.h, L.lo - 1, L.Nx_global, L.world, integrals, len(sx), ax.ctypes.data_as(i32p),
+                                                len(sy), ay.ctypes.data_as(i32p), extrema))
+        p, n = C.c_void_p(), C.c_size_t(0)
+        _lib.check(self.lib.gpf_slab_series_message(self.h, C.byref(p), C.byref(n)))
+        self.message = t.as_tensor(_DeviceArray(p.value, n.value), device='cuda')
+        self.gathered = t.zeros(n.value * L.world, dtype=t.float64, device='cuda')
+        self.nrec = len(_lib.INTEGRAL_SUMS) + len(sx) + len(sy)
+        self.reset()
+
+    def reset(self):
+        """The series start afresh (set_domain_series, pre_run)."""
+        integrals, extrema = self.strides
+        self.film = _Series('domain integrals', integrals) if integrals else None
+        self.ext = _Series('domain extrema', extrema) if extrema else None
+        self._base = 0
+
+    def clear(self):
+        _lib.check(self.lib.gpf_slab_series_clear(self.h))
+
+    def begin(self):
+        base = C.c_int64(0)
+        _lib.check(self.lib.gpf_slab_series_begin(self.h, C.byref(base)))
+        self._base = int(base.value)
+        return self._base
+
+    def chunk(self, base, n):
+        return _domain_chunk(base, n, self.strides, _lib.LOG_CAPACITY)
+
+    def due(self, expect):
+        return any(every and expect % every == 0 for every in self.strides)
+
+    def local(self, expect):
+        _lib.check(self.lib.gpf_slab_series_local(self.h, expect))
+
+    def fold(self, expect):
+        _lib.check(self.lib.gpf_slab_series_fold(self.h, C.c_void_p(self.gathered.data_ptr()), self.gathered.numel(), expect))
+
+    def end(self):
+        """The records of the steps the call committed -> the host's series; how many steps that were."""
+        ran = C.c_int64(0)
+        _lib.check(self.lib.gpf_slab_series_end(self.h, C.byref(ran)))
+        nq, i32p = len(_lib.EXTREMA_NAMES), C.POINTER(C.c_int32)
+        for which, rec, shapes in ((0, self.film, [((self.nrec,), np.float64)]), (1, self.ext, [((nq,), np.float64), ((nq, 2), np.int32)])):
+            if rec is None or ran.value < 1:
+                continue
+            entries = _CommittedSteps(self._base, int(ran.value))
+
+            def read(b, n, steps, have, which=which, entries=entries):
+                times = np.zeros(n)
+                cells = b[1].ctypes.data_as(i32p) if which == 1 else None
+                _lib.check(self.lib.gpf_slab_series_read(self.h, which, _lib.as_dp(b[0]), cells, _lib.as_dp(times), n, steps, have))
+                entries.times = {int(steps[k]): times[k] for k in range(n)}
+            rec.collect(read, entries, self._base, shapes)
+        return int(ran.value)
+
+    def now(self, dist):
+        """Both records of the current state, as the library hands them out: (integrals [nrec], values [7], cells [7][2]).  Collective."""
+        _lib.check(self.lib.gpf_slab_series_now_local(self.h))
+        dist.all_gather_into_tensor(self.gathered, self.message)
+        nq = len(_lib.EXTREMA_NAMES)
+        out, vals, cells = np.empty(self.nrec), np.empty(nq), np.zeros((nq, 2), dtype=np.int32)
+        _lib.check(self.lib.gpf_slab_series_now_fold(self.h, C.c_void_p(self.gathered.data_ptr()), self.gathered.numel(), _lib.as_dp(out), out.size,
+                                                     _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out, vals, cells
+
+
 class SlabProblem:
     """A Problem cut into x-slabs; construct it on every rank of an initialised process group."""
 
@@ -421,11 +552,11 @@ class SlabProblem:
 
     def set_integrals(self, *args, **kwargs):
         """Film integrals are reduced on unsliced problems only."""
-        raise NotImplementedError("integrals: not available on a SlabProblem")
+        raise NotImplementedError("integrals: not available on a SlabProblem (the whole domain's: set_domain_series / domain_film_integrals)")
 
     def film_integrals(self, *args, **kwargs):
         """Film integrals are reduced on unsliced problems only."""
-        raise NotImplementedError("integrals: not available on a SlabProblem")
+        raise NotImplementedError("integrals: not available on a SlabProblem (the whole domain's: set_domain_series / domain_film_integrals)")
 
     def set_weighted_integrals(self, *args, **kwargs):
         """Weighted film integrals are reduced on unsliced problems only."""
@@ -453,11 +584,11 @@ class SlabProblem:
 
     def set_extrema(self, *args, **kwargs):
         """Field extrema are recorded on unsliced problems only."""
-        raise NotImplementedError("extrema: not available on a SlabProblem")
+        raise NotImplementedError("extrema: not available on a SlabProblem (the whole domain's: set_domain_series / domain_field_extrema)")
 
     def field_extrema(self, *args, **kwargs):
         """Field extrema are taken on unsliced problems only."""
-        raise NotImplementedError("extrema: not available on a SlabProblem")
+        raise NotImplementedError("extrema: not available on a SlabProblem (the whole domain's: set_domain_series / domain_field_extrema)")
 
     def set_elastic_series(self, *args, **kwargs):
         """The deformation series is recorded on unsliced problems only."""
@@ -496,7 +627,8 @@ class SlabProblem:
                            ('elastic_series', 'elastic series'), ('statistics', 'statistics'), ('changes', 'changes')):
             given = opts.get(key)
             if given is not None if key in ('probes', 'integrals') else given:      # (the others: 0 is off, as on a Problem)
-                raise NotImplementedError(f"{label}: not available on a SlabProblem")
+                raise NotImplementedError(f"{label}: not available on a SlabProblem" +
+                                          (" (the whole domain's: options.domain_series)" if key in ('integrals', 'extrema') else ""))
         import torch
         if dist is None:
             import torch.distributed as dist
@@ -556,7 +688,7 @@ class SlabProblem:
                 _lib.check(self.lib.gpf_set_seam_topo(self._h, side, _lib.as_dp(seam), seam.size))
         self.engine = HipSlabEngine(self.lib, self._h, torch, self.world)
         self.driver = SlabDriver(self.engine, L, dist, torch)
-        self._elastic = None
+        self._elastic, self._domain = None, None
         if prop.get('elastic', {}).get('enabled', False):
             self._elastic = SlabElastic(self, grid, prop['elastic'], topo_rows)
 
@@ -581,6 +713,102 @@ class SlabProblem:
         if os.environ.get('GPF_SLAB_TRANSPORT', 'rccl') == 'p2p':
             if not self.connect_p2p():
                 raise RuntimeError("GPF_SLAB_TRANSPORT=p2p: the peers' mailboxes could not be mapped (HIP IPC)")
+        ds = opts.get('domain_series')              # options.domain_series (from the YAML text, or carried by a checkpoint's dictionaries)
+        if ds and (ds.get('integrals') or ds.get('extrema')):
+            self.set_domain_series(ds.get('integrals') or 0, ds.get('extrema') or 0, ds.get('sections_x'), ds.get('sections_y'))
+
+    # -- domain series ----------------------------------------------------------
+    def _domain_series_refusal(self):
+        if self._gp_models or self.input.get('gp') is not None:
+            raise NotImplementedError("domain series: surrogate (GP) closures replace the pressure and wall stress the series evaluate, "
+                                      "and a slab with surrogates steps stage-wise (not supported)")
+        if self._thinning:
+            raise NotImplementedError("domain series: shear thinning needs grad p and steps stage-wise on slabs (not supported)")
+        if self._elastic is not None:
+            raise NotImplementedError("domain series: an elastic gap steps stage-wise on slabs and deforms between steps (not supported)")
+        if self.driver.p2p:
+            raise NotImplementedError("domain series: not recorded over the peer-to-peer transport (its batches have no host between steps); "
+                                      "arm them on the all-gather transport")
+
+    def set_domain_series(self, integrals=0, extrema=0, sections_x=None, sections_y=None):
+        """Record, over the WHOLE domain and on every rank, the film integrals after every step whose count is a multiple of
+        `integrals` and the field extrema after every multiple of `extrema` (strides; 0: that series is off): the records of
+        Problem.set_integrals / Problem.set_extrema, bit for bit what the undivided problem records for the same state.
+        sections_x / sections_y: up to 8 GLOBAL 1-based interior rows / columns of the flow sections, default the first and last of
+        the domain, as on a Problem.  Each rank reduces its own rows on the device; one all-gather of 32 doubles per row carries
+        them, and every rank folds all rows in the undivided order (csrc/slab_series_kernels.hip), so every rank holds the same
+        series.  Collective: the same arguments on every rank.  Starts new series (``domain_integrals``, ``domain_extrema``).
+        While armed, steps are enqueued eagerly even with GPF_SLAB_GRAPH=1.  Not available with surrogate closures, shear
+        thinning or an elastic gap (these slabs step stage-wise), nor over the peer-to-peer transport.  Checkpoints do not carry
+        the series: a slab restored from one whose options hold `domain_series` has them armed again and its series start
+        empty."""
+        self._domain_series_refusal()
+        d = _domain_series_entry({'integrals': integrals, 'extrema': extrema, 'sections_x': sections_x, 'sections_y': sections_y},
+                                 self.grid['Nx'], self.grid['Ny'])
+        if not d['integrals'] and not d['extrema']:
+            raise ValueError("domain series: at least one of the strides `integrals`, `extrema` must be >= 1 (clear_domain_series disarms)")
+        sx = _integral_sections(d['sections_x'], self.grid['Nx'], 'sections_x')
+        sy = _integral_sections(d['sections_y'], self.grid['Ny'], 'sections_y')
+        self.driver.series = None
+        self.driver.series = self._domain = _DomainSeries(self, d['integrals'], d['extrema'], sx, sy)
+
+    def clear_domain_series(self):
+        """Stop recording and free the device buffers.  Collective."""
+        if self._domain is not None:
+            self._domain.clear()
+        self.driver.series = self._domain = None
+
+    @property
+    def domain_integrals(self):
+        """FilmIntegrals of the whole domain -- the keys, shapes and dtypes of Problem.integrals -- of every recorded step since
+        set_domain_series (or pre_run), across advance() / run() calls; the same on every rank.  None while not armed."""
+        if self._domain is None or self._domain.film is None:
+            return None
+        from .problem import _film_series
+        return _film_series(self._domain.film, *self._domain.sections)
+
+    @property
+    def domain_extrema(self):
+        """FieldExtrema of the whole domain -- as Problem.extrema, the cells' ix global in the ghosted index space -- of every
+        recorded step since set_domain_series (or pre_run); the same on every rank.  None while not armed."""
+        if self._domain is None or self._domain.ext is None:
+            return None
+        from .problem import _extrema_series
+        return _extrema_series(self._domain.ext)
+
+    def _domain_now(self):
+        self._domain_series_refusal()
+        d = self._domain
+        if d is not None:
+            return d, d.now(self.dist)
+        sx = _integral_sections(None, self.grid['Nx'], 'sections_x')        # not armed: the default sections, as on a Problem
+        sy = _integral_sections(None, self.grid['Ny'], 'sections_y')
+        d = _DomainSeries(self, 0, 0, sx, sy)
+        try:
+            return d, d.now(self.dist)
+        finally:
+            d.clear()
+
+    def domain_film_integrals(self):
+        """Problem.film_integrals for the whole domain: the record of the current state, as a dict of the names of
+        ``domain_integrals``.  Armed or not (then with the default sections).  Collective; the same dict on every rank."""
+        d, (out, _, _) = self._domain_now()
+        sx, sy = d.sections
+        ns = len(_lib.INTEGRAL_SUMS)
+        res = {name: np.float64(out[k]) for k, name in enumerate(_lib.INTEGRAL_SUMS)}
+        res.update(flow_x=out[ns:ns + len(sx)].copy(), flow_y=out[ns + len(sx):].copy(),
+                   sections_x=np.array(sx, dtype=np.int64), sections_y=np.array(sy, dtype=np.int64))
+        return res
+
+    def domain_field_extrema(self):
+        """Problem.field_extrema for the whole domain: the seven names of ``domain_extrema`` and, for each, `<name>_cell` =
+        (ix, iy), ix global.  Armed or not.  Collective; the same dict on every rank."""
+        _, (_, vals, cells) = self._domain_now()
+        res = {}
+        for k, name in enumerate(_lib.EXTREMA_NAMES):
+            res[name] = np.float64(vals[k])
+            res[name + '_cell'] = (int(cells[k, 0]), int(cells[k, 1]))
+        return res
 
     def _shared_asperity_heights(self, geo):
         """topography.py:141-146 draws the minimum heights of num^2 asperities from an unseeded normal distribution: every
@@ -597,6 +825,8 @@ class SlabProblem:
         IPC handles once through the process group, map them, and from then on `advance` enqueues whole batches of
         steps whose kernels talk to each other directly.  Collective; returns False (and stays on the all-gather
         transport) unless every rank succeeded."""
+        if getattr(self, '_domain', None) is not None:
+            raise NotImplementedError("domain series: not recorded over the peer-to-peer transport; clear_domain_series first")
         t, L = self.torch, self.layout
         buf = (C.c_ubyte * 64)()
         ok = self.lib.gpf_p2p_export(self._h, buf, 64) == 0
@@ -626,7 +856,7 @@ class SlabProblem:
         from .problem import _keep_own_options
         with _io.StringIO(text) as f:
             d = read_yaml_input(f)
-        _keep_own_options(d, text, base_dir)        # options.checkpoint_freq, as Problem.from_string; the series' keys: refused in __init__
+        _keep_own_options(d, text, base_dir)        # options.checkpoint_freq, as Problem.from_string; the series' keys: refused in __init__, but domain_series
         return cls(d, device=device, dist=dist)
 
     @classmethod
@@ -775,6 +1005,8 @@ class SlabProblem:
         _lib.check(self.lib.gpf_set_dt(self._h, float(dt)))
         _lib.check(self.lib.gpf_set_ekin_old(self._h, float(g['ekin'])))
         self._pre_run_done = True
+        if self._domain is not None:
+            self._domain.reset()                # the step count starts over: so do the domain series
 
     def advance(self, n, honor_stop=False, write_freq=None):
         if not self._gp_models and not self._thinning and self._elastic is None:
@@ -941,6 +1173,11 @@ class SlabProblem:
                 w = self._writer_problem
                 w._writer.close()
                 history_to_csv(os.path.join(w.outdir, 'history.csv'), w.history)
+                from .problem import _save_extrema_series, _save_film_series
+                if self.domain_integrals is not None:       # the files a serial run with options.integrals / options.extrema writes
+                    _save_film_series(w.outdir, self.domain_integrals)
+                if self.domain_extrema is not None:
+                    _save_extrema_series(w.outdir, self.domain_extrema)
         return st
 
     def local_q(self):

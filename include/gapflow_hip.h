@@ -593,6 +593,62 @@ int gpf_extrema_now(gpf_handle* h, double values[7], int32_t cells[14]);
  * gpf_*_time diagnostics (before the point probes). */
 int gpf_extrema_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- domain series of an x-slab run (no reference counterpart: the reference is single-process) ----------------------------- */
+/* The film integrals and the field extrema of the WHOLE domain, recorded by every rank of a slab run: the records above, taken
+ * over the undivided problem's interior, bit for bit what the undivided handle records for the same state.  Both series reduce a
+ * row to a vector and fold the rows' vectors, and slabs are cut along rows: a rank reduces its own rows (the cell centre x
+ * spelled from the GLOBAL row, so that the vector is the undivided problem's own), one all-gather of doubles carries every
+ * rank's vectors, and every rank folds them in the undivided order of the global rows -- so every rank holds the same record,
+ * as it holds the same dt.  No floating-point atomics, no arrival order.  (gpf_integrals_* and gpf_extrema_* keep refusing a
+ * slab: they speak of the handle's own interior.)
+ * The cut is gapflow_amd/slab.py: partition's (csrc/slab_rows.hpp): base, rem = divmod(nx_global, nranks), the first rem ranks own
+ * base + 1 rows.  A rank's message is [max_nx][32] doubles, max_nx = base + (rem > 0): per local row the film integrals' 18 sums,
+ * the seven extrema and the column of each as a double; the gathered buffer is [nranks][max_nx][32], and rows beyond a rank's own
+ * count are never read.  The host owns the collective, so a record is two calls around it; with nothing set no launch and no HIP
+ * call differs from a handle without the series.
+ *   gpf_slab_series_set        describes the cut -- row0: global interior rows below this handle's first; the handle's Nx rows must
+ *                              be one rank's slab of nx_global rows cut into nranks -- and arms the film integrals at the stride
+ *                              every_integrals and the extrema at every_extrema (0: that series is off; both 0: only
+ *                              gpf_slab_series_now_*).  Sections as gpf_integrals_set's, but GLOBAL: rows 1..nx_global, columns
+ *                              1..Ny, NULL / 0: the first and last of the domain; the same messages.  Allocates the message and
+ *                              the records ((log_cap + 1) each); collective in that every rank passes the same arguments but its
+ *                              own row0.  A handle with neither halo (nranks 1) is accepted and records the undivided record.
+ *                              GPF_ERR_INVALID with surrogate closures, shear thinning, an elastic gap (these step stage-wise on
+ *                              slabs) or a slip-length plane; GPF_ERR_STATE while a stage-wise step is open and after
+ *                              gpf_p2p_connect (the peer-to-peer batches have no host between steps).
+ *   gpf_slab_series_clear      disarms and frees the buffers, once the stream is idle.
+ *   gpf_slab_series_message    the message in device memory and its length in doubles (valid until _set / _clear / gpf_destroy).
+ *   gpf_slab_series_begin      a stepping call begins: synchronises, *base = the step count, the records of the call before go.
+ *   gpf_slab_series_local      behind the gpf_step_commit of the step that takes the count to `expect`: the partials of the series
+ *                              due then (expect a multiple of the stride), k_slab_film_partial / k_slab_extrema_partial, one
+ *                              workgroup per local row.  No launch when none is due.
+ *   gpf_slab_series_fold       behind the all-gather of the messages (`gathered`, `count` doubles = nranks * the message's): the
+ *                              folds of the same series, one workgroup each, into the slot of the step among the call's records.
+ *                              Like every recorder, all four kernels write only if the device's run state shows the count
+ *                              `expect` and a valid state.  A call may leave log_cap records per series: GPF_ERR_INVALID beyond.
+ *   gpf_slab_series_end        synchronises and takes the records of the steps the call committed to the host; *ran = how many
+ *                              steps that were.  A run that stopped on the device leaves none for the steps it skipped.
+ *   gpf_slab_series_read       the records of the last begin .. end, with gpf_integrals_read's / gpf_extrema_read's layout and
+ *                              rules: which 0 the film integrals (values [record][9 + nsx + nsy], cells unused), 1 the extrema
+ *                              (values [record][7], cells [record][7][2], ix GLOBAL in the ghosted index space); times: the
+ *                              simulated time of each record (a slab keeps no per-step log on the host).  Any pointer may be NULL.
+ *   gpf_slab_series_now_local, gpf_slab_series_now_fold
+ *                              the two halves of both records for the current committed state, armed or not (but set), in the
+ *                              slot behind a call's; the fold synchronises and hands them out.  GPF_ERR_STATE on an invalid state. */
+int gpf_slab_series_set(gpf_handle* h, int row0, int nx_global, int nranks, int64_t every_integrals, int nsx, const int32_t* ix, int nsy,
+                        const int32_t* iy, int64_t every_extrema);
+int gpf_slab_series_clear(gpf_handle* h);
+int gpf_slab_series_message(gpf_handle* h, void** message, size_t* count);
+int gpf_slab_series_begin(gpf_handle* h, int64_t* base);
+int gpf_slab_series_local(gpf_handle* h, int64_t expect);
+int gpf_slab_series_fold(gpf_handle* h, const void* gathered, size_t count, int64_t expect);
+int gpf_slab_series_end(gpf_handle* h, int64_t* ran);
+int gpf_slab_series_read(gpf_handle* h, int which, double* values, int32_t* cells, double* times, int64_t capacity_records, int64_t* steps_out,
+                         int64_t* n_records);
+int gpf_slab_series_now_local(gpf_handle* h);
+int gpf_slab_series_now_fold(gpf_handle* h, const void* gathered, size_t count, double* integrals, int64_t integrals_count, double values[7],
+                             int32_t cells[14]);
+
 /* ---- deformation series of an elastic gap (no reference counterpart: its users download the gap after every step) ---------- */
 /* What the wall gives way by under the film it carries, reduced on the device.  A record is six doubles and two cells, taken
  * over the interior cells 1..Nx x 1..Ny with d = the deformation plane the handle holds (GPF_FIELD_DEFORMATION), p = the
