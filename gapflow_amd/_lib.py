@@ -63,6 +63,10 @@ REGION_INTS = ('cells', 'ix_min', 'ix_max', 'iy_min', 'iy_max')     # gpf_region
 LINE_MAX = 8                        # gpf_lines_set: lines per handle
 LINE_FIELDS = ('rho', 'jx', 'jy', 'p', 'h', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top')       # gpf_lines_*: a point's nine values, in the record's order
 LINE_AXES = ('x', 'y')              # gpf_line.along: GPF_LINE_X, GPF_LINE_Y
+FRAME_FIELDS = LINE_FIELDS          # gpf_frame_spec.fields: bit f selects field f; a record keeps the mask's order
+FRAME_REDUCE = ('sample', 'mean')   # gpf_frame_spec.reduce: GPF_FRAME_SAMPLE, GPF_FRAME_MEAN
+FRAME_DTYPES = ('f8', 'f4')         # gpf_frame_spec.dtype: GPF_FRAME_F8, GPF_FRAME_F4
+FRAME_MAX_STRIDE = 64               # gpf_frame_spec.sx, sy
 FIELD_NCOMP = {FIELD_Q: 3, FIELD_TOPO: 3, FIELD_EXTRA: 1, FIELD_PRESSURE: 1, FIELD_TAU_AVG: 3,
                FIELD_WALL_LOWER: 6, FIELD_WALL_UPPER: 6, 7: 1, 8: 1, 9: 1, 10: 1}
 
@@ -87,6 +91,12 @@ class GpfRegion(C.Structure):
 class GpfLine(C.Structure):
     """gpf_line of include/gapflow_hip.h"""
     _fields_ = [('along', C.c_int32), ('i0', C.c_int32), ('i1', C.c_int32)]
+
+
+class GpfFrameSpec(C.Structure):
+    """gpf_frame_spec of include/gapflow_hip.h"""
+    _fields_ = [('fields', C.c_int32), ('ix0', C.c_int32), ('ix1', C.c_int32), ('iy0', C.c_int32), ('iy1', C.c_int32),
+                ('sx', C.c_int32), ('sy', C.c_int32), ('reduce', C.c_int32), ('dtype', C.c_int32)]
 
 
 class GpfScalars(C.Structure):
@@ -226,6 +236,12 @@ SIGNATURES = {
     'gpf_lines_read': (C.c_int, [C.c_void_p, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_lines_now': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfLine), _DP, C.c_int64]),
     'gpf_lines_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_frames_set': (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(GpfFrameSpec), C.c_int64]),
+    'gpf_frames_clear': (C.c_int, [C.c_void_p]),
+    'gpf_frames_read': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_frames_now': (C.c_int, [C.c_void_p, C.POINTER(GpfFrameSpec), C.c_void_p, C.c_int64]),
+    'gpf_frames_shape': (C.c_int, [C.c_void_p, C.POINTER(GpfFrameSpec), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    'gpf_frames_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_ensemble_create': (C.c_int, [_VPP, C.c_int, _VPP]),
     'gpf_ensemble_step': (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]),
     'gpf_ensemble_log': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GpfScalars), C.c_int64, C.POINTER(C.c_int64)]),

@@ -31,6 +31,7 @@
 #include "stats_kernels.hip"
 #include "region_kernels.hip"
 #include "line_kernels.hip"
+#include "frame_kernels.hip"
 #include "resample_kernels.hip"
 #include "elastic_series_kernels.hip"
 #include "change_kernels.hip"
@@ -76,17 +77,19 @@ enum { PREV_LOST_NO_STEP = 0, PREV_LOST_CLOSURES, PREV_LOST_STAGEWISE, PREV_LOST
 
 // What every strided series of a handle keeps (gpf_handle: the per-series structs derive from it): the recording stride that arms
 // it; the records of the last stepping call on the host -- doubles, for some a second channel of int32 (`cells`) or int64
-// (`ints`) -- with their step counts; and, for the series an elastic handle records behind gpf_elastic_update, whether a closed
-// step waits for that call and the step count it began at (api_series.inc: series_close_*).
+// (`ints`), for the frames raw bytes (`bytes`) instead -- with their step counts; and, for the series an elastic handle records
+// behind gpf_elastic_update, whether a closed step waits for that call and the step count it began at (api_series.inc:
+// series_close_*).
 struct SeriesStore {
     long long every = 0;                    // 0: not armed
     std::vector<double> host;
     std::vector<int32_t> cells;
     std::vector<long long> ints, steps;
+    std::vector<unsigned char> bytes;
     bool pending = false;
     long long pending_base = 0;
     bool armed() const { return every != 0; }
-    void forget() { host.clear(); cells.clear(); ints.clear(); steps.clear(); }
+    void forget() { host.clear(); cells.clear(); ints.clear(); bytes.clear(); steps.clear(); }
     void disarm() { every = 0; pending = false; forget(); }
 };
 
@@ -156,6 +159,10 @@ struct gpf_handle {
     // ([capacity + 1][rec_doubles]) and the chunk sums of the bands along y, both allocated by gpf_lines_set
     struct : SeriesStore { int K = 0; Line defs[LINE_MAX_K] = {}; long long rec_doubles = 0, capacity = 0; double* rec = nullptr;
              double* scratch = nullptr; } lines;
+    // reduced frames (api_frames.inc): the frame as the kernels read it, normalised; bytes per record and records the device buffer
+    // holds (a batch never leaves more: frames_batch); the device records of the batch in flight ([capacity + 1][record_bytes],
+    // float or double as the frame says -> the store's `bytes`), allocated by gpf_frames_set
+    struct FrameSeries : SeriesStore { FrameSpec spec = {}; long long record_bytes = 0, capacity = 0; char* rec = nullptr; } frames;
     // field extrema (api_extrema.inc): the device records of the batch in flight ([log_cap + 1][7] doubles, [log_cap + 1][14] int32
     // -> the store's `cells`) and the row scratch, allocated on first use (`narrow`: as above)
     // `dev`: the ExtremaArgs of these buffers in device memory, for k_small_steps
@@ -1132,6 +1139,7 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
 #include "api_changes.inc"
 #include "api_regions.inc"
 #include "api_lines.inc"
+#include "api_frames.inc"
 #include "api_stats.inc"
 
 extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t* log, int64_t log_capacity,
@@ -1149,7 +1157,7 @@ extern "C" int gpf_step(gpf_handle* h, int64_t n, int honor_stop, gpf_scalars_t*
         if (r.fused) GPF_TRY(r.begin(h));
     while (done < n) {
         const long long base = h->host_step;
-        const int64_t batch = lines_batch(h, std::min<int64_t>(n - done, h->log_cap), base);        // (lines: no more records than their buffer holds)
+        const int64_t batch = frames_batch(h, lines_batch(h, std::min<int64_t>(n - done, h->log_cap), base), base);     // (lines, frames: no more records than their buffers hold)
         if (small) GPF_TRY(small_batch_cut(h, batch, honor_stop, base));       // the batch, cut at the union of the armed series' steps
         else for (int64_t i = 0; i < batch; ++i) {
             GPF_TRY(enqueue_step(h, honor_stop, base, nullptr));

@@ -66,6 +66,7 @@ static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first, int
     if (h->probes.n) return "probes are armed on it (their records need per-member slots; gpf_probes_clear, or step it alone)";
     if (h->extr.every) return "extrema are armed on it (their records need per-member slots; gpf_extrema_clear, or step it alone)";
     if (h->chg.every) return "changes are armed on it (they cut the batch per member; gpf_changes_clear, or step it alone)";
+    if (h->frames.every) return "frames are armed on it (they cut the batch per member; gpf_frames_clear, or step it alone)";
     return "";
 }
 

@@ -1,6 +1,6 @@
 // Part of api.hip (included there, not compiled on its own): what the per-step recorders of a handle -- probes, film integrals,
-// weighted integrals, regions, lines, extrema, statistics, step changes, an elastic handle's deformation series (api_<name>.inc,
-// included behind this file) -- have in common: the arithmetic of a stride's records, their way to the host and out of it, the
+// weighted integrals, regions, lines, extrema, statistics, step changes, reduced frames, an elastic handle's deformation series
+// (api_<name>.inc, included behind this file) -- have in common: the arithmetic of a stride's records, their way to the host and out of it, the
 // alignment test of the 16-byte loads, the arguments and the two launches of the row-reduced series (device side:
 // series_rows.hpp), the cases the film reductions refuse, the table of the series (SERIES) and every walk over it -- the records
 // forgotten, the buffers freed, the series put aside for a call, the cut of a small-grid batch, the closed stage-wise step and the
@@ -161,7 +161,7 @@ static long long stats_next_record(gpf_handle* h, const Series& r, long long at)
     static int x##_begin(gpf_handle*); static int x##_launch(gpf_handle*, long long, long long);                                \
     static int x##_collect(gpf_handle*, long long, long long); static int x##_release(gpf_handle*); static SeriesBuffers x##_owned(gpf_handle*);
 SERIES_HOOKS(probes) SERIES_HOOKS(integrals) SERIES_HOOKS(weighted) SERIES_HOOKS(regions) SERIES_HOOKS(lines) SERIES_HOOKS(extrema)
-SERIES_HOOKS(stats) SERIES_HOOKS(changes) SERIES_HOOKS(eldef)
+SERIES_HOOKS(stats) SERIES_HOOKS(changes) SERIES_HOOKS(frames) SERIES_HOOKS(eldef)
 #undef SERIES_HOOKS
 // The first columns of a row whose struct in gpf_handle derives from SeriesStore; the hooks' columns
 #define SERIES_STORE(field) [](gpf_handle* h) { return &h->field.every; }, [](gpf_handle* h) { h->field.forget(); }, [](gpf_handle* h) -> SeriesStore* { return &h->field; }
@@ -169,7 +169,7 @@ SERIES_HOOKS(stats) SERIES_HOOKS(changes) SERIES_HOOKS(eldef)
 
 // In gpf_step's order -- of the refusals a caller sees first, and of the recording launches on the stream --, the deformation
 // series, which gpf_step does not record, behind them
-enum { S_PROBES, S_INTEGRALS, S_WEIGHTED, S_REGIONS, S_LINES, S_EXTREMA, S_STATS, S_CHANGES, S_ELDEF };
+enum { S_PROBES, S_INTEGRALS, S_WEIGHTED, S_REGIONS, S_LINES, S_EXTREMA, S_STATS, S_CHANGES, S_FRAMES, S_ELDEF };
 static const Series SERIES[] = {
     {"probes", [](gpf_handle* h) { return &h->probes.n; }, [](gpf_handle* h) { h->probes.host.clear(); h->probes.first_step = h->host_step + 1; }, nullptr,
      SERIES_HOOKS(probes), true, nullptr, SERIES_AT_CLOSE},
@@ -181,6 +181,7 @@ static const Series SERIES[] = {
     // (the statistics hold a window, not a call's records: stats_restart; their floor decides where they cut)
     {"stats", [](gpf_handle* h) { return &h->stats.every; }, nullptr, nullptr, SERIES_HOOKS(stats), true, stats_next_record, SERIES_AT_CLOSE},
     {"changes", SERIES_STORE(chg), SERIES_HOOKS(changes), true, series_next_record, SERIES_NOT_STAGEWISE},
+    {"frames", SERIES_STORE(frames), SERIES_HOOKS(frames), true, series_next_record, SERIES_NOT_STAGEWISE},
     {"elastic_series", SERIES_STORE(eldef), SERIES_HOOKS(eldef), false, nullptr, SERIES_BEHIND_UPDATE},
 };
 #undef SERIES_STORE

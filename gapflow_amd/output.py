@@ -83,3 +83,42 @@ class FieldWriter:
         if self._topo_file is not None:
             self._topo_file.close()
             self._topo_file = None
+
+
+class FrameWriter:
+    """frames.nc: the reduced frames a problem records (Problem.set_frames), appended batch by batch.  Dimensions `frame`
+    (unlimited), `nx` = mx, `ny` = my; one variable per selected field (frame, nx, ny) of the records' dtype, `step` (i4) and `time`
+    per frame, `x` (nx) and `y` (ny), the cell-centre coordinates of the output points; the window, the stride and the reduction
+    as global attributes."""
+
+    def __init__(self, path, fields, dtype, x, y, window, stride, reduce):
+        f = self._f = netcdf_file(path, 'w', version=2)
+        f.createDimension('frame', None)
+        f.createDimension('nx', len(x))
+        f.createDimension('ny', len(y))
+        f.window, f.stride, f.reduce = np.array(window, dtype=np.int32), np.array(stride, dtype=np.int32), reduce
+        for name, v in (('x', x), ('y', y)):
+            f.createVariable(name, 'f8', ('n' + name,))[:] = v
+        self._step = f.createVariable('step', 'i4', ('frame',))
+        self._time = f.createVariable('time', 'f8', ('frame',))
+        self._fields = {name: f.createVariable(name, dtype, ('frame', 'nx', 'ny')) for name in fields}
+        self._n = 0
+        f.flush()
+
+    def append(self, steps, times, arrays):
+        """arrays: {field: (n, mx, my)} of the n records at `steps`, `times`."""
+        n = len(steps)
+        if n == 0:
+            return
+        k = self._n
+        self._step[k:k + n] = np.asarray(steps, dtype=np.int32)
+        self._time[k:k + n] = times
+        for name, v in self._fields.items():
+            v[k:k + n] = arrays[name]
+        self._n += n
+        self._f.flush()
+
+    def close(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None

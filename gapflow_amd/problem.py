@@ -26,7 +26,8 @@ from . import __version__
 from .io import read_yaml_input, write_yaml, create_output_directory, history_to_csv
 from .series import (ALL_SERIES, SERIES, _Series, _changes_stride, _domain_series_entry, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
                      _integral_stride, _line_centre, _line_entries, _line_span, _lines_stride, _probe_cells, _region_entries,
-                     _regions_stride, _statistics_fields, _statistics_stride, _stride, _weight_planes, _weighted_stride)
+                     _regions_stride, _statistics_fields, _statistics_stride, _stride, _weight_planes, _weighted_stride,
+                     _frame_axes, _frame_shape, _frame_spec, _frame_window, _frames_stride)
 from .topography import Topography
 from .stress import Pressure, WallStress, BulkStress
 
@@ -179,8 +180,11 @@ class Problem:
         self._elastic_series_every = None
         if options.get('elastic_series'):           # options.elastic_series (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_elastic_series(options['elastic_series'])
+        self._frames_every, self._frames_nc = None, None
+        if options.get('frames'):                   # options.frames / options.frame_spec (from the YAML text, or a checkpoint's dictionaries); 0: off
+            self.set_frames(options['frames'], **(options.get('frame_spec') or {}))
         self._changes_every = None
-        if options.get('changes'):                  # options.changes (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
+        if options.get('changes'):                 # options.changes (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_changes(options['changes'])
         self._stats_every = None
         if options.get('statistics'):               # options.statistics (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
@@ -1006,6 +1010,159 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'lines.npz'), **arrays)
 
     # -------------------------------------------------------------------------------------
+    # reduced frames (no reference counterpart: its pictures are drawn from the frames of sol.nc)
+    # -------------------------------------------------------------------------------------
+    def _frames_refusal(self):
+        if self.has_gp_model or self._gp_models:
+            raise NotImplementedError("frames: surrogate (GP) closures replace the pressure and wall stress the frames evaluate")
+        if self._cfg.thinning:
+            raise NotImplementedError("frames: shear thinning needs grad p, which the recording does not model")
+        if self._elastic or self.topo.elastic:
+            raise NotImplementedError("frames: an elastic gap steps stage-wise and deforms between steps (not supported)")
+
+    def _frame_struct(self, spec):
+        s = _lib.GpfFrameSpec()
+        s.fields = sum(1 << _lib.FRAME_FIELDS.index(f) for f in spec['fields'])
+        s.ix0, s.ix1, s.iy0, s.iy1 = _frame_window(spec, self.grid['Nx'], self.grid['Ny'])
+        s.sx, s.sy = spec['stride']
+        s.reduce, s.dtype = _lib.FRAME_REDUCE.index(spec['reduce']), _lib.FRAME_DTYPES.index(spec['dtype'])
+        return s
+
+    def _frame_bytes(self, spec):
+        mx, my = _frame_shape(spec, self.grid['Nx'], self.grid['Ny'])
+        return len(spec['fields']) * mx * my * np.dtype(spec['dtype']).itemsize
+
+    def _frame_split(self, data, spec):
+        """{field: array(n, mx, my)} of records (n, bytes of a record) in the library's layout: [field in mask order][a][b]."""
+        mx, my = _frame_shape(spec, self.grid['Nx'], self.grid['Ny'])
+        block = np.ascontiguousarray(data).view(np.dtype(spec['dtype'])).reshape(len(data), len(spec['fields']), mx, my)
+        return {f: block[:, k].copy() for k, f in enumerate(spec['fields'])}
+
+    def set_frames(self, every=1, fields=('rho', 'jx', 'jy', 'p'), window=None, stride=(1, 1), reduce='sample', dtype='f4',
+                   capacity=None, keep=None):
+        """Record reduced frames of the committed state after every step whose count is a multiple of `every`, on the device,
+        whichever way the steps are taken (`update()`, `run()`, batches of any length): the picture of the film at a recorded
+        step -- few fields, a window, a coarser lattice, single precision -- where a written frame (`write()`) is every derived
+        field on the whole ghosted grid in double precision, through the host.
+
+        fields: names out of the lines' nine, with the lines' definitions: rho, jx, jy (the state's own bits), p (the equation of
+        state's pressure of the committed density, bit for bit a probe's p), h (the gap the device holds), tau_xz_bot,
+        tau_yz_bot, tau_xz_top, tau_yz_top (the walls' shear stresses as ``integrals`` evaluates them -- of the committed state,
+        not the corrector-stage closures of `sol.nc`).  A record keeps them in that order.
+        window: (ix0, ix1, iy0, iy1), inclusive 1-based interior indices as in the `box` of regions; None: the whole interior.
+        stride: (sx, sy), each in 1..64: the window is cut into blocks of sx x sy cells from its corner (ix0, iy0), the last block
+        of an axis possibly ragged; a frame is (mx, my) = (ceil(rows / sx), ceil(columns / sy)) values per field.
+        reduce: 'sample', the value at the block's first cell (no arithmetic), or 'mean', the arithmetic mean over the block's
+        cells inside the window, added in a fixed order and divided once: the same state gives the same bits
+        whatever the batch size, stride `every`, capacity or kernel that stepped.  'mean' at stride (1, 1) is 'sample'.
+        dtype: 'f4' (the double result converted once, as `astype(float32)` does) or 'f8'.
+        capacity: the records the device buffer holds (None: as many as fit 64 MiB, or GPF_FRAMES_MB MiB; at least 1).  A batch
+        never holds more steps than leave that many records.  On grids small enough for the one-workgroup kernel the batch is
+        also cut at every recorded step: choose a stride there.
+        keep: whether the records also stay in memory for ``frames``; None: True for a silent problem, False otherwise -- a
+        problem that is not silent appends every collected batch to `frames.nc` in its output directory, and a long run does not
+        pile frames up in host memory.
+        A step that is rolled back as invalid leaves no record.  Starts a new series (see ``frames``).  Checkpoints do not carry
+        the series: a problem restored from one whose options hold `frames` (and `frame_spec`) has it armed again and its series
+        begins at the restart step; frames set from code do not survive a restore.  Not available with surrogate closures, shear
+        thinning or an elastic gap."""
+        self._frames_refusal()
+        every = _frames_stride(every)
+        spec = _frame_spec({'fields': fields, 'window': window, 'stride': stride, 'reduce': reduce, 'dtype': dtype, 'capacity': capacity},
+                           self.grid['Nx'], self.grid['Ny'])
+        if keep is not None and not isinstance(keep, (bool, np.bool_)):
+            raise ValueError(f"frames: keep must be True, False or None, got {keep!r}")
+        _lib.check(self._lib.gpf_frames_set(self._h, every, C.byref(self._frame_struct(spec)), spec['capacity'] or 0))
+        self._close_frames_nc()
+        self._frames_every, self._frames_spec, self._frames_rec = every, spec, _Series('frames', every)
+        self._frames_keep = bool(self.options['silent']) if keep is None else bool(keep)
+
+    def clear_frames(self):
+        """Stop recording, drop the series, close `frames.nc` and free the device buffer."""
+        if self._frames_every is not None:
+            _lib.check(self._lib.gpf_frames_clear(self._h))
+            self._close_frames_nc()
+        self._frames_every = None
+
+    def _frame_dict(self, spec, arrays, **head):
+        nx, ny = self.grid['Nx'], self.grid['Ny']
+        x, y = _frame_axes(spec, nx, ny, self.grid['dx'], self.grid['dy'])
+        out = dict(head, fields=spec['fields'], window=_frame_window(spec, nx, ny), stride=tuple(spec['stride']), reduce=spec['reduce'], x=x, y=y)
+        out.update(arrays)
+        return out
+
+    @property
+    def frames(self):
+        """The series of every recorded step since set_frames (or _pre_run) that was kept in memory (`keep`), across `update()`
+        and `run()` calls: a dict with `step`, `time` (nrecords,), `fields`, `window`, `stride`, `reduce` (as recorded: 'mean' at
+        stride (1, 1) is 'sample'), `x` (mx,), `y` (my,) -- the cell-centre coordinates of the output points: the first cell's for
+        'sample', the mean of the block's cell centres for 'mean' -- and per field an array (nrecords, mx, my) of the chosen
+        dtype.  None when no frames are armed."""
+        if self._frames_every is None:
+            return None
+        rec, spec = self._frames_rec, self._frames_spec
+        data = rec.stacked(0, (self._frame_bytes(spec),), np.uint8)
+        return self._frame_dict(spec, self._frame_split(data, spec), step=rec.step_array(), time=rec.time_array())
+
+    def frame_now(self, **spec):
+        """The same record for the current state: bit for bit what a step committing this state would have recorded, as the dict
+        of ``frames`` without `step` and `time` and with one (mx, my) array per field.  Of the armed frame (no arguments), or of
+        the frame given by set_frames' `fields`, `window`, `stride`, `reduce`, `dtype`, without arming anything.  Reads only."""
+        self._frames_refusal()
+        if not spec and self._frames_every is None:
+            raise RuntimeError("frame_now: no frames are set (set_frames), and no spec is given")
+        if spec:
+            if 'capacity' in spec or 'keep' in spec or 'every' in spec:
+                raise ValueError(f"frame_now: fields, window, stride, reduce and dtype describe a frame, got {sorted(spec)}")
+            spec = _frame_spec(spec, self.grid['Nx'], self.grid['Ny'], where='frame_now')
+            arg = C.byref(self._frame_struct(spec))
+        else:
+            spec, arg = self._frames_spec, None
+        self._sync_to_device()
+        out = np.empty((1, self._frame_bytes(spec)), dtype=np.uint8)
+        _lib.check(self._lib.gpf_frames_now(self._h, arg, out.ctypes.data_as(C.c_void_p), out.size))
+        return self._frame_dict(spec, {f: v[0] for f, v in self._frame_split(out, spec).items()})
+
+    def _frames_writer(self):
+        """frames.nc of a problem that is not silent, opened when the first batch is collected (or the run ends without one)."""
+        if self._frames_nc is None:
+            from .output import FrameWriter
+            spec, nx, ny = self._frames_spec, self.grid['Nx'], self.grid['Ny']
+            x, y = _frame_axes(spec, nx, ny, self.grid['dx'], self.grid['dy'])
+            self._frames_nc = FrameWriter(os.path.join(self.outdir, 'frames.nc'), spec['fields'], spec['dtype'], x, y,
+                                          _frame_window(spec, nx, ny), spec['stride'], spec['reduce'])
+        return self._frames_nc
+
+    def _close_frames_nc(self):
+        if self._frames_nc is not None:
+            self._frames_nc.close()
+        self._frames_nc = None
+
+    def _collect_frames(self, entries, before):
+        """The records of the stepping call that took the step count from `before` through `entries` (its committed steps): to
+        `frames.nc` unless the problem is silent, and to the series in memory if it keeps them."""
+        if self._frames_every is None:
+            return
+        rec, spec = self._frames_rec, self._frames_spec
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_frames_read(self._h, b[0].ctypes.data_as(C.c_void_p), n, steps, have))
+        had = len(rec.blocks)
+        rec.collect(read, entries, before, [((self._frame_bytes(spec),), np.uint8)])
+        if len(rec.blocks) == had:
+            return
+        n = len(rec.blocks[-1][0])
+        if n and not self.options['silent']:
+            self._frames_writer().append(rec.steps[len(rec.steps) - n:], rec.times[len(rec.times) - n:], self._frame_split(rec.blocks[-1][0], spec))
+        if not self._frames_keep:
+            rec.reset()
+
+    def _write_frames(self):
+        """frames.nc is complete: every batch was appended as it was collected."""
+        self._frames_writer()
+        self._close_frames_nc()
+
+    # -------------------------------------------------------------------------------------
     # field extrema (no reference counterpart; DESIGN.md 3.3g)
     # -------------------------------------------------------------------------------------
     def _extrema_refusal(self):
@@ -1668,6 +1825,19 @@ def _own_lines(input_dict, opts, base_dir):
         raise ValueError("options.lines: options.line_list must list the lines")
 
 
+def _own_frames(input_dict, opts, base_dir):
+    """`options.frames: N` (the stride; 0 or absent: off) and `options.frame_spec: {fields: [rho, p], window: [ix0, ix1, iy0, iy1],
+    stride: [sx, sy], reduce: mean, dtype: f4, capacity: n}` (_frame_spec; the window is checked against the grid, when the input
+    has one)."""
+    grid = input_dict.get('grid') or {}
+    if opts.get('frames') is not None:
+        input_dict['options']['frames'] = _frames_stride(opts['frames'], allow_zero=True)
+    if opts.get('frame_spec') is not None:
+        spec = _frame_spec(opts['frame_spec'], int(grid['Nx']) if 'Nx' in grid else None, int(grid['Ny']) if 'Ny' in grid else None,
+                           where='options.frame_spec')
+        input_dict['options']['frame_spec'] = dict(spec, fields=list(spec['fields']))
+
+
 def _own_init_from(input_dict, opts, base_dir):
     """`options.init_from: path` (a checkpoint to start from, Problem.init_from).  A relative path is relative to the YAML file
     (`base_dir`; a string has none: the working directory)."""
@@ -1680,7 +1850,7 @@ def _own_init_from(input_dict, opts, base_dir):
 
 
 _OWN_KEYS = (_own_checkpoint_freq, _own_probes, _own_integrals, _own_extrema, _own_elastic_series, _own_weighted, _own_statistics,
-             _own_regions, _own_lines, _own_changes, _own_domain_series, _own_init_from)
+             _own_regions, _own_lines, _own_frames, _own_changes, _own_domain_series, _own_init_from)
 
 
 def _keep(keys, input_dict, ymlstring, base_dir=None):
@@ -1709,6 +1879,7 @@ def _keep_weighted(input_dict, ymlstring, base_dir=None): _keep([_own_weighted],
 def _keep_statistics(input_dict, ymlstring): _keep([_own_statistics], input_dict, ymlstring)
 def _keep_regions(input_dict, ymlstring): _keep([_own_regions], input_dict, ymlstring)
 def _keep_lines(input_dict, ymlstring): _keep([_own_lines], input_dict, ymlstring)
+def _keep_frames(input_dict, ymlstring): _keep([_own_frames], input_dict, ymlstring)
 def _keep_changes(input_dict, ymlstring): _keep([_own_changes], input_dict, ymlstring)
 def _keep_domain_series(input_dict, ymlstring): _keep([_own_domain_series], input_dict, ymlstring)
 def _keep_init_from(input_dict, ymlstring, base_dir=None): _keep([_own_init_from], input_dict, ymlstring, base_dir)

@@ -97,6 +97,7 @@ SERIES = (
 )
 # The series added since: behind SERIES in the arming, collecting, writing and refusal order
 SERIES_MORE = (
+    _Row('_frames_every', '_frames_rec', '_collect_frames', '_write_frames', 'frames', 'clear_frames', (8, CUTS), True),
     _Row('_changes_every', '_changes_rec', '_collect_changes', '_write_changes', 'changes', 'clear_changes', (7, CUTS), True),
 )
 ALL_SERIES = SERIES + SERIES_MORE
@@ -116,6 +117,7 @@ def _lines_stride(every, allow_zero=False): return _stride('lines', every, 0 if 
 def _extrema_stride(every, allow_zero=True): return _stride('extrema', every, 0 if allow_zero else 1)
 def _elastic_series_stride(every, allow_zero=True): return _stride('elastic series', every, 0 if allow_zero else 1)
 def _changes_stride(every, allow_zero=True): return _stride('changes', every, 0 if allow_zero else 1)
+def _frames_stride(every, allow_zero=False): return _stride('frames', every, 0 if allow_zero else 1)
 def _statistics_stride(v, key, low): return _stride('statistics', v, low, key)
 
 
@@ -320,3 +322,85 @@ def _statistics_fields(fields):
             not all(isinstance(f, str) and f in _lib.STATS_FIELDS for f in fields) or len(set(fields)) != len(fields):
         raise ValueError(f"statistics: statistics_fields must be a non-empty list of distinct names out of {list(_lib.STATS_FIELDS)}, got {fields!r}")
     return tuple(f for f in _lib.STATS_FIELDS if f in fields)
+
+
+FRAME_SPEC_KEYS = ('fields', 'window', 'stride', 'reduce', 'dtype', 'capacity')
+FRAME_DEFAULT_FIELDS = ('rho', 'jx', 'jy', 'p')
+
+
+def _frame_spec(given=None, nx=None, ny=None, where='frames'):
+    """What set_frames / frame_now / options.frame_spec is given, checked and completed: {fields, window, stride, reduce, dtype,
+    capacity} with `fields` a tuple of distinct names of the nine in the library's order (the record's), `window` a list [ix0, ix1,
+    iy0, iy1] of inclusive 1-based interior indices or None (the whole interior), `stride` [sx, sy] each in 1..64, `reduce` 'sample'
+    or 'mean' -- a mean over blocks of one cell is the cell: 'sample' --, `dtype` 'f4' or 'f8', `capacity` an int >= 1 or None (the
+    default).  ValueError for an unknown key, a bad field name, a window outside the interior (checked against nx, ny where given)
+    or reversed, a stride outside 1..64, an unknown reduce or dtype, a bad capacity.  Host only: no library call."""
+    given = {} if given is None else given
+
+    def bad(msg):
+        return ValueError(f"{where}: {msg}, got {given!r}")
+
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+    def is_list(v, n):
+        return not isinstance(v, (str, bytes, dict)) and hasattr(v, '__len__') and len(v) == n
+    if not isinstance(given, dict) or set(given) - set(FRAME_SPEC_KEYS):
+        raise bad(f"a mapping with the keys {list(FRAME_SPEC_KEYS)} is required")
+    fields = given.get('fields')
+    fields = FRAME_DEFAULT_FIELDS if fields is None else fields
+    if isinstance(fields, (str, bytes, dict)) or not hasattr(fields, '__len__') or len(fields) < 1 or \
+            not all(isinstance(f, str) and f in _lib.FRAME_FIELDS for f in fields) or len(set(fields)) != len(fields):
+        raise bad(f"fields must be a non-empty list of distinct names out of {list(_lib.FRAME_FIELDS)}")
+    window = given.get('window')
+    if window is not None:
+        if not is_list(window, 4) or not all(is_int(v) for v in window):
+            raise bad("window must be four integers [ix0, ix1, iy0, iy1]")
+        window = [int(v) for v in window]
+        if not (1 <= window[0] <= window[1] and 1 <= window[2] <= window[3]) or (nx is not None and window[1] > nx) or \
+                (ny is not None and window[3] > ny):
+            raise bad("window must be ix0 <= ix1 and iy0 <= iy1 inside the interior (inclusive, 1-based)")
+    stride = given.get('stride')
+    stride = (1, 1) if stride is None else stride
+    if not is_list(stride, 2) or not all(is_int(v) and 1 <= v <= _lib.FRAME_MAX_STRIDE for v in stride):
+        raise bad(f"stride must be two integers [sx, sy] within 1..{_lib.FRAME_MAX_STRIDE}")
+    stride = [int(v) for v in stride]
+    reduce = given.get('reduce')
+    reduce = 'sample' if reduce is None else reduce
+    if reduce not in _lib.FRAME_REDUCE:
+        raise bad(f"reduce must be one of {list(_lib.FRAME_REDUCE)}")
+    if stride == [1, 1]:
+        reduce = 'sample'
+    dtype = given.get('dtype')
+    dtype = 'f4' if dtype is None else dtype
+    if dtype not in _lib.FRAME_DTYPES:
+        raise bad(f"dtype must be one of {list(_lib.FRAME_DTYPES)}")
+    capacity = given.get('capacity')
+    if capacity is not None and (not is_int(capacity) or capacity < 1):
+        raise bad("capacity must be an integer >= 1 (None: the default)")
+    return {'fields': tuple(f for f in _lib.FRAME_FIELDS if f in fields), 'window': window, 'stride': stride, 'reduce': reduce,
+            'dtype': dtype, 'capacity': None if capacity is None else int(capacity)}
+
+
+def _frame_window(spec, nx, ny):
+    """(ix0, ix1, iy0, iy1) of a checked spec on an nx x ny interior: its window, or the whole interior."""
+    return tuple(spec['window']) if spec['window'] is not None else (1, nx, 1, ny)
+
+
+def _frame_shape(spec, nx, ny):
+    """(mx, my): the blocks of a checked spec's window along x and y, the last of an axis possibly ragged."""
+    ix0, ix1, iy0, iy1 = _frame_window(spec, nx, ny)
+    sx, sy = spec['stride']
+    return -(-(ix1 - ix0 + 1) // sx), -(-(iy1 - iy0 + 1) // sy)
+
+
+def _frame_axes(spec, nx, ny, dx, dy):
+    """(x (mx,), y (my,)): the cell-centre coordinates of a checked spec's output points -- the first cell's for 'sample', the
+    mean of the block's cell centres (clipped to the window) for 'mean'."""
+    ix0, ix1, iy0, iy1 = _frame_window(spec, nx, ny)
+    out = []
+    for first, last, s, d in ((ix0, ix1, spec['stride'][0], dx), (iy0, iy1, spec['stride'][1], dy)):
+        lo = np.arange(first, last + 1, s)
+        hi = np.minimum(lo + s - 1, last) if spec['reduce'] == 'mean' else lo
+        out.append((0.5 * (lo + hi) - 0.5) * d)
+    return out[0], out[1]

@@ -582,6 +582,14 @@ class SlabProblem:
         """Line profiles are recorded on unsliced problems only."""
         raise NotImplementedError("lines: not available on a SlabProblem")
 
+    def set_frames(self, *args, **kwargs):
+        """Reduced frames are recorded on unsliced problems only (`options.frames` is stored and never armed here)."""
+        raise NotImplementedError("frames: not available on a SlabProblem")
+
+    def frame_now(self, *args, **kwargs):
+        """Reduced frames are taken on unsliced problems only."""
+        raise NotImplementedError("frames: not available on a SlabProblem")
+
     def set_extrema(self, *args, **kwargs):
         """Field extrema are recorded on unsliced problems only."""
         raise NotImplementedError("extrema: not available on a SlabProblem (the whole domain's: set_domain_series / domain_field_extrema)")
@@ -1105,6 +1113,7 @@ class SlabProblem:
         if self._writer_problem is None:
             from .problem import Problem
             d = deepcopy(self.input)
+            d['options'].pop('frames', None)        # stored, never armed: the writer steps nothing, and frames are not recorded on slabs
             # with surrogates the writer shares this rank's database and mirrors its models (same data, same
             # hyper-parameters), so the closures of a frame are the surrogates' means as in a serial run
             self._writer_problem = Problem(d['options'], d['grid'], d['numerics'], d['properties'], d['geometry'],

@@ -903,6 +903,69 @@ int gpf_lines_now(gpf_handle* h, int K, const gpf_line* lines /* [K], or NULL */
  * series: the one rule of the gpf_*_time diagnostics (before the point probes). */
 int gpf_lines_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- reduced frames (no reference counterpart: the reference's pictures of a run are drawn from the frames of sol.nc) ------- */
+/* A written frame is every derived field on the whole ghosted grid in double precision, through the host.  A picture or a movie
+ * needs few fields, a window, a coarser lattice and single precision: these entry points record exactly that of the COMMITTED state
+ * on the device, in one read-only pass.  A frame is, for each selected field, one (mx, my) array:
+ *   fields   a mask of the line profiles' nine, bit f = field f in their order and with their definitions: rho, jx, jy (the
+ *            state's own bits), p (eos_pressure of the committed density, bit for bit a probe's p), h (plane 0 of the gap), tau_xz_bot,
+ *            tau_yz_bot, tau_xz_top, tau_yz_top (lower[4], lower[3], upper[4], upper[3] of cell_fields).  The gap and the slip length
+ *            are read only if h or a stress is selected, cell_fields is evaluated only if a stress is: a rho / jx / jy / p frame reads
+ *            24 bytes per window cell.
+ *   window   ix0..ix1, iy0..iy1 inclusive, 1-based interior indices (four zeros: the whole interior).  Ghost cells never enter.
+ *   stride   sx, sy in 1..64: the window is cut into blocks of sx x sy cells from its corner (ix0, iy0); mx = ceil((ix1 - ix0 + 1)
+ *            / sx), my likewise; the last block of an axis may be ragged.  At most 65535 output rows.
+ *   reduce   GPF_FRAME_SAMPLE: the value of the block's first cell (ix0 + a sx, iy0 + b sy), no arithmetic (a -0.0 stays a -0.0).
+ *            GPF_FRAME_MEAN: the arithmetic mean over the block's cells inside the window, each field on its own, in this order
+ *            (csrc/frames.hpp, so that a loop on the host can restate it): per column of the block a sum from +0.0 over the rows in
+ *            ascending ix; those sums added from +0.0 in ascending iy; one division by (double)(rows * cols).  mean with sx = sy = 1
+ *            is stored, and reported by gpf_frames_shape's callers, as sample.
+ *   dtype    GPF_FRAME_F8 doubles, GPF_FRAME_F4 the double result converted once, round to nearest even.
+ * Record layout: [field in mask order][a = 0..mx-1][b = 0..my-1], values of the dtype, no padding.
+ * A record is a pure function of the state and the frame: no atomics, no arrival order, the same bits for every batch length,
+ * stride, capacity and kernel that stepped.  Recording only reads.
+ *   gpf_frames_set    arms recording after every committed step whose new step count is a multiple of `every` (>= 1) with the frame
+ *                     (copied), and starts with empty records.  `capacity`: the records the device buffer holds; 0: as many as fit
+ *                     64 MiB (GPF_FRAMES_MB in the environment: another number of MiB), at least 1; never more than ceil(4096 /
+ *                     every).  GPF_ERR_INVALID for every < 1, capacity < 0, a null spec, an empty mask or bits beyond the nine, a
+ *                     window outside the interior or reversed, a stride outside 1..64, an unknown reduce or dtype, surrogate
+ *                     closures, shear thinning or an elastic gap; GPF_ERR_STATE on a slab and while a stage-wise step is open.
+ *   gpf_frames_clear  disarms and frees the buffer.
+ *   gpf_frames_read   the records of the LAST gpf_step call, out [record][bytes of a record], and the step count of each in
+ *                     steps_out (either may be NULL); *n_records how many the call left, min(*n_records, capacity_records) are
+ *                     copied.  A batch that stopped on the device leaves the records of the steps that ran; a step that was rolled
+ *                     back as invalid leaves none.  GPF_ERR_STATE unless armed.
+ *   gpf_frames_now    the same record for the current committed state, by the same kernels: of the armed frame (spec NULL), or of
+ *                     the frame given, with a buffer of this call's own and nothing armed or disarmed.  `bytes`: what `out` has room
+ *                     for (>= a record's).  GPF_ERR_STATE on an invalid run state, and without a spec unless armed.
+ *   gpf_frames_shape  mx, my and the bytes of a record of `spec` on this handle's grid (each pointer may be NULL); the checks of
+ *                     gpf_frames_set on the spec, no device call.
+ * Where they are written: k_frame_sample or k_frame_mean (csrc/frame_kernels.hip), one launch behind the step's, told the step count
+ * the step produces if it commits and writing only if the device's run state shows that count and a valid state.  The buffer is
+ * bounded, so gpf_step never puts more than `capacity` records into one batch: with frames armed a batch is at most capacity * every
+ * - steps since the last record; a call in several batches is bitwise the call in one.  On grids small enough for k_small_steps the
+ * batch is also cut at the recorded steps, like the lines'.  gpf_close_step, gpf_step_timed and the slab calls record nothing. */
+#define GPF_FRAME_SAMPLE 0
+#define GPF_FRAME_MEAN 1
+#define GPF_FRAME_F8 0
+#define GPF_FRAME_F4 1
+typedef struct {
+    int32_t fields;             /* bit f: field f of rho jx jy p h tau_xz_bot tau_yz_bot tau_xz_top tau_yz_top */
+    int32_t ix0, ix1, iy0, iy1; /* the window, inclusive; four zeros: the whole interior                       */
+    int32_t sx, sy;             /* the block, 1..64 each                                                       */
+    int32_t reduce;             /* GPF_FRAME_SAMPLE / GPF_FRAME_MEAN                                           */
+    int32_t dtype;              /* GPF_FRAME_F8 / GPF_FRAME_F4                                                 */
+} gpf_frame_spec;
+int gpf_frames_set(gpf_handle* h, int64_t every, const gpf_frame_spec* spec, int64_t capacity);
+int gpf_frames_clear(gpf_handle* h);
+int gpf_frames_read(gpf_handle* h, void* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_frames_now(gpf_handle* h, const gpf_frame_spec* spec /* or NULL */, void* out, int64_t bytes);
+int gpf_frames_shape(gpf_handle* h, const gpf_frame_spec* spec, int32_t* mx, int32_t* my, int64_t* record_bytes);
+/* Diagnostic: n steps (1..4096) enqueued as gpf_step does, *ms from the first launch to the last on the handle's stream, with
+ * mode 0 no recording, 1 recording at the armed stride, n no more than one batch may hold (tools/frames_time.py).  The other
+ * series: the one rule of the gpf_*_time diagnostics (before the point probes). */
+int gpf_frames_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* ---- ensembles (no reference counterpart: the reference runs a parameter study as one process per problem) ---------------- */
 /* Many small problems advanced by ONE launch per kernel instantiation: workgroup m of k_small_ensemble runs, on member m's own
  * buffers, the very body that k_small_steps runs for a handle alone (csrc/small_kernel.hip), so a member's field, run state
