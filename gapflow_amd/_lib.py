@@ -253,6 +253,12 @@ SIGNATURES = {
     'gpf_ensemble_integrals_set': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
     'gpf_ensemble_integrals_clear': (C.c_int, [C.c_void_p]),
     'gpf_ensemble_integrals_read': (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_ensemble_extrema_set': (C.c_int, [C.c_void_p, C.c_int64]),
+    'gpf_ensemble_extrema_clear': (C.c_int, [C.c_void_p]),
+    'gpf_ensemble_extrema_read': (C.c_int, [C.c_void_p, C.c_int, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_ensemble_probes_set': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
+    'gpf_ensemble_probes_clear': (C.c_int, [C.c_void_p]),
+    'gpf_ensemble_probes_read': (C.c_int, [C.c_void_p, C.c_int, _DP, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_resample': (C.c_int, [C.c_void_p, C.c_void_p]),
     'gpf_resample_time': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _DP]),
 }

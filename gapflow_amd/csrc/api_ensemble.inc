@@ -36,6 +36,32 @@ struct gpf_ensemble {
         std::vector<std::vector<long long>> steps;
         int nrec(int i) const { return FILM_NSUM + args[i].nsx + args[i].nsy; }
     } film;
+    // field-extrema series, the same way: stride (0: not armed), `cap` records per member in ONE device allocation `rec` -- the
+    // values of all members ([m][cap][7] doubles), then their cells ([m][cap][7][2] ints) --, the members' ExtremaArgs in device
+    // memory ([m]; no row scratch: both kernels fold inside the workgroup), the records of the last gpf_ensemble_step on the host
+    struct Extrema {
+        long long every = 0, cap = 0;
+        char* rec = nullptr;
+        ExtremaArgs* dev = nullptr;
+        std::vector<std::vector<double>> host;
+        std::vector<std::vector<int32_t>> cells;
+        std::vector<std::vector<long long>> steps;
+        double* val(int i) const { return (double*)rec + (size_t)i * cap * EXTREMA_NQ; }
+        int* cell(size_t m, int i) const { return (int*)((double*)rec + m * cap * EXTREMA_NQ) + (size_t)i * cap * 2 * EXTREMA_NQ; }
+    } ext;
+    // point probes: per member its count (empty: not armed) and where its records start in `out` (ONE device allocation, log_cap
+    // records of n[i] x nv doubles per member: a record per committed step); `dev`: the members' ProbeArgs ([m]) and behind them
+    // everyone's cells, in device memory; the records of the last gpf_ensemble_step on the host and the step count of the first
+    struct Probes {
+        std::vector<int> n;
+        int nv = 0;
+        std::vector<size_t> off;
+        double* out = nullptr;
+        ProbeArgs* dev = nullptr;
+        std::vector<std::vector<double>> host;
+        std::vector<long long> first;
+        bool armed() const { return !n.empty(); }
+    } probes;
     size_t args_off() const { return members.size() * sizeof(StepState); }
     size_t bytes() const { return args_off() + members.size() * (sizeof(SmallArgs) + sizeof(Phys) + sizeof(double*)); }
 };
@@ -122,6 +148,10 @@ extern "C" int gpf_ensemble_destroy(gpf_ensemble* e) {
     hipStreamSynchronize(e->members[0]->stream);        // a launch that records into the buffers below may still be queued
     if (e->film.rec) hipFree(e->film.rec);
     if (e->film.dev) hipFree(e->film.dev);
+    if (e->ext.rec) hipFree(e->ext.rec);
+    if (e->ext.dev) hipFree(e->ext.dev);
+    if (e->probes.out) hipFree(e->probes.out);
+    if (e->probes.dev) hipFree(e->probes.dev);
     if (e->dev) hipFree(e->dev);
     if (e->ws) hipFree(e->ws);
     if (e->host) hipHostFree(e->host);
@@ -154,6 +184,8 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         e->entries[i] = 0;
         if (n[i] > 0) slots.push_back(i);
         if (e->film.every) { e->film.host[i].clear(); e->film.steps[i].clear(); }      // the records of the call before go
+        if (e->ext.every) { e->ext.host[i].clear(); e->ext.cells[i].clear(); e->ext.steps[i].clear(); }
+        if (e->probes.armed()) { e->probes.host[i].clear(); e->probes.first[i] = e->members[i]->host_step + 1; }
     }
     std::stable_sort(slots.begin(), slots.end(), [&](int a, int b) { return key(a) < key(b); });
     const int nslots = (int)slots.size();
@@ -172,7 +204,9 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         SmallArgs& a = ha[s];
         a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
         a.log = h->log; a.log_base = h->host_step; a.log_cap = h->log_cap; a.L = h->L; a.E = h->E;
-        a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop; a.probe = nullptr; a.extrema = nullptr;
+        a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop;
+        a.probe = e->probes.armed() ? e->probes.dev + slots[s] : nullptr;
+        a.extrema = e->ext.every ? e->ext.dev + slots[s] : nullptr;
         a.film = e->film.every ? e->film.dev + slots[s] : nullptr;
         hp[s] = h->P;
         hw[s] = e->tier[slots[s]] == GPF_ENSEMBLE_TIER_WORKSPACE ? (double*)(e->ws + e->ws_off[slots[s]]) : nullptr;
@@ -238,6 +272,23 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
                 e->film.host[i].swap(got);
                 for (long long k = 1; k <= cnt; ++k) e->film.steps[i].push_back((h->host_step / e->film.every + k) * e->film.every);
             }
+        }
+        // its extrema records likewise (values and cells), and a probe record per committed step
+        const long long ecnt = e->ext.every ? series_count(h->host_step, ran, e->ext.every) : 0;
+        if (ecnt > 0) {
+            std::vector<double> val((size_t)ecnt * EXTREMA_NQ);
+            std::vector<int32_t> cell((size_t)ecnt * 2 * EXTREMA_NQ);
+            if (hip_ok(hipMemcpy(val.data(), e->ext.val(i), val.size() * sizeof(double), hipMemcpyDeviceToHost), "extrema record copy") &&
+                hip_ok(hipMemcpy(cell.data(), e->ext.cell((size_t)m, i), cell.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "extrema record copy")) {
+                e->ext.host[i].swap(val);
+                e->ext.cells[i].swap(cell);
+                for (long long k = 1; k <= ecnt; ++k) e->ext.steps[i].push_back((h->host_step / e->ext.every + k) * e->ext.every);
+            }
+        }
+        if (e->probes.armed() && ran > 0) {
+            std::vector<double> got((size_t)ran * e->probes.n[i] * e->probes.nv);
+            if (hip_ok(hipMemcpy(got.data(), e->probes.out + e->probes.off[i], got.size() * sizeof(double), hipMemcpyDeviceToHost), "probe record copy"))
+                e->probes.host[i].swap(got);
         }
         h->host_step = st.step; h->next_step = st.step;
         prev_state_after(h, ran >= 1 && !st.invalid);
@@ -363,5 +414,175 @@ extern "C" int gpf_ensemble_integrals_read(gpf_ensemble* e, int member, double* 
     *n_records = have;
     if (out && take > 0) std::memcpy(out, e->film.host[member].data(), (size_t)take * nrec * sizeof(double));
     for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = e->film.steps[member][(size_t)k];
+    return GPF_OK;
+}
+
+// ---- the ensemble's extrema series (the record of gpf_extrema_*) and point probes (that of gpf_probes_*) -------------------------
+// Both kernels write them inside the batch, behind each commit: k_small_ensemble through extrema_record_block / probe_record_block
+// on its LDS planes -- in every bit what the member's solo batch records --, k_mid_ensemble through extrema_record_wide /
+// probe_record_block on its workspace planes.
+
+static int ensemble_extrema_release(gpf_ensemble* e) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->members[0]->stream));       // a recording launch may still be queued
+    if (e->ext.rec) HIP_TRY(hipFree(e->ext.rec));
+    e->ext.rec = nullptr;
+    if (e->ext.dev) HIP_TRY(hipFree(e->ext.dev));
+    e->ext.dev = nullptr;
+    e->ext = gpf_ensemble::Extrema();
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_extrema_set(gpf_ensemble* e, int64_t every) {
+    if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_set: null argument");
+    if (every < 1) return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_set: every >= 1 required (gpf_ensemble_extrema_clear disarms), got " + std::to_string(every));
+    const int m = (int)e->members.size();
+    for (int i = 0; i < m; ++i) GPF_TRY(extrema_refusal(e->members[i], "gpf_ensemble_extrema_set: member " + std::to_string(i)));
+    HIP_TRY(hipSetDevice(e->device));
+    gpf_ensemble::Extrema x;
+    x.every = every;
+    x.cap = LOG_CAPACITY / every + 1;               // series_count(base, ran, every) <= ran / every + 1
+    x.host.resize(m); x.cells.resize(m); x.steps.resize(m);
+    const size_t per = (size_t)x.cap * EXTREMA_NQ;
+    hipError_t err = hipMalloc(&x.rec, (size_t)m * per * (sizeof(double) + 2 * sizeof(int)));
+    if (err == hipSuccess) err = hipMalloc(&x.dev, (size_t)m * sizeof(ExtremaArgs));
+    std::vector<ExtremaArgs> args(m);
+    for (int i = 0; i < m && err == hipSuccess; ++i) {
+        args[i].val = x.val(i); args[i].cell = x.cell((size_t)m, i);
+        args[i].row_val = nullptr; args[i].row_iy = nullptr;        // k_extrema_partial's: no launch of it here
+        args[i].every = every; args[i].cap = x.cap;
+    }
+    if (err == hipSuccess) err = hipMemcpy(x.dev, args.data(), (size_t)m * sizeof(ExtremaArgs), hipMemcpyHostToDevice);
+    if (err != hipSuccess) {                        // the ensemble stays as it was
+        if (x.rec) (void)hipFree(x.rec);
+        if (x.dev) (void)hipFree(x.dev);
+        return fail(GPF_ERR_HIP, std::string("gpf_ensemble_extrema_set: ") + hipGetErrorString(err));
+    }
+    const int rc = ensemble_extrema_release(e);
+    if (rc != GPF_OK) {
+        (void)hipFree(x.rec); (void)hipFree(x.dev);
+        return rc;
+    }
+    e->ext = std::move(x);
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_extrema_clear(gpf_ensemble* e) {
+    if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_clear: null argument");
+    return ensemble_extrema_release(e);
+}
+
+extern "C" int gpf_ensemble_extrema_read(gpf_ensemble* e, int member, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out,
+                                         int64_t* n_records) {
+    if (!e || !n_records) return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_read: null argument (e and n_records are required)");
+    if (member < 0 || member >= (int)e->members.size())
+        return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_read: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    if (!e->ext.every) return fail(GPF_ERR_STATE, "gpf_ensemble_extrema_read: no extrema are armed (gpf_ensemble_extrema_set)");
+    const int64_t have = (int64_t)e->ext.steps[member].size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
+    *n_records = have;
+    if (values && take > 0) std::memcpy(values, e->ext.host[member].data(), (size_t)take * EXTREMA_NQ * sizeof(double));
+    if (cells && take > 0) std::memcpy(cells, e->ext.cells[member].data(), (size_t)take * 2 * EXTREMA_NQ * sizeof(int32_t));
+    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = e->ext.steps[member][(size_t)k];
+    return GPF_OK;
+}
+
+static int ensemble_probes_release(gpf_ensemble* e) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->members[0]->stream));       // a recording launch may still be queued
+    if (e->probes.out) HIP_TRY(hipFree(e->probes.out));
+    e->probes.out = nullptr;
+    if (e->probes.dev) HIP_TRY(hipFree(e->probes.dev));
+    e->probes.dev = nullptr;
+    e->probes = gpf_ensemble::Probes();
+    return GPF_OK;
+}
+
+// The most bytes the probe records of an ensemble may take on the device: GPF_ENSEMBLE_PROBES_MB (MiB, read at every set), 256
+static size_t ensemble_probes_budget() {
+    const char* s = std::getenv("GPF_ENSEMBLE_PROBES_MB");
+    const long long mb = s ? std::atoll(s) : 0;
+    return (size_t)(mb > 0 ? mb : 256) << 20;
+}
+
+extern "C" int gpf_ensemble_probes_set(gpf_ensemble* e, int per_member, const int32_t* nprobe, const int32_t* cells, int with_pressure) {
+    if (!e || !nprobe || !cells) return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_set: null argument");
+    const int m = (int)e->members.size();
+    gpf_ensemble::Probes p;
+    p.n.resize(m); p.off.resize(m); p.host.resize(m); p.first.assign(m, 0);
+    p.nv = with_pressure ? 4 : 3;
+    std::vector<size_t> first_cell(m);              // where member i's cells start in `cells`, in cells
+    size_t ncells = 0, total = 0;
+    for (int i = 0; i < m; ++i) {
+        const gpf_handle* h = e->members[i];
+        const std::string who = "gpf_ensemble_probes_set: member " + std::to_string(i);
+        GPF_TRY(probes_refusal(h, who));
+        if (with_pressure) GPF_TRY(probes_pressure_refusal(h, who));
+        const int n = nprobe[per_member ? i : 0];
+        if (n < 1) return fail(GPF_ERR_INVALID, who + ": n >= 1 cells required (gpf_ensemble_probes_clear removes them), got " + std::to_string(n));
+        if (n > PROBE_MAX)
+            return fail(GPF_ERR_INVALID, who + ": probe " + std::to_string(PROBE_MAX) + " is one too many (" + std::to_string(n) + " given, at most " +
+                                         std::to_string(PROBE_MAX) + " per member)");
+        first_cell[i] = per_member ? ncells : 0;
+        const int32_t* c = cells + 2 * first_cell[i];
+        for (int k = 0; k < n; ++k)
+            if (c[2 * k] < 0 || c[2 * k] > h->L.Nx + 1 || c[2 * k + 1] < 0 || c[2 * k + 1] > h->L.Ny + 1)
+                return fail(GPF_ERR_INVALID, who + ": probe " + std::to_string(k) + " at cell (" + std::to_string(c[2 * k]) + ", " + std::to_string(c[2 * k + 1]) +
+                                             ") lies outside 0.." + std::to_string(h->L.Nx + 1) + " x 0.." + std::to_string(h->L.Ny + 1));
+        p.n[i] = n;
+        p.off[i] = total;
+        ncells = per_member ? ncells + (size_t)n : (size_t)n;
+        total += (size_t)h->log_cap * (size_t)n * (size_t)p.nv;     // a record per step of the longest call
+    }
+    const size_t need = total * sizeof(double), budget = ensemble_probes_budget();
+    if (need > budget)
+        return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_set: the records of one call need " + std::to_string(need) + " bytes of device memory (" +
+                                     std::to_string(LOG_CAPACITY) + " steps x probes x values x 8 per member), more than the budget of " +
+                                     std::to_string(budget) + " bytes (GPF_ENSEMBLE_PROBES_MB, in MiB; default 256)");
+    HIP_TRY(hipSetDevice(e->device));
+    // ProbeArgs[m], then the cells: one small allocation, one copy
+    std::vector<char> image((size_t)m * sizeof(ProbeArgs) + ncells * 2 * sizeof(int));
+    hipError_t err = hipMalloc(&p.out, need);
+    if (err == hipSuccess) err = hipMalloc(&p.dev, image.size());
+    if (err == hipSuccess) {
+        const int* dev_cells = (const int*)((char*)p.dev + (size_t)m * sizeof(ProbeArgs));
+        ProbeArgs* args = (ProbeArgs*)image.data();
+        for (int i = 0; i < m; ++i) {
+            args[i].cells = dev_cells + 2 * first_cell[i];
+            args[i].out = p.out + p.off[i];
+            args[i].nprobe = p.n[i]; args[i].nv = p.nv;
+            args[i].base = 0; args[i].cap = e->members[i]->log_cap;     // (the one-workgroup kernels take both from their own arguments)
+        }
+        std::memcpy(image.data() + (size_t)m * sizeof(ProbeArgs), cells, ncells * 2 * sizeof(int));
+        err = hipMemcpy(p.dev, image.data(), image.size(), hipMemcpyHostToDevice);
+    }
+    if (err != hipSuccess) {                        // the ensemble stays as it was
+        if (p.out) (void)hipFree(p.out);
+        if (p.dev) (void)hipFree(p.dev);
+        return fail(GPF_ERR_HIP, std::string("gpf_ensemble_probes_set: ") + hipGetErrorString(err));
+    }
+    const int rc = ensemble_probes_release(e);
+    if (rc != GPF_OK) {
+        (void)hipFree(p.out); (void)hipFree(p.dev);
+        return rc;
+    }
+    e->probes = std::move(p);
+    return GPF_OK;
+}
+
+extern "C" int gpf_ensemble_probes_clear(gpf_ensemble* e) {
+    if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_clear: null argument");
+    return ensemble_probes_release(e);
+}
+
+extern "C" int gpf_ensemble_probes_read(gpf_ensemble* e, int member, double* out, int64_t capacity_records, int64_t* first_step, int64_t* n_records) {
+    if (!e || !n_records) return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_read: null argument (e and n_records are required)");
+    if (member < 0 || member >= (int)e->members.size())
+        return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_read: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    if (!e->probes.armed()) return fail(GPF_ERR_STATE, "gpf_ensemble_probes_read: no probes are set (gpf_ensemble_probes_set)");
+    const size_t per = (size_t)e->probes.n[member] * e->probes.nv;
+    const int64_t have = (int64_t)(e->probes.host[member].size() / per), take = std::max<int64_t>(0, std::min(have, capacity_records));
+    *n_records = have;
+    if (first_step) *first_step = e->probes.first[member];
+    if (out && take > 0) std::memcpy(out, e->probes.host[member].data(), (size_t)take * per * sizeof(double));
     return GPF_OK;
 }

@@ -62,10 +62,22 @@ static int probes_release(gpf_handle* h) {
     return GPF_OK;
 }
 
+// The cases the records do not cover (gpf_probes_set's and, per member, gpf_ensemble_probes_set's), and the one a record with p
+// does not
+static int probes_refusal(const gpf_handle* h, const std::string& who) {
+    if (h->E.halo[0] || h->E.halo[1]) return fail(GPF_ERR_STATE, who + ": this handle is a slab; probes are not available on slabs");
+    if (h->step_open) return fail(GPF_ERR_STATE, who + ": a stage-wise step is open; close it first");
+    return GPF_OK;
+}
+
+static int probes_pressure_refusal(const gpf_handle* h, const std::string& who) {
+    if (h->gp[0].set) return fail(GPF_ERR_INVALID, who + ": no EOS pressure to record, this handle's pressure comes from a surrogate");
+    return GPF_OK;
+}
+
 extern "C" int gpf_probes_set(gpf_handle* h, int n, const int32_t* ix, const int32_t* iy, int with_pressure) {
     if (!h) return fail(GPF_ERR_INVALID, "null handle");
-    if (h->E.halo[0] || h->E.halo[1]) return fail(GPF_ERR_STATE, "gpf_probes_set: this handle is a slab; probes are not available on slabs");
-    if (h->step_open) return fail(GPF_ERR_STATE, "gpf_probes_set: a stage-wise step is open; close it first");
+    GPF_TRY(probes_refusal(h, "gpf_probes_set"));
     if (n < 1 || !ix || !iy) return fail(GPF_ERR_INVALID, "gpf_probes_set: n >= 1 cells required (gpf_probes_clear removes them)");
     if (n > PROBE_MAX)
         return fail(GPF_ERR_INVALID, "gpf_probes_set: probe " + std::to_string(PROBE_MAX) + " is one too many (" + std::to_string(n) +
@@ -78,8 +90,7 @@ extern "C" int gpf_probes_set(gpf_handle* h, int n, const int32_t* ix, const int
                                          std::to_string(h->L.Ny + 1));
         cells[2 * p] = ix[p]; cells[2 * p + 1] = iy[p];
     }
-    if (with_pressure && h->gp[0].set)
-        return fail(GPF_ERR_INVALID, "gpf_probes_set: probe 0: no EOS pressure to record, this handle's pressure comes from a surrogate");
+    if (with_pressure) GPF_TRY(probes_pressure_refusal(h, "gpf_probes_set: probe 0"));
     GPF_TRY(series_disarm(h, SERIES[S_PROBES]));
     HIP_TRY(hipMalloc(&h->probes.cells, cells.size() * sizeof(int)));
     HIP_TRY(hipMemcpy(h->probes.cells, cells.data(), cells.size() * sizeof(int), hipMemcpyHostToDevice));

@@ -13,6 +13,8 @@
 //   k_extrema_partial + k_extrema_fold   behind every launch-per-step step, guarded by the device's run state like k_probe_record
 //   extrema_record_block                 inside k_small_steps, after commit_step, from the field the workgroup holds in LDS
 //                                        (one wave per quantity)
+//   extrema_record_wide                  inside k_mid_ensemble, after commit_step, from the workspace planes in device memory
+//                                        (the whole block walks the interior once)
 // k_extrema_partial runs one 256-thread workgroup per interior row; thread t owns the column pairs (1 + 2k, 2 + 2k) for
 // k = t, t + 256, ..., fetched with one 16-byte load per plane where the buffers allow it (series_wide_ok) and with 8-byte loads
 // otherwise; the ghost column an odd Ny reaches is loaded and never compared.  It reads 4 planes (rho, jx, jy, h: 32 B per
@@ -189,6 +191,34 @@ __device__ __forceinline__ void extrema_record_block(const ExtremaArgs& x, const
         x.cell[(slot * EXTREMA_NQ + k) * 2] = bx;
         x.cell[(slot * EXTREMA_NQ + k) * 2 + 1] = by;
     }
+}
+
+// The same record from the dense workspace planes of k_mid_ensemble (mid_kernel.hip), where a member has up to 126 x 126
+// interior cells: one wave per quantity would leave each lane some 250 cells, a division per cell and seven walks, against a
+// step whose passes give a thread about 32 cells.  So here the WHOLE block (blockDim.x threads, a multiple of 64, at most 512)
+// walks the interior once -- thread t takes the interior cells t, t + blockDim.x, ... in row-major order, a MidCursor of width
+// Ny in place of a division per cell --, every thread keeps all seven candidates (ExtAcc::cell: the expressions of
+// k_extrema_partial, so p, u_max and v_max carry the same bits), and extrema_block_first folds them: lanes, then the waves'
+// firsts in `sm` (one ExtAcc per wave).  A thread without a cell holds none(), which every cell comes before.  The order is
+// total, so the walk's shape does not show in the record.
+// Block-uniform; reads only.  The caller has a workgroup barrier between the stores that made q and this call (the planes are
+// in device memory: the barrier is their release / acquire), and one between two calls (`sm` is used again).
+template <int EOS>
+__device__ __forceinline__ void extrema_record_wide(const ExtremaArgs& x, const double* q, const double* h, int Nx, int Ny, int nc, int w,
+                                                    long long slot, const Phys& P, ExtAcc* sm) {
+    if (slot < 0 || slot >= x.cap) return;              // block-uniform
+    const int ncell = Nx * Ny, nt = blockDim.x;
+    ExtAcc a;
+    a.none();
+    MidCursor k(threadIdx.x, nt, Ny);
+    for (int t = threadIdx.x; t < ncell; t += nt, k.next()) {
+        const int ix = 1 + k.ix, iy = 1 + k.iy;
+        const int c = ix * w + iy;
+        const double rho = q[c];
+        a.cell(eos_pressure<EOS>(rho, P), rho, q[nc + c], q[2 * nc + c], h[c], ix, iy);
+    }
+    const ExtAcc r = extrema_block_first(a, sm, nt);
+    if (threadIdx.x == 0) extrema_store(x, slot, r);
 }
 
 }  // namespace gpf

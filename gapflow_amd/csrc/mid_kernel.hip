@@ -19,26 +19,21 @@
 
 namespace gpf {
 
-// cell index t -> (ix, iy) for the cells one thread visits: t = tid, tid + 512, ... without a division per cell
-struct MidCursor {
-    int ix, iy, dq, dr, w;
-    __device__ __forceinline__ MidCursor(int tid, int nt, int w_) : ix(tid / w_), iy(tid % w_), dq(nt / w_), dr(nt % w_), w(w_) {}
-    __device__ __forceinline__ void next() {
-        ix += dq; iy += dr;
-        if (iy >= w) { iy -= w; ix += 1; }
-    }
-};
-
 // The whole batch of one member on one workgroup of 512 threads.  The workgroup's only stores to global memory go to its own
 // workspace `ws`, a.qa, a.qb, a.st, a.log and the film records (a.film: film_record_block, whose row vectors pass through the
-// workspace's flux planes under the barriers' release / acquire like everything else here).  Probes and extrema are not recorded
-// here (gpf_ensemble_create refuses members that have them armed).  Returns the run state the batch ended on (in LDS; thread 0 alone may read it without a barrier).
+// workspace's flux planes under the barriers' release / acquire like everything else here), the probe records (a.probe:
+// probe_record_block) and the extrema records (a.extrema: extrema_record_wide) -- the ensemble's own series, in slots it owns; a
+// member with a series armed on itself is still refused by gpf_ensemble_create.  All three are written behind the commit and
+// only read the state: the committed field q0 was stored to device memory by other threads than those that read it here, and
+// what makes those stores visible is the workgroup barrier behind commit_step (with the one that ends ghosts(q2) before it).
+// Returns the run state the batch ended on (in LDS; thread 0 alone may read it without a barrier).
 template <int EOS, bool HAS_LS>
 __device__ __forceinline__ const StepState* mid_steps_body(const SmallArgs& a, const Phys& P, double* ws) {
     __shared__ Acc sm[16];
     __shared__ int sh_flags[2];
     __shared__ StepState sst;                       // the run state stays on-chip for the whole batch
     __shared__ double film_sm[4][FILM_NV];          // film_record_block's wave staging
+    __shared__ ExtAcc ext_sm[MID_THREADS / 64];     // extrema_record_wide's: one candidate set per wave
     const Layout& G = a.L;                          // layout of the member's own planes
     const int w = G.Ny + 2, nc = (G.Nx + 2) * w;
     Layout D;                                       // dense layout of the workspace planes
@@ -94,7 +89,8 @@ __device__ __forceinline__ const StepState* mid_steps_body(const SmallArgs& a, c
     };
 
     int committed = 0;                              // steps this launch has committed (block-uniform)
-    SeriesCursor film;
+    SeriesCursor ext, film;
+    if (a.extrema) ext.begin(a.extrema->every, st->step, a.log_base);
     if (a.film) film.begin(a.film->every, st->step, a.log_base);
     for (int step = 0; step < a.nsteps; ++step) {
         if (st->invalid != 0 || (a.honor_stop && (st->converged || st->step >= st->max_it))) break;     // block-uniform
@@ -153,6 +149,17 @@ __device__ __forceinline__ const StepState* mid_steps_body(const SmallArgs& a, c
         if (sh_flags[1]) break;                     // rolled back: q0 still holds the last valid state
         double* tmp = q0; q0 = q2; q2 = tmp;        // the averaged field is the current one now, q2 the state before this step
         committed += 1;
+        // the records: block-uniform, reads of q0 and T only, behind the barrier above (q0 is not written again before the
+        // commit after next; ext_sm not before the next record, a step's barriers later)
+        if (a.probe) probe_record_block<EOS>(*a.probe, q0, nc, w, st->step - 1 - a.log_base, a.log_cap, P);
+        if (a.extrema && ext.due(st->step)) {           // the arguments are fetched when a record is due, as the film's
+#ifdef GPF_MID_EXTREMA_PER_WAVE                         // diagnostic build (tools/ensemble_series_time.py): the LDS tier's one wave per quantity
+            extrema_record_block<EOS>(*a.extrema, q0, T, D.Nx, D.Ny, nc, w, ext.slot, P);
+#else
+            extrema_record_wide<EOS>(*a.extrema, q0, T, D.Nx, D.Ny, nc, w, ext.slot, P, ext_sm);
+#endif
+            ext.advance();
+        }
         if (a.film && film.due(st->step)) {             // block-uniform; F is free until the next closure pass
             film_record_block<EOS>(a.film, q0, T, F, film_sm, D.Nx, D.Ny, nc, w, film.slot, P);
             film.advance();

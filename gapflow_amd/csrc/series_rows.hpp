@@ -144,4 +144,15 @@ struct SeriesCursor {
     __device__ __forceinline__ void advance() { next += every; slot += 1; }
 };
 
+// cell index t -> (ix, iy) in rows of w cells for the cells one thread of nt visits: t = tid, tid + nt, ... without a division per
+// cell (mid_kernel.hip walks its planes with it, extrema_kernels.hip: extrema_record_wide the interior)
+struct MidCursor {
+    int ix, iy, dq, dr, w;
+    __device__ __forceinline__ MidCursor(int tid, int nt, int w_) : ix(tid / w_), iy(tid % w_), dq(nt / w_), dr(nt % w_), w(w_) {}
+    __device__ __forceinline__ void next() {
+        ix += dq; iy += dr;
+        if (iy >= w) { iy -= w; ix += 1; }
+    }
+};
+
 }  // namespace gpf

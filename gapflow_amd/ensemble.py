@@ -4,9 +4,12 @@ process per problem).  DESIGN.md 3.2c.
 
     ens = Ensemble.sweep("journal1d.yaml", {'geometry.eps': [0.5, 0.7, 0.9], 'geometry.U': [0.05, 0.1]})
     ens.set_integrals(every=10)                 # load, friction and flow histories, recorded inside the launches
+    ens.set_extrema(every=10)                   # peak pressure, minimum film, ... with their cells, likewise
+    ens.set_probes([[50, 1]])                   # rho, jx, jy, p at a cell after every step, likewise
     ens.run()
     loads = [r['load'] for r in ens.film_integrals()]
     history = [s.load for s in ens.integrals]
+    peaks = [s.p_max for s in ens.extrema]
 
 An ensemble HOLDS its `Problem` objects, it does not copy them: after `run()` or `step()` every member is, bit for bit, what
 the same call on it alone would have made it (`q`, `step`, `simtime`, `dt`, `residual`, `residual_buffer`, `history`, derived
@@ -29,8 +32,8 @@ from datetime import datetime
 import numpy as np
 
 from . import _lib
-from .problem import Problem, _film_series, _in_main_thread, _termination_signals
-from .series import ALL_SERIES, _Series, _integral_sections, _integral_stride
+from .problem import Problem, ProbeSeries, _extrema_series, _film_series, _in_main_thread, _save_extrema_series, _termination_signals
+from .series import ALL_SERIES, _Series, _extrema_stride, _integral_sections, _integral_stride, _probe_cells
 
 
 def member_tier(nx, ny):
@@ -137,6 +140,8 @@ class Ensemble:
         self.problems = problems
         self.parameters = None              # sweep(): what each member got, {dotted key: value}
         self._integral_every = None         # set_integrals: the stride, per member its sections and its series
+        self._extrema_every = None          # set_extrema: the stride, per member its series
+        self._probe_cells = None            # set_probes: per member its cells and its series
         self._lib = problems[0]._lib
         self._e = C.c_void_p()
         handles = (C.c_void_p * len(problems))(*[p._h.value for p in problems])
@@ -218,6 +223,8 @@ class Ensemble:
             before = p.step
             out.append(p._absorb_batch(log, n, int(nexec[i]) - before, before))
             self._collect_integrals(i, out[-1], before)
+            self._collect_extrema(i, out[-1], before)
+            self._collect_probes(i, out[-1])
         return out
 
     def step(self, n):
@@ -255,8 +262,14 @@ class Ensemble:
                 if running[i] and not p._run_active():
                     running[i] = False
                     p._run_end(cfs[i], keep_open)
-                    if self._integral_every is not None and not keep_open and not p.options['silent']:
+                    if keep_open or p.options['silent']:
+                        continue
+                    if self._integral_every is not None:
                         np.savez(os.path.join(p.outdir, 'integrals.npz'), **self._member_integrals(i)._asdict())
+                    if self._extrema_every is not None:         # the arrays a solo run's extrema.npz / probes.npz hold
+                        _save_extrema_series(p.outdir, _extrema_series(self._extrema_series[i]))
+                    if self._probe_cells is not None:
+                        np.savez(os.path.join(p.outdir, 'probes.npz'), **{k: v for k, v in self._member_probes(i)._asdict().items() if v is not None})
 
         try:
             retire()
@@ -322,6 +335,102 @@ class Ensemble:
         if self._integral_every is None:
             return None
         return [self._member_integrals(i) for i in range(len(self.problems))]
+
+    # -------------------------------------------------------------------------------------
+    # extrema series and point probes
+    # -------------------------------------------------------------------------------------
+    def set_extrema(self, every=1):
+        """Record `Problem.set_extrema`'s record -- p_max, p_min, rho_max, rho_min, h_min, u_max, v_max, each with its cell -- for
+        EVERY member after each of its committed steps whose count is a multiple of `every`, inside the ensemble's launches: both
+        one-workgroup kernels write it after the step's commit, bit for bit what `field_extrema()` gives for the same state, and
+        no launch is cut.  Starts new series (see ``extrema``).  A member that has `set_extrema` armed on itself is still
+        refused; the members' own `extrema` stay None."""
+        every = _extrema_stride(every, allow_zero=False)
+        _lib.check(self._lib.gpf_ensemble_extrema_set(self._e, every))
+        self._extrema_every = every
+        self._extrema_series = [_Series(f'Ensemble extrema: member {i}', every) for i in range(len(self.problems))]
+
+    def clear_extrema(self):
+        """Stop recording and drop the series."""
+        if self._extrema_every is not None:
+            _lib.check(self._lib.gpf_ensemble_extrema_clear(self._e))
+        self._extrema_every = None
+
+    def _collect_extrema(self, i, entries, before):
+        """Member i's records of the call that took its step count from `before` through `entries` (its committed steps)."""
+        if self._extrema_every is None:
+            return
+        nq = len(_lib.EXTREMA_NAMES)
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_ensemble_extrema_read(self._e, i, _lib.as_dp(b[0]), b[1].ctypes.data_as(C.POINTER(C.c_int32)), n, steps, have))
+        self._extrema_series[i].collect(read, entries, before, [((nq,), np.float64), ((nq, 2), np.int32)])
+
+    @property
+    def extrema(self):
+        """One FieldExtrema(step, time, p_max, ..., v_max, cells, index) per member -- `Problem.extrema`'s type -- of every recorded
+        step since set_extrema, across `step()` and `run()` calls; None when none are armed."""
+        if self._extrema_every is None:
+            return None
+        return [_extrema_series(rec) for rec in self._extrema_series]
+
+    def set_probes(self, cells, pressure=True):
+        """Record `Problem.set_probes`' record -- rho, jx, jy (and p) at `cells` -- for EVERY member after each of its committed
+        steps, inside the ensemble's launches.  cells: one list of [ix, iy] pairs of the ghosted index space that holds for all
+        members, or one such list per member (a list of len(ensemble) lists); every cell must lie inside its member's ghosted grid
+        (ValueError naming the member otherwise).  The records of one call live in one device buffer, 4096 x cells x values
+        doubles per member; beyond 256 MiB (GPF_ENSEMBLE_PROBES_MB sets another limit, in MiB) the library refuses.  Starts new
+        series (see ``probes``).  A member that has `set_probes` armed on itself is still refused; the members' own `probes` stay
+        None."""
+        ps = self.problems
+
+        def is_pair(c):
+            return not isinstance(c, (str, bytes, dict)) and hasattr(c, '__len__') and len(c) == 2 and not any(hasattr(v, '__len__') for v in c)
+        per_member = not isinstance(cells, (str, bytes, dict)) and hasattr(cells, '__len__') and len(cells) > 0 and \
+            all(not isinstance(c, (str, bytes, dict)) and hasattr(c, '__len__') and not is_pair(c) for c in cells)
+        if per_member and len(cells) != len(ps):
+            raise ValueError(f"Ensemble.set_probes: {len(cells)} lists of cells for {len(ps)} members (one list for all, or one per member)")
+        checked = []
+        for i, p in enumerate(ps):
+            try:
+                checked.append(_probe_cells(cells[i] if per_member else cells, p._shape))
+            except ValueError as err:
+                raise ValueError(f"Ensemble.set_probes: member {i}: {err}") from None
+        i32p = C.POINTER(C.c_int32)
+        counts = np.array([len(c) for c in checked] if per_member else [len(checked[0])], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(checked) if per_member else checked[0], dtype=np.int32)
+        _lib.check(self._lib.gpf_ensemble_probes_set(self._e, int(per_member), counts.ctypes.data_as(i32p), flat.ctypes.data_as(i32p), int(bool(pressure))))
+        self._probe_cells, self._probe_pressure = checked, bool(pressure)
+        self._probe_series = [_Series(f'Ensemble probes: member {i}') for i in range(len(ps))]
+
+    def clear_probes(self):
+        """Stop recording and drop the series."""
+        if self._probe_cells is not None:
+            _lib.check(self._lib.gpf_ensemble_probes_clear(self._e))
+        self._probe_cells = None
+
+    def _collect_probes(self, i, entries):
+        """Member i's probe records of the call that returned `entries` (its committed steps' scalar records)."""
+        if self._probe_cells is None:
+            return
+
+        def read(out, n, first, have):
+            _lib.check(self._lib.gpf_ensemble_probes_read(self._e, i, _lib.as_dp(out), n, first, have))
+        self._probe_series[i].collect_every_step(read, entries, (len(self._probe_cells[i]), 4 if self._probe_pressure else 3))
+
+    def _member_probes(self, i):
+        rec, nv = self._probe_series[i], 4 if self._probe_pressure else 3
+        data = rec.stacked(0, (len(self._probe_cells[i]), nv))
+        return ProbeSeries(rec.step_array(), rec.time_array(), self._probe_cells[i].copy(), data[:, :, 0], data[:, :, 1], data[:, :, 2],
+                           data[:, :, 3] if nv == 4 else None)
+
+    @property
+    def probes(self):
+        """One ProbeSeries(step, time, cells, rho, jx, jy, p) per member -- `Problem.probes`' type -- of every step committed
+        since set_probes, across `step()` and `run()` calls; None when no probes are set."""
+        if self._probe_cells is None:
+            return None
+        return [self._member_probes(i) for i in range(len(self.problems))]
 
     # -------------------------------------------------------------------------------------
     # views

@@ -1028,7 +1028,38 @@ int gpf_frames_time(gpf_handle* h, int64_t n, int mode, double* ms);
  *                         multiples of the stride among the steps the member committed in that call, by its own count: a
  *                         member that stopped on the device leaves those of the steps that ran, a rolled-back step none, a
  *                         member with n[i] = 0 none --, min(*n_records, capacity_records) are copied.  GPF_ERR_STATE unless
- *                         armed. */
+ *                         armed.
+ * Field-extrema series and point probes of an ensemble (the records of gpf_extrema_* and gpf_probes_*), the same way: they belong
+ * to the ensemble -- a member with gpf_extrema_set or gpf_probes_set armed on itself is still refused -- and both kernels write
+ * them inside the batch, behind each commit, without cutting a launch.  k_small_ensemble records through the routines of
+ * k_small_steps, so an LDS-tier member's records are in every bit those of its solo batch; k_mid_ensemble records the extrema
+ * with one walk of the whole workgroup over the interior (csrc/extrema_kernels.hip: extrema_record_wide; the order on
+ * (value, ix, iy) is total, so the record is gpf_extrema_now's of the same state in every bit) and the probes from its workspace
+ * planes.  Recording only reads.  All three ensemble series may be armed together, each at its own stride.
+ *   gpf_ensemble_extrema_set    arms recording, for every member, after each of ITS committed steps whose new count is a multiple
+ *                         of `every`, and starts with empty records.  GPF_ERR_INVALID for every < 1 and, naming the member, for
+ *                         one whose pressure comes from a surrogate (gpf_extrema_set's refusals); nothing is changed then.
+ *                         Allocates, per member, LOG_CAPACITY / every + 1 records and its arguments on the device.
+ *   gpf_ensemble_extrema_clear  disarms and frees them.
+ *   gpf_ensemble_extrema_read   the records member `member` left in the LAST gpf_ensemble_step with gpf_extrema_read's layout,
+ *                         values [record][7], cells [record][7][2], and the step count of each in steps_out (any may be NULL);
+ *                         *n_records (required) how many, by the member's own count as for the film integrals;
+ *                         min(*n_records, capacity_records) are copied.  GPF_ERR_STATE unless armed.
+ *   gpf_ensemble_probes_set     replaces the ensemble's probes.  per_member == 0: the nprobe[0] cells (ix, iy pairs of the ghosted
+ *                         index space) hold for every member; otherwise member i has nprobe[i] cells, all members' pairs one
+ *                         behind the other in `cells`.  with_pressure as gpf_probes_set's.  GPF_ERR_INVALID with a message that
+ *                         names the member for a cell outside its ghosted grid, fewer than 1 or more than 256 cells, or
+ *                         with_pressure on a member whose pressure comes from a surrogate; and, with the need and the limit in
+ *                         bytes, when the records of one call -- LOG_CAPACITY x cells x values doubles per member, in one device
+ *                         allocation -- pass the budget: 256 MiB, or GPF_ENSEMBLE_PROBES_MB (MiB, read at every set).  A failed
+ *                         set leaves the ensemble as it was.
+ *   gpf_ensemble_probes_clear   removes them and frees the buffers.
+ *   gpf_ensemble_probes_read    the records of the steps member `member` committed in the LAST gpf_ensemble_step, layout
+ *                         [step][probe][value] as gpf_probes_read's: *first_step (may be NULL) the step count of the first,
+ *                         *n_records (required) how many -- none for a rolled-back step or a member with n[i] = 0 --,
+ *                         min(*n_records, capacity_records) are copied to out (NULL: none).  GPF_ERR_STATE without probes.
+ * The records of the call before are dropped at the next gpf_ensemble_step; _clear and gpf_ensemble_destroy free the buffers
+ * once the stream is idle. */
 #define GPF_ENSEMBLE_FORCE_WORKSPACE 1
 enum { GPF_ENSEMBLE_TIER_LDS = 0, GPF_ENSEMBLE_TIER_WORKSPACE = 1 };
 typedef struct gpf_ensemble gpf_ensemble;
@@ -1043,6 +1074,12 @@ int gpf_ensemble_member_info(gpf_ensemble* e, int member, int32_t* tier, int64_t
 int gpf_ensemble_integrals_set(gpf_ensemble* e, int64_t every, int nsx, const int32_t* ix, int nsy, const int32_t* iy);
 int gpf_ensemble_integrals_clear(gpf_ensemble* e);
 int gpf_ensemble_integrals_read(gpf_ensemble* e, int member, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_ensemble_extrema_set(gpf_ensemble* e, int64_t every);
+int gpf_ensemble_extrema_clear(gpf_ensemble* e);
+int gpf_ensemble_extrema_read(gpf_ensemble* e, int member, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_ensemble_probes_set(gpf_ensemble* e, int per_member, const int32_t* nprobe, const int32_t* cells, int with_pressure);
+int gpf_ensemble_probes_clear(gpf_ensemble* e);
+int gpf_ensemble_probes_read(gpf_ensemble* e, int member, double* out, int64_t capacity_records, int64_t* first_step, int64_t* n_records);
 
 /* ---- resampling a state onto another grid (no reference counterpart) ------------------------------- */
 /* dst's state from src's committed state, both covering the same domain with different (Nx, Ny): bilinear interpolation, over
