@@ -6,8 +6,42 @@
 // A member is a handle of its own, borrowed: everything a solo gpf_step of the same count would leave in it -- buffers, run
 // state, log, host_step / next_step, prev_state_valid, g1_ready -- is left in it here, so that it can go on alone.
 //
-// Film-integral series (gpf_ensemble_integrals_*) belong to the ENSEMBLE, not to its members: both kernels record them inside
-// the batch (integral_kernels.hip: film_record_block) into per-member slots that the ensemble owns, so nothing cuts a launch.
+// The series -- film integrals (gpf_ensemble_integrals_*), field extrema (gpf_ensemble_extrema_*), point probes
+// (gpf_ensemble_probes_*) -- belong to the ENSEMBLE, not to its members: both kernels record them inside the batch, behind each
+// commit (film_record_block, extrema_record_block / extrema_record_wide, probe_record_block), into per-member slots that the
+// ensemble owns, so nothing cuts a launch.  All three are one EnsembleSeries: where a member's records lie is
+// ensemble_slots.hpp's to say, every gpf_ensemble_*_set ends in ensemble_series_install, every release is
+// ensemble_series_release, a call's records come to the host through series_collect and leave through series_read
+// (api_series.inc), as a handle's do.  A further series is its _set's checks and argument image, its _clear and _read shells, an
+// entry in gpf_ensemble::series() and a pointer in SmallArgs; ensemble_collect takes a second channel of int32 as it is, any
+// other kind of channel needs its arm there.
+
+#include "ensemble_slots.hpp"
+
+// One series of an ensemble: `what` an error message calls its records; the stride that arms it (0: not armed; the probes' is
+// 1); `cap`, the records every member's slots hold -- what a call of at most LOG_CAPACITY steps can leave at the stride; 0 for the
+// probes, whose capacity is each member's own log's and lives in `at` alone --; ONE device allocation `rec` for every member's
+// records, laid out by `at`; the members' argument structs in device memory (`dev`: [m], and whatever the series keeps behind
+// them), which point into `rec`; per member what the last gpf_ensemble_step left on the host (of each SeriesStore the records and
+// their steps alone: the stride is `every` here, and nothing is ever pending).
+struct EnsembleSeries {
+    const char* what = "";
+    long long every = 0, cap = 0;
+    char* rec = nullptr;
+    char* dev = nullptr;
+    EnsembleSlots at;
+    std::vector<SeriesStore> last;
+    SeriesBuffers owned() { return {(void**)&rec, (void**)&dev}; }
+    // member i's argument struct for the kernels (null while not armed)
+    template <class Args> Args* args(int i) const { return every ? (Args*)dev + i : nullptr; }
+    // channel c of member i's records: on the device, and where a call's come to rest
+    template <class T> SeriesChannel<T> device_channel(int c, int i, std::vector<T>& host) const {
+        return series_channel(host, (T*)(rec + at.at(c, i)), at.record_bytes(c, i) / sizeof(T));
+    }
+    template <class T> SeriesChannel<T> read_channel(int c, int i, std::vector<T>& host, T* out) const {
+        return series_channel(host, out, at.record_bytes(c, i) / sizeof(T));
+    }
+};
 
 struct gpf_ensemble {
     std::vector<gpf_handle*> members;
@@ -23,45 +57,10 @@ struct gpf_ensemble {
     std::vector<int> tier;                  // per member: GPF_ENSEMBLE_TIER_LDS / _WORKSPACE, fixed at create
     std::vector<long long> ws_off;          // per member of the workspace tier: where its workspace starts in `ws`, in bytes
     char* ws = nullptr;                     // one device allocation for all workspaces (mid_layout.hpp)
-    // film-integral series: stride (0: not armed); per member its sections, doubles per record and where its records start in
-    // `rec` (one device allocation, `cap` records per member: what a call of at most LOG_CAPACITY steps can leave at the stride);
-    // the members' FilmBlockArgs in device memory ([m]); the records of the last gpf_ensemble_step and their step counts on the host
-    struct Film {
-        long long every = 0, cap = 0;
-        std::vector<FilmBlockArgs> args;
-        std::vector<size_t> off;
-        double* rec = nullptr;
-        FilmBlockArgs* dev = nullptr;
-        std::vector<std::vector<double>> host;
-        std::vector<std::vector<long long>> steps;
-        int nrec(int i) const { return FILM_NSUM + args[i].nsx + args[i].nsy; }
-    } film;
-    // field-extrema series, the same way: stride (0: not armed), `cap` records per member in ONE device allocation `rec` -- the
-    // values of all members ([m][cap][7] doubles), then their cells ([m][cap][7][2] ints) --, the members' ExtremaArgs in device
-    // memory ([m]; no row scratch: both kernels fold inside the workgroup), the records of the last gpf_ensemble_step on the host
-    struct Extrema {
-        long long every = 0, cap = 0;
-        char* rec = nullptr;
-        ExtremaArgs* dev = nullptr;
-        std::vector<std::vector<double>> host;
-        std::vector<std::vector<int32_t>> cells;
-        std::vector<std::vector<long long>> steps;
-        double* val(int i) const { return (double*)rec + (size_t)i * cap * EXTREMA_NQ; }
-        int* cell(size_t m, int i) const { return (int*)((double*)rec + m * cap * EXTREMA_NQ) + (size_t)i * cap * 2 * EXTREMA_NQ; }
-    } ext;
-    // point probes: per member its count (empty: not armed) and where its records start in `out` (ONE device allocation, log_cap
-    // records of n[i] x nv doubles per member: a record per committed step); `dev`: the members' ProbeArgs ([m]) and behind them
-    // everyone's cells, in device memory; the records of the last gpf_ensemble_step on the host and the step count of the first
-    struct Probes {
-        std::vector<int> n;
-        int nv = 0;
-        std::vector<size_t> off;
-        double* out = nullptr;
-        ProbeArgs* dev = nullptr;
-        std::vector<std::vector<double>> host;
-        std::vector<long long> first;
-        bool armed() const { return !n.empty(); }
-    } probes;
+    // the three series; the probes keep per member the step count of the first record of the last call beside theirs
+    EnsembleSeries film, ext, probes;
+    std::vector<long long> probes_first;
+    std::array<EnsembleSeries*, 3> series() { return {&film, &ext, &probes}; }
     size_t args_off() const { return members.size() * sizeof(StepState); }
     size_t bytes() const { return args_off() + members.size() * (sizeof(SmallArgs) + sizeof(Phys) + sizeof(double*)); }
 };
@@ -84,6 +83,7 @@ static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first, int
     if (h->cfg.device != first->cfg.device) return "it lives on device " + std::to_string(h->cfg.device) + ", member 0 on device " +
                                                    std::to_string(first->cfg.device) + " (one launch needs one device)";
     if (h->stream != first->stream) return "its stream differs from member 0's (one launch needs one stream)";
+    // (spelled out, not walked from SERIES: the order differs from the table's, and the host tests of the series read these lines)
     if (h->integ.every) return "film integrals are armed on it (they cut the batch per member; gpf_integrals_clear, or step it alone)";
     if (h->weighted.every) return "weighted integrals are armed on it (they cut the batch per member; gpf_weighted_clear, or step it alone)";
     if (h->stats.every) return "statistics are armed on it (they cut the batch per member; gpf_stats_clear, or step it alone)";
@@ -94,6 +94,62 @@ static std::string ensemble_member_refusal(gpf_handle* h, gpf_handle* first, int
     if (h->chg.every) return "changes are armed on it (they cut the batch per member; gpf_changes_clear, or step it alone)";
     if (h->frames.every) return "frames are armed on it (they cut the batch per member; gpf_frames_clear, or step it alone)";
     return "";
+}
+
+static int ensemble_member_check(const gpf_ensemble* e, int member, const char* who) {
+    if (member >= 0 && member < (int)e->members.size()) return GPF_OK;
+    return fail(GPF_ERR_INVALID, std::string(who) + ": member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+}
+
+// ---- the ensemble's series ---------------------------------------------------------------------------------------------------------
+// What is armed goes, with its buffers and the records on the host
+static int ensemble_series_release(gpf_ensemble* e, EnsembleSeries& s) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->members[0]->stream));       // a recording launch may still be queued
+    GPF_TRY(series_free(s.owned()));
+    s = EnsembleSeries();
+    return GPF_OK;
+}
+
+// What every gpf_ensemble_*_set ends in, its checks passed: `fresh` holds the stride, the capacity and the layout; `image` is what
+// `dev` shall hold -- the members' argument structs and whatever lies behind them --, complete but for the device addresses,
+// which `patch(fresh)` writes into it once they are known.  Built first and swapped in last: on an error the ensemble stays as
+// it was, the series that was armed included.
+template <class Patch> static int ensemble_series_install(gpf_ensemble* e, EnsembleSeries& s, EnsembleSeries&& fresh, const char* who, void* image,
+                                                          size_t image_bytes, Patch&& patch) {
+    HIP_TRY(hipSetDevice(e->device));
+    fresh.last.resize(e->members.size());
+    hipError_t err = hipMalloc(&fresh.rec, fresh.at.total);
+    if (err == hipSuccess) err = hipMalloc(&fresh.dev, image_bytes);
+    if (err == hipSuccess) {
+        patch(fresh);
+        err = hipMemcpy(fresh.dev, image, image_bytes, hipMemcpyHostToDevice);
+    }
+    const int rc = err == hipSuccess ? ensemble_series_release(e, s) : fail(GPF_ERR_HIP, std::string(who) + ": " + hipGetErrorString(err));
+    if (rc != GPF_OK) {
+        (void)series_free(fresh.owned());
+        return rc;
+    }
+    s = std::move(fresh);
+    return GPF_OK;
+}
+
+// After a call's states have been read: member i's records of the `ran` steps it committed from step count `base` -> host.  The
+// multiples of each stride in (base, base + ran], by its own ran (a member that stopped on the device ran a prefix of its steps;
+// a rolled-back step left none); a probe record per committed step.  One copy per channel, each series whatever became of the others.
+static int ensemble_collect(gpf_ensemble* e, int i, long long base, long long ran) {
+    int rc = GPF_OK;
+    for (EnsembleSeries* s : e->series()) {
+        if (!s->every) continue;
+        SeriesStore& r = s->last[i];
+        // channel 0: doubles -> `host`; a series laid out with a second channel has int32 there -> `cells`
+        const int got = s->at.channels() == 2 ? series_collect(s->every, r.steps, base, ran, s->device_channel(0, i, r.host), s->device_channel(1, i, r.cells))
+                                              : series_collect(s->every, r.steps, base, ran, s->device_channel(0, i, r.host));
+        if (got == GPF_OK) continue;
+        r.forget();                                 // (series_append made room before the copy that failed)
+        if (rc == GPF_OK) rc = fail(got, std::string("gpf_ensemble_step: ") + s->what + " record copy: " + g_err);
+    }
+    return rc;
 }
 
 extern "C" int gpf_ensemble_create(gpf_handle* const* members, int m, gpf_ensemble** out) {
@@ -118,6 +174,7 @@ extern "C" int gpf_ensemble_create2(gpf_handle* const* members, int m, int flags
     e->members.assign(members, members + m);
     e->device = members[0]->cfg.device;
     e->entries.assign(m, 0);
+    e->probes_first.assign(m, 0);
     e->flags = flags;
     e->tier.assign(m, GPF_ENSEMBLE_TIER_LDS);
     e->ws_off.assign(m, 0);
@@ -146,12 +203,9 @@ extern "C" int gpf_ensemble_destroy(gpf_ensemble* e) {
     for (gpf_handle* h : e->members) ensemble_members_drop(h, false);
     hipSetDevice(e->device);
     hipStreamSynchronize(e->members[0]->stream);        // a launch that records into the buffers below may still be queued
-    if (e->film.rec) hipFree(e->film.rec);
-    if (e->film.dev) hipFree(e->film.dev);
-    if (e->ext.rec) hipFree(e->ext.rec);
-    if (e->ext.dev) hipFree(e->ext.dev);
-    if (e->probes.out) hipFree(e->probes.out);
-    if (e->probes.dev) hipFree(e->probes.dev);
+    for (EnsembleSeries* s : e->series())               // (errors are not reported here: series_destroy)
+        for (void** p : s->owned())
+            if (p && *p) (void)hipFree(*p);
     if (e->dev) hipFree(e->dev);
     if (e->ws) hipFree(e->ws);
     if (e->host) hipHostFree(e->host);
@@ -183,9 +237,9 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
     for (int i = 0; i < m; ++i) {
         e->entries[i] = 0;
         if (n[i] > 0) slots.push_back(i);
-        if (e->film.every) { e->film.host[i].clear(); e->film.steps[i].clear(); }      // the records of the call before go
-        if (e->ext.every) { e->ext.host[i].clear(); e->ext.cells[i].clear(); e->ext.steps[i].clear(); }
-        if (e->probes.armed()) { e->probes.host[i].clear(); e->probes.first[i] = e->members[i]->host_step + 1; }
+        for (EnsembleSeries* s : e->series())
+            if (s->every) s->last[i].forget();          // the records of the call before go
+        if (e->probes.every) e->probes_first[i] = e->members[i]->host_step + 1;
     }
     std::stable_sort(slots.begin(), slots.end(), [&](int a, int b) { return key(a) < key(b); });
     const int nslots = (int)slots.size();
@@ -205,9 +259,9 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         a.qa = h->q[0]; a.qb = h->q[1]; a.topo = h->topo; a.Ls = h->Ls; a.st = h->st;
         a.log = h->log; a.log_base = h->host_step; a.log_cap = h->log_cap; a.L = h->L; a.E = h->E;
         a.nsteps = (int)n[slots[s]]; a.honor_stop = honor_stop;
-        a.probe = e->probes.armed() ? e->probes.dev + slots[s] : nullptr;
-        a.extrema = e->ext.every ? e->ext.dev + slots[s] : nullptr;
-        a.film = e->film.every ? e->film.dev + slots[s] : nullptr;
+        a.probe = e->probes.args<ProbeArgs>(slots[s]);
+        a.extrema = e->ext.args<ExtremaArgs>(slots[s]);
+        a.film = e->film.args<FilmBlockArgs>(slots[s]);
         hp[s] = h->P;
         hw[s] = e->tier[slots[s]] == GPF_ENSEMBLE_TIER_WORKSPACE ? (double*)(e->ws + e->ws_off[slots[s]]) : nullptr;
     }
@@ -262,34 +316,8 @@ extern "C" int gpf_ensemble_step(gpf_ensemble* e, const int64_t* n, int honor_st
         const StepState& st = hs[s];
         const long long ran = st.step - h->host_step;
         e->entries[i] = ran + ((st.invalid && ran < n[i]) ? 1 : 0);
-        // the member's film records: the multiples of the stride in (base, base + ran], by its own ran (a member that stopped on
-        // the device ran a prefix of its steps; a rolled-back step left none)
-        const long long cnt = e->film.every ? series_count(h->host_step, ran, e->film.every) : 0;
-        if (cnt > 0) {
-            const size_t nrec = (size_t)e->film.nrec(i);
-            std::vector<double> got((size_t)cnt * nrec);
-            if (hip_ok(hipMemcpy(got.data(), e->film.rec + e->film.off[i], got.size() * sizeof(double), hipMemcpyDeviceToHost), "film record copy")) {
-                e->film.host[i].swap(got);
-                for (long long k = 1; k <= cnt; ++k) e->film.steps[i].push_back((h->host_step / e->film.every + k) * e->film.every);
-            }
-        }
-        // its extrema records likewise (values and cells), and a probe record per committed step
-        const long long ecnt = e->ext.every ? series_count(h->host_step, ran, e->ext.every) : 0;
-        if (ecnt > 0) {
-            std::vector<double> val((size_t)ecnt * EXTREMA_NQ);
-            std::vector<int32_t> cell((size_t)ecnt * 2 * EXTREMA_NQ);
-            if (hip_ok(hipMemcpy(val.data(), e->ext.val(i), val.size() * sizeof(double), hipMemcpyDeviceToHost), "extrema record copy") &&
-                hip_ok(hipMemcpy(cell.data(), e->ext.cell((size_t)m, i), cell.size() * sizeof(int32_t), hipMemcpyDeviceToHost), "extrema record copy")) {
-                e->ext.host[i].swap(val);
-                e->ext.cells[i].swap(cell);
-                for (long long k = 1; k <= ecnt; ++k) e->ext.steps[i].push_back((h->host_step / e->ext.every + k) * e->ext.every);
-            }
-        }
-        if (e->probes.armed() && ran > 0) {
-            std::vector<double> got((size_t)ran * e->probes.n[i] * e->probes.nv);
-            if (hip_ok(hipMemcpy(got.data(), e->probes.out + e->probes.off[i], got.size() * sizeof(double), hipMemcpyDeviceToHost), "probe record copy"))
-                e->probes.host[i].swap(got);
-        }
+        const int rcol = ensemble_collect(e, i, h->host_step, ran);
+        if (rc == GPF_OK) rc = rcol;
         h->host_step = st.step; h->next_step = st.step;
         prev_state_after(h, ran >= 1 && !st.invalid);
         h->g1_ready = false;
@@ -314,8 +342,7 @@ extern "C" int gpf_ensemble_limits2(int64_t* mid_max_cells, int32_t* mid_doubles
 
 extern "C" int gpf_ensemble_member_info(gpf_ensemble* e, int member, int32_t* tier, int64_t* workspace_bytes) {
     if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_member_info: null argument");
-    if (member < 0 || member >= (int)e->members.size())
-        return fail(GPF_ERR_INVALID, "gpf_ensemble_member_info: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    GPF_TRY(ensemble_member_check(e, member, "gpf_ensemble_member_info"));
     const bool ws = e->tier[member] == GPF_ENSEMBLE_TIER_WORKSPACE;
     if (tier) *tier = e->tier[member];
     if (workspace_bytes) *workspace_bytes = ws ? mid_workspace_bytes(mid_cells(e->members[member]->L.Nx, e->members[member]->L.Ny)) : 0;
@@ -324,8 +351,7 @@ extern "C" int gpf_ensemble_member_info(gpf_ensemble* e, int member, int32_t* ti
 
 extern "C" int gpf_ensemble_log(gpf_ensemble* e, int member, gpf_scalars_t* log, int64_t log_capacity, int64_t* n_entries) {
     if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_log: null argument");
-    if (member < 0 || member >= (int)e->members.size())
-        return fail(GPF_ERR_INVALID, "gpf_ensemble_log: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    GPF_TRY(ensemble_member_check(e, member, "gpf_ensemble_log"));
     const long long have = e->entries[member];
     if (n_entries) *n_entries = have;
     const long long take = std::min<long long>(have, log ? log_capacity : 0);
@@ -337,16 +363,9 @@ extern "C" int gpf_ensemble_log(gpf_ensemble* e, int member, gpf_scalars_t* log,
     return GPF_OK;
 }
 
-static int ensemble_film_release(gpf_ensemble* e) {
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->members[0]->stream));       // a recording launch may still be queued
-    if (e->film.rec) HIP_TRY(hipFree(e->film.rec));
-    e->film.rec = nullptr;
-    if (e->film.dev) HIP_TRY(hipFree(e->film.dev));
-    e->film.dev = nullptr;
-    e->film = gpf_ensemble::Film();
-    return GPF_OK;
-}
+// ---- film integrals (the record of gpf_integrals_*), extrema (that of gpf_extrema_*), point probes (that of gpf_probes_*) -------------
+// k_small_ensemble records them on its LDS planes -- in every bit what the member's solo batch records --, k_mid_ensemble on its
+// workspace planes.
 
 extern "C" int gpf_ensemble_integrals_set(gpf_ensemble* e, int64_t every, int nsx, const int32_t* ix, int nsy, const int32_t* iy) {
     if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_set: null argument");
@@ -369,12 +388,12 @@ extern "C" int gpf_ensemble_integrals_set(gpf_ensemble* e, int64_t every, int ns
                 return fail(GPF_ERR_INVALID, who + ": y-section " + std::to_string(k) + " at column " + std::to_string(iy[k]) +
                                              " lies outside its interior columns 1.." + std::to_string(h->L.Ny));
     }
-    GPF_TRY(ensemble_film_release(e));
-    gpf_ensemble::Film f;
+    EnsembleSeries f;
+    f.what = "film";
     f.every = every;
     f.cap = LOG_CAPACITY / every + 1;               // series_count(base, ran, every) <= ran / every + 1
-    f.args.resize(m); f.off.resize(m); f.host.resize(m); f.steps.resize(m);
-    size_t total = 0;
+    std::vector<FilmBlockArgs> args(m);
+    std::vector<size_t> record_bytes(m);
     for (int i = 0; i < m; ++i) {
         const gpf_handle* h = e->members[i];
         // default: first and last interior row / column, one where the extent is 1 (integrals_default_sections)
@@ -382,54 +401,25 @@ extern "C" int gpf_ensemble_integrals_set(gpf_ensemble* e, int64_t every, int ns
         int mx = h->L.Nx > 1 ? 2 : 1, my = h->L.Ny > 1 ? 2 : 1;
         if (ix && nsx > 0) { mx = nsx; for (int k = 0; k < nsx; ++k) sx[k] = ix[k]; }
         if (iy && nsy > 0) { my = nsy; for (int k = 0; k < nsy; ++k) sy[k] = iy[k]; }
-        f.args[i] = film_block_args(nullptr, every, f.cap, h->cfg.dx, h->cfg.dy, mx, sx, my, sy);
-        f.off[i] = total;
-        total += (size_t)f.cap * (size_t)(FILM_NSUM + mx + my);
+        args[i] = film_block_args(nullptr, every, f.cap, h->cfg.dx, h->cfg.dy, mx, sx, my, sy);
+        record_bytes[i] = (size_t)(FILM_NSUM + mx + my) * sizeof(double);
     }
-    hipError_t err = hipMalloc(&f.rec, total * sizeof(double));
-    if (err == hipSuccess) err = hipMalloc(&f.dev, (size_t)m * sizeof(FilmBlockArgs));
-    for (int i = 0; i < m; ++i) f.args[i].rec = f.rec ? f.rec + f.off[i] : nullptr;
-    if (err == hipSuccess) err = hipMemcpy(f.dev, f.args.data(), (size_t)m * sizeof(FilmBlockArgs), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (f.rec) (void)hipFree(f.rec);
-        if (f.dev) (void)hipFree(f.dev);
-        return fail(GPF_ERR_HIP, std::string("gpf_ensemble_integrals_set: ") + hipGetErrorString(err));
-    }
-    e->film = std::move(f);
-    return GPF_OK;
+    f.at = ensemble_slots({record_bytes}, std::vector<long long>(m, f.cap));
+    return ensemble_series_install(e, e->film, std::move(f), "gpf_ensemble_integrals_set", args.data(), args.size() * sizeof(FilmBlockArgs),
+                                   [&](const EnsembleSeries& s) { for (int i = 0; i < m; ++i) args[i].rec = (double*)(s.rec + s.at.at(0, i)); });
 }
 
 extern "C" int gpf_ensemble_integrals_clear(gpf_ensemble* e) {
     if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_clear: null argument");
-    return ensemble_film_release(e);
+    return ensemble_series_release(e, e->film);
 }
 
 extern "C" int gpf_ensemble_integrals_read(gpf_ensemble* e, int member, double* out, int64_t capacity_records, int64_t* steps_out, int64_t* n_records) {
     if (!e || !n_records) return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_read: null argument (e and n_records are required)");
-    if (member < 0 || member >= (int)e->members.size())
-        return fail(GPF_ERR_INVALID, "gpf_ensemble_integrals_read: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    GPF_TRY(ensemble_member_check(e, member, "gpf_ensemble_integrals_read"));
     if (!e->film.every) return fail(GPF_ERR_STATE, "gpf_ensemble_integrals_read: no integrals are armed (gpf_ensemble_integrals_set)");
-    const size_t nrec = (size_t)e->film.nrec(member);
-    const int64_t have = (int64_t)e->film.steps[member].size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
-    *n_records = have;
-    if (out && take > 0) std::memcpy(out, e->film.host[member].data(), (size_t)take * nrec * sizeof(double));
-    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = e->film.steps[member][(size_t)k];
-    return GPF_OK;
-}
-
-// ---- the ensemble's extrema series (the record of gpf_extrema_*) and point probes (that of gpf_probes_*) -------------------------
-// Both kernels write them inside the batch, behind each commit: k_small_ensemble through extrema_record_block / probe_record_block
-// on its LDS planes -- in every bit what the member's solo batch records --, k_mid_ensemble through extrema_record_wide /
-// probe_record_block on its workspace planes.
-
-static int ensemble_extrema_release(gpf_ensemble* e) {
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->members[0]->stream));       // a recording launch may still be queued
-    if (e->ext.rec) HIP_TRY(hipFree(e->ext.rec));
-    e->ext.rec = nullptr;
-    if (e->ext.dev) HIP_TRY(hipFree(e->ext.dev));
-    e->ext.dev = nullptr;
-    e->ext = gpf_ensemble::Extrema();
+    SeriesStore& r = e->film.last[member];
+    series_read(r.steps, capacity_records, steps_out, n_records, e->film.read_channel(0, member, r.host, out));
     return GPF_OK;
 }
 
@@ -438,62 +428,36 @@ extern "C" int gpf_ensemble_extrema_set(gpf_ensemble* e, int64_t every) {
     if (every < 1) return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_set: every >= 1 required (gpf_ensemble_extrema_clear disarms), got " + std::to_string(every));
     const int m = (int)e->members.size();
     for (int i = 0; i < m; ++i) GPF_TRY(extrema_refusal(e->members[i], "gpf_ensemble_extrema_set: member " + std::to_string(i)));
-    HIP_TRY(hipSetDevice(e->device));
-    gpf_ensemble::Extrema x;
+    EnsembleSeries x;
+    x.what = "extrema";
     x.every = every;
     x.cap = LOG_CAPACITY / every + 1;               // series_count(base, ran, every) <= ran / every + 1
-    x.host.resize(m); x.cells.resize(m); x.steps.resize(m);
-    const size_t per = (size_t)x.cap * EXTREMA_NQ;
-    hipError_t err = hipMalloc(&x.rec, (size_t)m * per * (sizeof(double) + 2 * sizeof(int)));
-    if (err == hipSuccess) err = hipMalloc(&x.dev, (size_t)m * sizeof(ExtremaArgs));
+    // the values of all members ([m][cap][7] doubles), then their cells ([m][cap][7][2] ints)
+    x.at = ensemble_slots({std::vector<size_t>(m, EXTREMA_NQ * sizeof(double)), std::vector<size_t>(m, 2 * EXTREMA_NQ * sizeof(int))},
+                          std::vector<long long>(m, x.cap));
     std::vector<ExtremaArgs> args(m);
-    for (int i = 0; i < m && err == hipSuccess; ++i) {
-        args[i].val = x.val(i); args[i].cell = x.cell((size_t)m, i);
-        args[i].row_val = nullptr; args[i].row_iy = nullptr;        // k_extrema_partial's: no launch of it here
-        args[i].every = every; args[i].cap = x.cap;
+    for (ExtremaArgs& a : args) {
+        a.row_val = nullptr; a.row_iy = nullptr;    // k_extrema_partial's: no launch of it here (both kernels fold inside the workgroup)
+        a.every = every; a.cap = x.cap;
     }
-    if (err == hipSuccess) err = hipMemcpy(x.dev, args.data(), (size_t)m * sizeof(ExtremaArgs), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {                        // the ensemble stays as it was
-        if (x.rec) (void)hipFree(x.rec);
-        if (x.dev) (void)hipFree(x.dev);
-        return fail(GPF_ERR_HIP, std::string("gpf_ensemble_extrema_set: ") + hipGetErrorString(err));
-    }
-    const int rc = ensemble_extrema_release(e);
-    if (rc != GPF_OK) {
-        (void)hipFree(x.rec); (void)hipFree(x.dev);
-        return rc;
-    }
-    e->ext = std::move(x);
-    return GPF_OK;
+    return ensemble_series_install(e, e->ext, std::move(x), "gpf_ensemble_extrema_set", args.data(), args.size() * sizeof(ExtremaArgs),
+                                   [&](const EnsembleSeries& s) {
+                                       for (int i = 0; i < m; ++i) { args[i].val = (double*)(s.rec + s.at.at(0, i)); args[i].cell = (int*)(s.rec + s.at.at(1, i)); }
+                                   });
 }
 
 extern "C" int gpf_ensemble_extrema_clear(gpf_ensemble* e) {
     if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_clear: null argument");
-    return ensemble_extrema_release(e);
+    return ensemble_series_release(e, e->ext);
 }
 
 extern "C" int gpf_ensemble_extrema_read(gpf_ensemble* e, int member, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out,
                                          int64_t* n_records) {
     if (!e || !n_records) return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_read: null argument (e and n_records are required)");
-    if (member < 0 || member >= (int)e->members.size())
-        return fail(GPF_ERR_INVALID, "gpf_ensemble_extrema_read: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
+    GPF_TRY(ensemble_member_check(e, member, "gpf_ensemble_extrema_read"));
     if (!e->ext.every) return fail(GPF_ERR_STATE, "gpf_ensemble_extrema_read: no extrema are armed (gpf_ensemble_extrema_set)");
-    const int64_t have = (int64_t)e->ext.steps[member].size(), take = std::max<int64_t>(0, std::min(have, capacity_records));
-    *n_records = have;
-    if (values && take > 0) std::memcpy(values, e->ext.host[member].data(), (size_t)take * EXTREMA_NQ * sizeof(double));
-    if (cells && take > 0) std::memcpy(cells, e->ext.cells[member].data(), (size_t)take * 2 * EXTREMA_NQ * sizeof(int32_t));
-    for (int64_t k = 0; steps_out && k < take; ++k) steps_out[k] = e->ext.steps[member][(size_t)k];
-    return GPF_OK;
-}
-
-static int ensemble_probes_release(gpf_ensemble* e) {
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipStreamSynchronize(e->members[0]->stream));       // a recording launch may still be queued
-    if (e->probes.out) HIP_TRY(hipFree(e->probes.out));
-    e->probes.out = nullptr;
-    if (e->probes.dev) HIP_TRY(hipFree(e->probes.dev));
-    e->probes.dev = nullptr;
-    e->probes = gpf_ensemble::Probes();
+    SeriesStore& r = e->ext.last[member];
+    series_read(r.steps, capacity_records, steps_out, n_records, e->ext.read_channel(0, member, r.host, values), e->ext.read_channel(1, member, r.cells, cells));
     return GPF_OK;
 }
 
@@ -507,11 +471,11 @@ static size_t ensemble_probes_budget() {
 extern "C" int gpf_ensemble_probes_set(gpf_ensemble* e, int per_member, const int32_t* nprobe, const int32_t* cells, int with_pressure) {
     if (!e || !nprobe || !cells) return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_set: null argument");
     const int m = (int)e->members.size();
-    gpf_ensemble::Probes p;
-    p.n.resize(m); p.off.resize(m); p.host.resize(m); p.first.assign(m, 0);
-    p.nv = with_pressure ? 4 : 3;
-    std::vector<size_t> first_cell(m);              // where member i's cells start in `cells`, in cells
-    size_t ncells = 0, total = 0;
+    const int nv = with_pressure ? 4 : 3;
+    std::vector<int> count(m);
+    std::vector<size_t> first_cell(m), record_bytes(m);     // where member i's cells start in `cells`, in cells; its n x nv doubles
+    std::vector<long long> cap(m);                          // a record per step of the longest call
+    size_t ncells = 0;
     for (int i = 0; i < m; ++i) {
         const gpf_handle* h = e->members[i];
         const std::string who = "gpf_ensemble_probes_set: member " + std::to_string(i);
@@ -528,61 +492,47 @@ extern "C" int gpf_ensemble_probes_set(gpf_ensemble* e, int per_member, const in
             if (c[2 * k] < 0 || c[2 * k] > h->L.Nx + 1 || c[2 * k + 1] < 0 || c[2 * k + 1] > h->L.Ny + 1)
                 return fail(GPF_ERR_INVALID, who + ": probe " + std::to_string(k) + " at cell (" + std::to_string(c[2 * k]) + ", " + std::to_string(c[2 * k + 1]) +
                                              ") lies outside 0.." + std::to_string(h->L.Nx + 1) + " x 0.." + std::to_string(h->L.Ny + 1));
-        p.n[i] = n;
-        p.off[i] = total;
+        count[i] = n;
         ncells = per_member ? ncells + (size_t)n : (size_t)n;
-        total += (size_t)h->log_cap * (size_t)n * (size_t)p.nv;     // a record per step of the longest call
+        record_bytes[i] = (size_t)n * (size_t)nv * sizeof(double);
+        cap[i] = h->log_cap;
     }
-    const size_t need = total * sizeof(double), budget = ensemble_probes_budget();
+    EnsembleSeries p;
+    p.what = "probe";
+    p.every = 1;                                    // (cap stays 0: per member, below)
+    p.at = ensemble_slots({record_bytes}, cap);
+    const size_t need = p.at.total, budget = ensemble_probes_budget();
     if (need > budget)
         return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_set: the records of one call need " + std::to_string(need) + " bytes of device memory (" +
                                      std::to_string(LOG_CAPACITY) + " steps x probes x values x 8 per member), more than the budget of " +
                                      std::to_string(budget) + " bytes (GPF_ENSEMBLE_PROBES_MB, in MiB; default 256)");
-    HIP_TRY(hipSetDevice(e->device));
     // ProbeArgs[m], then the cells: one small allocation, one copy
     std::vector<char> image((size_t)m * sizeof(ProbeArgs) + ncells * 2 * sizeof(int));
-    hipError_t err = hipMalloc(&p.out, need);
-    if (err == hipSuccess) err = hipMalloc(&p.dev, image.size());
-    if (err == hipSuccess) {
-        const int* dev_cells = (const int*)((char*)p.dev + (size_t)m * sizeof(ProbeArgs));
-        ProbeArgs* args = (ProbeArgs*)image.data();
-        for (int i = 0; i < m; ++i) {
-            args[i].cells = dev_cells + 2 * first_cell[i];
-            args[i].out = p.out + p.off[i];
-            args[i].nprobe = p.n[i]; args[i].nv = p.nv;
-            args[i].base = 0; args[i].cap = e->members[i]->log_cap;     // (the one-workgroup kernels take both from their own arguments)
-        }
-        std::memcpy(image.data() + (size_t)m * sizeof(ProbeArgs), cells, ncells * 2 * sizeof(int));
-        err = hipMemcpy(p.dev, image.data(), image.size(), hipMemcpyHostToDevice);
+    ProbeArgs* args = (ProbeArgs*)image.data();
+    for (int i = 0; i < m; ++i) {
+        args[i].nprobe = count[i]; args[i].nv = nv;
+        args[i].base = 0; args[i].cap = cap[i];     // (the one-workgroup kernels take both from their own arguments)
     }
-    if (err != hipSuccess) {                        // the ensemble stays as it was
-        if (p.out) (void)hipFree(p.out);
-        if (p.dev) (void)hipFree(p.dev);
-        return fail(GPF_ERR_HIP, std::string("gpf_ensemble_probes_set: ") + hipGetErrorString(err));
-    }
-    const int rc = ensemble_probes_release(e);
-    if (rc != GPF_OK) {
-        (void)hipFree(p.out); (void)hipFree(p.dev);
-        return rc;
-    }
-    e->probes = std::move(p);
+    std::memcpy(image.data() + (size_t)m * sizeof(ProbeArgs), cells, ncells * 2 * sizeof(int));
+    GPF_TRY(ensemble_series_install(e, e->probes, std::move(p), "gpf_ensemble_probes_set", image.data(), image.size(), [&](const EnsembleSeries& s) {
+        const int* dev_cells = (const int*)(s.dev + (size_t)m * sizeof(ProbeArgs));
+        for (int i = 0; i < m; ++i) { args[i].cells = dev_cells + 2 * first_cell[i]; args[i].out = (double*)(s.rec + s.at.at(0, i)); }
+    }));
+    e->probes_first.assign(m, 0);
     return GPF_OK;
 }
 
 extern "C" int gpf_ensemble_probes_clear(gpf_ensemble* e) {
     if (!e) return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_clear: null argument");
-    return ensemble_probes_release(e);
+    return ensemble_series_release(e, e->probes);
 }
 
 extern "C" int gpf_ensemble_probes_read(gpf_ensemble* e, int member, double* out, int64_t capacity_records, int64_t* first_step, int64_t* n_records) {
     if (!e || !n_records) return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_read: null argument (e and n_records are required)");
-    if (member < 0 || member >= (int)e->members.size())
-        return fail(GPF_ERR_INVALID, "gpf_ensemble_probes_read: member " + std::to_string(member) + " outside 0 .. " + std::to_string(e->members.size() - 1));
-    if (!e->probes.armed()) return fail(GPF_ERR_STATE, "gpf_ensemble_probes_read: no probes are set (gpf_ensemble_probes_set)");
-    const size_t per = (size_t)e->probes.n[member] * e->probes.nv;
-    const int64_t have = (int64_t)(e->probes.host[member].size() / per), take = std::max<int64_t>(0, std::min(have, capacity_records));
-    *n_records = have;
-    if (first_step) *first_step = e->probes.first[member];
-    if (out && take > 0) std::memcpy(out, e->probes.host[member].data(), (size_t)take * per * sizeof(double));
+    GPF_TRY(ensemble_member_check(e, member, "gpf_ensemble_probes_read"));
+    if (!e->probes.every) return fail(GPF_ERR_STATE, "gpf_ensemble_probes_read: no probes are set (gpf_ensemble_probes_set)");
+    SeriesStore& r = e->probes.last[member];
+    series_read(r.steps, capacity_records, nullptr, n_records, e->probes.read_channel(0, member, r.host, out));
+    if (first_step) *first_step = e->probes_first[member];      // the member's step count at the start of the call + 1, record or none
     return GPF_OK;
 }

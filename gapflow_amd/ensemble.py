@@ -27,13 +27,27 @@ import ctypes as C
 import itertools
 import os
 import signal
+from collections import namedtuple
 from datetime import datetime
 
 import numpy as np
 
 from . import _lib
-from .problem import Problem, ProbeSeries, _extrema_series, _film_series, _in_main_thread, _save_extrema_series, _termination_signals
+from .problem import (Problem, _extrema_series, _film_series, _in_main_thread, _probe_series, _save_extrema_series, _save_film_series,
+                      _save_probe_series, _termination_signals)
 from .series import ALL_SERIES, _Series, _extrema_stride, _integral_sections, _integral_stride, _probe_cells
+
+
+# The ensemble's series, in the order _advance collects them and run() writes them, as series.ALL_SERIES lists a Problem's.
+# marker: the Ensemble attribute that is None while the series is off (its set_* sets it, and the per-member _Series list);
+# clear: the library's entry point that disarms it; collect(i, entries, before), view(i): Ensemble's methods -- member i's records
+# of a call to its _Series, its series as the named tuple Problem gives; save(outdir, view): the file a solo run writes.
+_Row = namedtuple('_Row', 'marker clear collect view save')
+ENSEMBLE_SERIES = {
+    'integrals': _Row('_integral_every', 'gpf_ensemble_integrals_clear', '_collect_integrals', '_member_integrals', _save_film_series),
+    'extrema': _Row('_extrema_every', 'gpf_ensemble_extrema_clear', '_collect_extrema', '_member_extrema', _save_extrema_series),
+    'probes': _Row('_probe_cells', 'gpf_ensemble_probes_clear', '_collect_probes', '_member_probes', _save_probe_series),
+}
 
 
 def member_tier(nx, ny):
@@ -213,7 +227,7 @@ class Ensemble:
         arr = (C.c_int64 * len(ps))(*[int(n) for n in counts])
         nexec = (C.c_int64 * len(ps))()
         _lib.check(self._lib.gpf_ensemble_step(self._e, arr, int(honor_stop), nexec))
-        out = []
+        out, armed = [], self._armed()
         for i, (p, n) in enumerate(zip(ps, counts)):
             if n == 0:
                 out.append([])
@@ -222,9 +236,8 @@ class Ensemble:
             _lib.check(self._lib.gpf_ensemble_log(self._e, i, log, n, None))
             before = p.step
             out.append(p._absorb_batch(log, n, int(nexec[i]) - before, before))
-            self._collect_integrals(i, out[-1], before)
-            self._collect_extrema(i, out[-1], before)
-            self._collect_probes(i, out[-1])
+            for row in armed:
+                getattr(self, row.collect)(i, out[-1], before)
         return out
 
     def step(self, n):
@@ -264,12 +277,8 @@ class Ensemble:
                     p._run_end(cfs[i], keep_open)
                     if keep_open or p.options['silent']:
                         continue
-                    if self._integral_every is not None:
-                        np.savez(os.path.join(p.outdir, 'integrals.npz'), **self._member_integrals(i)._asdict())
-                    if self._extrema_every is not None:         # the arrays a solo run's extrema.npz / probes.npz hold
-                        _save_extrema_series(p.outdir, _extrema_series(self._extrema_series[i]))
-                    if self._probe_cells is not None:
-                        np.savez(os.path.join(p.outdir, 'probes.npz'), **{k: v for k, v in self._member_probes(i)._asdict().items() if v is not None})
+                    for row in self._armed():            # the arrays a solo run's integrals.npz / extrema.npz / probes.npz hold
+                        row.save(p.outdir, getattr(self, row.view)(i))
 
         try:
             retire()
@@ -283,6 +292,23 @@ class Ensemble:
         finally:
             for s, hdl in old.items():
                 signal.signal(s, hdl)
+
+    # -------------------------------------------------------------------------------------
+    # the series (ENSEMBLE_SERIES above): what they share
+    # -------------------------------------------------------------------------------------
+    def _armed(self):
+        """The rows of the series that are armed: the only ones whose collect and view may be called."""
+        return [row for row in ENSEMBLE_SERIES.values() if getattr(self, row.marker) is not None]
+
+    def _clear(self, row):
+        if getattr(self, row.marker) is not None:
+            _lib.check(getattr(self._lib, row.clear)(self._e))
+        setattr(self, row.marker, None)
+
+    def _views(self, row):
+        if getattr(self, row.marker) is None:
+            return None
+        return [getattr(self, row.view)(i) for i in range(len(self.problems))]
 
     # -------------------------------------------------------------------------------------
     # film-integral series (DESIGN.md 3.3m)
@@ -311,14 +337,11 @@ class Ensemble:
 
     def clear_integrals(self):
         """Stop recording and drop the series."""
-        if self._integral_every is not None:
-            _lib.check(self._lib.gpf_ensemble_integrals_clear(self._e))
-        self._integral_every = None
+        self._clear(ENSEMBLE_SERIES['integrals'])
 
     def _collect_integrals(self, i, entries, before):
-        """Member i's records of the call that took its step count from `before` through `entries` (its committed steps)."""
-        if self._integral_every is None:
-            return
+        """Member i's records of the call that took its step count from `before` through `entries` (its committed steps).
+        Only while the series is armed (_advance calls it through _armed())."""
         sx, sy = self._integral_sections[i]
 
         def read(b, n, steps, have):
@@ -332,9 +355,7 @@ class Ensemble:
     def integrals(self):
         """One FilmIntegrals(step, time, load, ..., flow_x, flow_y, sections_x, sections_y) per member -- `Problem.integrals`'
         type -- of every recorded step since set_integrals, across `step()` and `run()` calls; None when none are armed."""
-        if self._integral_every is None:
-            return None
-        return [self._member_integrals(i) for i in range(len(self.problems))]
+        return self._views(ENSEMBLE_SERIES['integrals'])
 
     # -------------------------------------------------------------------------------------
     # extrema series and point probes (DESIGN.md 3.3s)
@@ -352,27 +373,25 @@ class Ensemble:
 
     def clear_extrema(self):
         """Stop recording and drop the series."""
-        if self._extrema_every is not None:
-            _lib.check(self._lib.gpf_ensemble_extrema_clear(self._e))
-        self._extrema_every = None
+        self._clear(ENSEMBLE_SERIES['extrema'])
 
     def _collect_extrema(self, i, entries, before):
-        """Member i's records of the call that took its step count from `before` through `entries` (its committed steps)."""
-        if self._extrema_every is None:
-            return
+        """Member i's records of the call that took its step count from `before` through `entries` (its committed steps).
+        Only while the series is armed (_advance calls it through _armed())."""
         nq = len(_lib.EXTREMA_NAMES)
 
         def read(b, n, steps, have):
             _lib.check(self._lib.gpf_ensemble_extrema_read(self._e, i, _lib.as_dp(b[0]), b[1].ctypes.data_as(C.POINTER(C.c_int32)), n, steps, have))
         self._extrema_series[i].collect(read, entries, before, [((nq,), np.float64), ((nq, 2), np.int32)])
 
+    def _member_extrema(self, i):
+        return _extrema_series(self._extrema_series[i])
+
     @property
     def extrema(self):
         """One FieldExtrema(step, time, p_max, ..., v_max, cells, index) per member -- `Problem.extrema`'s type -- of every recorded
         step since set_extrema, across `step()` and `run()` calls; None when none are armed."""
-        if self._extrema_every is None:
-            return None
-        return [_extrema_series(rec) for rec in self._extrema_series]
+        return self._views(ENSEMBLE_SERIES['extrema'])
 
     def set_probes(self, cells, pressure=True):
         """Record `Problem.set_probes`' record -- rho, jx, jy (and p) at `cells` -- for EVERY member after each of its committed
@@ -405,32 +424,24 @@ class Ensemble:
 
     def clear_probes(self):
         """Stop recording and drop the series."""
-        if self._probe_cells is not None:
-            _lib.check(self._lib.gpf_ensemble_probes_clear(self._e))
-        self._probe_cells = None
+        self._clear(ENSEMBLE_SERIES['probes'])
 
-    def _collect_probes(self, i, entries):
-        """Member i's probe records of the call that returned `entries` (its committed steps' scalar records)."""
-        if self._probe_cells is None:
-            return
+    def _collect_probes(self, i, entries, before=None):
+        """Member i's probe records of the call that returned `entries` (its committed steps' scalar records).  Only while
+        probes are set (_advance calls it through _armed())."""
 
         def read(out, n, first, have):
             _lib.check(self._lib.gpf_ensemble_probes_read(self._e, i, _lib.as_dp(out), n, first, have))
         self._probe_series[i].collect_every_step(read, entries, (len(self._probe_cells[i]), 4 if self._probe_pressure else 3))
 
     def _member_probes(self, i):
-        rec, nv = self._probe_series[i], 4 if self._probe_pressure else 3
-        data = rec.stacked(0, (len(self._probe_cells[i]), nv))
-        return ProbeSeries(rec.step_array(), rec.time_array(), self._probe_cells[i].copy(), data[:, :, 0], data[:, :, 1], data[:, :, 2],
-                           data[:, :, 3] if nv == 4 else None)
+        return _probe_series(self._probe_series[i], self._probe_cells[i], self._probe_pressure)
 
     @property
     def probes(self):
         """One ProbeSeries(step, time, cells, rho, jx, jy, p) per member -- `Problem.probes`' type -- of every step committed
         since set_probes, across `step()` and `run()` calls; None when no probes are set."""
-        if self._probe_cells is None:
-            return None
-        return [self._member_probes(i) for i in range(len(self.problems))]
+        return self._views(ENSEMBLE_SERIES['probes'])
 
     # -------------------------------------------------------------------------------------
     # views

@@ -65,6 +65,18 @@ def _extrema_series(rec):
                         {name: k for k, name in enumerate(_lib.EXTREMA_NAMES)})
 
 
+def _probe_series(rec, cells, pressure):
+    """ProbeSeries of the records the _Series `rec` holds, taken at `cells` with or without p (Problem's and an Ensemble member's)."""
+    nv = 4 if pressure else 3
+    data = rec.stacked(0, (len(cells), nv))
+    return ProbeSeries(rec.step_array(), rec.time_array(), cells.copy(), data[:, :, 0], data[:, :, 1], data[:, :, 2], data[:, :, 3] if nv == 4 else None)
+
+
+def _save_probe_series(outdir, series):
+    """probes.npz of a ProbeSeries (no p where none was asked for)"""
+    np.savez(os.path.join(outdir, 'probes.npz'), **{k: v for k, v in series._asdict().items() if v is not None})
+
+
 def _save_film_series(outdir, series):
     """integrals.npz of a FilmIntegrals"""
     np.savez(os.path.join(outdir, 'integrals.npz'), **series._asdict())
@@ -603,10 +615,7 @@ class Problem:
         the same steps; p is None unless pressure was asked for."""
         if self._probe_cells is None:
             return None
-        rec, nv = self._probe_rec, 4 if self._probe_pressure else 3
-        data = rec.stacked(0, (len(self._probe_cells), nv))
-        return ProbeSeries(rec.step_array(), rec.time_array(), self._probe_cells.copy(), data[:, :, 0], data[:, :, 1], data[:, :, 2],
-                           data[:, :, 3] if nv == 4 else None)
+        return _probe_series(self._probe_rec, self._probe_cells, self._probe_pressure)
 
     def _collect_probes(self, entries, before=None):
         """The probe records of the stepping call that returned `entries` (its committed steps' scalar records)."""
@@ -618,9 +627,7 @@ class Problem:
         self._probe_rec.collect_every_step(read, entries, (len(self._probe_cells), 4 if self._probe_pressure else 3))
 
     def _write_probes(self):
-        s = self.probes
-        arrays = {k: v for k, v in s._asdict().items() if v is not None}
-        np.savez(os.path.join(self.outdir, 'probes.npz'), **arrays)
+        _save_probe_series(self.outdir, self.probes)
 
     # -------------------------------------------------------------------------------------
     # film integrals (no reference counterpart)

@@ -1021,7 +1021,10 @@ int gpf_frames_time(gpf_handle* h, int64_t n, int mode, double* ms);
  *                         member its first and last interior row / column (one where the extent is 1).  Explicit sections
  *                         hold for all members and must lie inside every member's interior: GPF_ERR_INVALID with a message that
  *                         names the member and the section otherwise, and for every < 1 or more than 8 sections; nothing is
- *                         changed then.  Allocates, per member, LOG_CAPACITY / every + 1 records and its arguments on the device.
+ *                         changed then.  Allocates, per member, LOG_CAPACITY / every + 1 records and its arguments on the device:
+ *                         the new series is built first and swapped in last, as the extrema's and the probes' are, so that a
+ *                         set that fails on the device (GPF_ERR_HIP) too leaves the armed series, its stride and its records
+ *                         as they were.
  *   gpf_ensemble_integrals_clear  disarms and frees them.
  *   gpf_ensemble_integrals_read   the records member `member` left in the LAST gpf_ensemble_step, [record][9 + nsx + nsy], and
  *                         the step count of each in steps_out (either may be NULL); *n_records (required) how many -- the
