@@ -34,11 +34,8 @@ static int changes_buffers(gpf_handle* h) {
         DBG("changes_buffers: k_change_partial takes %s pair loads", changes_wide_ok(h) ? "16-byte" : "8-byte");       // (GPF_DEBUG: the narrow-load test reads this)
         HIP_TRY(hipMalloc(&h->chg.rec, slots * CHANGE_NREC * sizeof(double)));
     }
-    if (!h->chg.cell) HIP_TRY(hipMalloc(&h->chg.cell, slots * 2 * CHANGE_NMAX * sizeof(int)));
     if (!h->chg.part) HIP_TRY(hipMalloc(&h->chg.part, nx * CHANGE_NSUM * sizeof(double)));
-    if (!h->chg.row_val) HIP_TRY(hipMalloc(&h->chg.row_val, nx * CHANGE_NMAX * sizeof(double)));
-    if (!h->chg.row_iy) HIP_TRY(hipMalloc(&h->chg.row_iy, nx * CHANGE_NMAX * sizeof(int)));
-    return GPF_OK;
+    return series_first_buffers(h, CHANGE_NMAX, h->chg.cell, h->chg.row_val, h->chg.row_iy);
 }
 
 // A stepping call begins: its records replace those of the call before

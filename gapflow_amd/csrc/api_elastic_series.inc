@@ -26,11 +26,8 @@ static int eldef_buffers(gpf_handle* h) {
         DBG("eldef_buffers: k_eldef_partial takes %s pair loads", eldef_wide_ok(h) ? "16-byte" : "8-byte");     // (GPF_DEBUG: the narrow-load test reads this)
         HIP_TRY(hipMalloc(&d.rec, slots * ELDEF_NREC * sizeof(double)));
     }
-    if (!d.cell) HIP_TRY(hipMalloc(&d.cell, slots * 2 * ELDEF_NEXT * sizeof(int)));
     if (!d.part) HIP_TRY(hipMalloc(&d.part, nx * ELDEF_NSUM * sizeof(double)));
-    if (!d.row_val) HIP_TRY(hipMalloc(&d.row_val, nx * ELDEF_NEXT * sizeof(double)));
-    if (!d.row_iy) HIP_TRY(hipMalloc(&d.row_iy, nx * ELDEF_NEXT * sizeof(int)));
-    return GPF_OK;
+    return series_first_buffers(h, ELDEF_NEXT, d.cell, d.row_val, d.row_iy);
 }
 
 // A stepping call begins: its records replace those of the call before

@@ -18,15 +18,13 @@ static bool extrema_wide_ok(const gpf_handle* h) { return series_wide_ok(h, h->e
 // memory, on first use.  `dev` is set last, once everything it describes is in place.
 static int extrema_buffers(gpf_handle* h) {
     ExtremaArgs& a = h->extr.a;
-    const size_t slots = (size_t)h->log_cap + 1, nx = (size_t)h->L.Nx;
+    const size_t slots = (size_t)h->log_cap + 1;
     if (!a.val) {
         h->extr.narrow = std::getenv("GPF_FILM_NARROW") != nullptr;
         DBG("extrema_buffers: k_extrema_partial takes %s pair loads", extrema_wide_ok(h) ? "16-byte" : "8-byte");      // (GPF_DEBUG: the narrow-load test reads this)
         HIP_TRY(hipMalloc(&a.val, slots * EXTREMA_NQ * sizeof(double)));
     }
-    if (!a.cell) HIP_TRY(hipMalloc(&a.cell, slots * 2 * EXTREMA_NQ * sizeof(int)));
-    if (!a.row_val) HIP_TRY(hipMalloc(&a.row_val, nx * EXTREMA_NQ * sizeof(double)));
-    if (!a.row_iy) HIP_TRY(hipMalloc(&a.row_iy, nx * EXTREMA_NQ * sizeof(int)));
+    GPF_TRY(series_first_buffers(h, EXTREMA_NQ, a.cell, a.row_val, a.row_iy));
     a.cap = h->log_cap;
     if (!h->extr.dev) {
         ExtremaArgs* dev = nullptr;

@@ -95,6 +95,16 @@ template <class Args> static void series_row_args(const gpf_handle* h, bool wide
     f.slot = slot; f.cap = h->log_cap;
 }
 
+// What a series with n first candidates (series_first.hpp) keeps beside its values, on first use: the cells of its records,
+// cell [log_cap + 1][n][2], and the row scratch its row kernel hands its fold, row_val [Nx][n] and row_iy [Nx][n]
+static int series_first_buffers(const gpf_handle* h, size_t n, int*& cell, double*& row_val, int*& row_iy) {
+    const size_t slots = (size_t)h->log_cap + 1, nx = (size_t)h->L.Nx;
+    if (!cell) HIP_TRY(hipMalloc(&cell, slots * 2 * n * sizeof(int)));
+    if (!row_val) HIP_TRY(hipMalloc(&row_val, nx * n * sizeof(double)));
+    if (!row_iy) HIP_TRY(hipMalloc(&row_iy, nx * n * sizeof(int)));
+    return GPF_OK;
+}
+
 // The two launches on the handle's stream, partial<EOS, HAS_LS> on `grid` (x: the interior rows) and fold on grid.y workgroups:
 // the record if the step count is `expect`.  Returns from the calling function on a launch error.  `grid` and `f`: variables.
 #define SERIES_ROWS_ENQUEUE(h, partial, fold, grid, f, expect)                                                                   \

@@ -10,23 +10,19 @@
 // launches these kernels only then.  d of neighbouring states is a difference of nearly equal numbers and therefore (almost
 // always) exact, which is why dmass resolves the mass defect of one step where the difference of two global sums does not.
 //
-// The two launches per record, the guard, the pair order, the fold tree and the row loop are series_rows.hpp's:
+// The two launches per record, the guard, the fold tree and the row loop of the sums are series_rows.hpp's; the maxima -- their
+// order, accumulator, folds and stores -- are series_first.hpp's.  The pair walk is plane_pairs' rule on the kernel's
+// own code: through plane_pairs its seven planes cost k_change_partial 9 VGPRs (66 -> 75) and a wave per SIMD (7 -> 6).
 //   k_change_partial   one 256-thread workgroup per interior row; reads 7 planes (three of each buffer and h: 56 B per cell) once;
 //                      thread 0 stores the row's seven sums and its three maxima with their columns.
 //   k_change_fold      one workgroup; thread 0 applies dx dy, copies dt_last and stores the record.
-// The walk is the kernel's own, beside series_rows.hpp: row_pairs and not inside it -- that one fetches one buffer of q and the
-// three gap planes for CellIn, and the kernels built on it keep their registers as long as it stays as it is.  Thread t owns the
-// column pairs (1 + 2k, 2 + 2k), k = t, t + 256, ..., the lower column first, one 16-byte load per plane where the buffers allow
-// it and two 8-byte loads otherwise; the ghost column an odd Ny reaches is loaded and never handed on.  The sums go through
-// block_sum and fold_rows: who adds what depends on (Nx, Ny) alone.  Every product (d d, q q, d_rho h) is rounded on its own
-// (elastic_series_kernels.hip: the canonicalize between product and sum), so a NumPy restatement of the terms meets the device's.
-// The maxima are ordered by extrema_kernels.hip: extrema_before -- the larger |d|, then the smaller ix, then the smaller iy --, a
-// total order, so the shape of their tree does not matter.  A record is a pure function of (q^n, q^(n-1), h, dt_last): no
-// floating-point atomics, no arrival order, the same bits for every stride and for the wide and narrow loads.
+// The sums go through block_sum and fold_rows: who adds what depends on (Nx, Ny) alone.  Every product (d d, q q, d_rho h) is
+// rounded on its own (elastic_series_kernels.hip: the canonicalize between product and sum), so a NumPy restatement of the terms
+// meets the device's.  A record is a pure function of (q^n, q^(n-1), h, dt_last): no floating-point atomics, no arrival order,
+// the same bits for every stride and for the wide and narrow loads.
 #pragma once
 
-#include "series_rows.hpp"
-#include "extrema_kernels.hip"
+#include "series_first.hpp"
 
 namespace gpf {
 
@@ -49,42 +45,7 @@ struct ChangeArgs {
 };
 
 using ChangeAcc = RowAcc<CHANGE_NSUM>;
-
-// The first candidates for the three maxima under extrema_before
-struct ChangeExt {
-    double v[CHANGE_NMAX];
-    int ix[CHANGE_NMAX], iy[CHANGE_NMAX];
-    // the candidate every cell comes before (|d| >= 0)
-    __device__ __forceinline__ void none() {
-#pragma unroll
-        for (int k = 0; k < CHANGE_NMAX; ++k) { v[k] = -__builtin_huge_val(); ix[k] = EXTREMA_NO_CELL; iy[k] = EXTREMA_NO_CELL; }
-    }
-    __device__ __forceinline__ void take(int k, double x, int cx, int cy) {
-        if (extrema_before(false, x, cx, cy, v[k], ix[k], iy[k])) { v[k] = x; ix[k] = cx; iy[k] = cy; }
-    }
-};
-
-// The first candidates of the workgroup's 256 threads, valid in thread 0: lanes 32, 16, .. 1 apart, then the four waves, as the
-// extrema fold theirs.  A thread without a cell holds none(), which never displaces a cell.
-__device__ __forceinline__ ChangeExt change_block_first(ChangeExt a, ChangeExt* sm) {
-    for (int s = 32; s >= 1; s >>= 1) {
-#pragma unroll
-        for (int k = 0; k < CHANGE_NMAX; ++k) {
-            const double ov = __shfl_down(a.v[k], s);
-            const int ox = __shfl_down(a.ix[k], s), oy = __shfl_down(a.iy[k], s);
-            a.take(k, ov, ox, oy);
-        }
-    }
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < 4; ++i) {
-#pragma unroll
-            for (int k = 0; k < CHANGE_NMAX; ++k) a.take(k, sm[i].v[k], sm[i].ix[k], sm[i].iy[k]);
-        }
-    }
-    return a;
-}
+using ChangeExt = FirstAcc<CHANGE_NMAX, 0>;     // three maxima (|d| >= 0)
 
 // One cell's terms: qn, qo the three fields of the new and of the previous state, h the gap
 __device__ __forceinline__ void change_cell(ChangeAcc& a, ChangeExt& e, const double qn[3], const double qo[3], double h, int ix, int iy) {
@@ -147,16 +108,12 @@ __global__ __launch_bounds__(256) void k_change_partial(const ChangeArgs f, long
         }
     }
     const ChangeAcc r = block_sum(a, sm);
-    const ChangeExt x = change_block_first(e, sme);
+    const ChangeExt x = block_first(e, sme, 256);
     if (threadIdx.x == 0) {
         double* out = f.part + (long long)(ix - 1) * CHANGE_NSUM;
 #pragma unroll
         for (int k = 0; k < CHANGE_NSUM; ++k) out[k] = r.v[k];
-#pragma unroll
-        for (int k = 0; k < CHANGE_NMAX; ++k) {
-            f.row_val[(long long)(ix - 1) * CHANGE_NMAX + k] = x.v[k];
-            f.row_iy[(long long)(ix - 1) * CHANGE_NMAX + k] = x.iy[k];
-        }
+        store_row_first(f.row_val, f.row_iy, ix - 1, x);
     }
 }
 
@@ -166,21 +123,13 @@ __global__ __launch_bounds__(256) void k_change_fold(const ChangeArgs f, long lo
     if (series_skip(f.st, expect, f.slot, f.cap)) return;
     const int Nx = f.L.Nx;
     const ChangeAcc r = fold_rows<CHANGE_NSUM>(f.part, 0, Nx, sm);
-    ChangeExt e;
-    e.none();
-    for (int row = threadIdx.x; row < Nx; row += 256) {
-#pragma unroll
-        for (int k = 0; k < CHANGE_NMAX; ++k) e.take(k, f.row_val[(long long)row * CHANGE_NMAX + k], row + 1, f.row_iy[(long long)row * CHANGE_NMAX + k]);
-    }
-    const ChangeExt x = change_block_first(e, sme);
+    const ChangeExt x = block_first(first_of_rows<ChangeExt>(f.row_val, f.row_iy, Nx), sme, 256);
     if (threadIdx.x != 0) return;
     double* out = f.rec + f.slot * CHANGE_NREC;
-    int* c = f.cell + f.slot * 2 * CHANGE_NMAX;
     const double dA = f.dx * f.dy;
 #pragma unroll
     for (int k = 0; k < CHANGE_NSUM; ++k) out[k] = r.v[k] * dA;
-#pragma unroll
-    for (int k = 0; k < CHANGE_NMAX; ++k) { out[CHANGE_NSUM + k] = x.v[k]; c[2 * k] = x.ix[k]; c[2 * k + 1] = x.iy[k]; }
+    store_first(f.rec + CHANGE_NSUM, f.cell, f.slot, x, CHANGE_NREC);
     out[CHANGE_NREC - 1] = f.st->dt_last;
 }
 

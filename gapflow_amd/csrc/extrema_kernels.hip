@@ -1,13 +1,9 @@
 // Field extrema of the committed state, each with its cell (entry points in api_extrema.inc): the largest and smallest EOS
 // pressure and density, the smallest gap height, the largest |jx / rho| and |jy / rho|, over the interior cells 1..Nx x 1..Ny.
 //
-// ONE comparison, extrema_before, orders candidates (value, ix, iy) totally: the better value first, then the smaller ix, then
-// the smaller iy.  Every fold -- a thread over its cells, lanes over a wave, waves over a workgroup, rows over the grid -- keeps
-// the first of two candidates under that order.  The minimum of a total order does not depend on how the candidates are
-// bracketed, so the shape of the reduction tree is free: a record is a pure function of the state (no floating-point atomics,
-// no arrival order), and the wide and narrow loads, the row kernels and the one-workgroup kernel agree in every bit.
-// A committed state has no NaN and rho >= 0 (q_is_valid).  rho = 0 makes |j / rho| inf (NaN for j = 0, which no comparison
-// ever prefers or displaces): plain IEEE, not special-cased.
+// The order on candidates (value, ix, iy), their accumulator, the workgroup fold, the row fold and the stores are
+// series_first.hpp's, which states their contract once.  A committed state has no NaN and rho >= 0 (q_is_valid).
+// rho = 0 makes |j / rho| inf (NaN for j = 0, which no comparison ever prefers or displaces): plain IEEE, not special-cased.
 //
 // Three writers, one record (seven doubles, fourteen int32):
 //   k_extrema_partial + k_extrema_fold   behind every launch-per-step step, guarded by the device's run state like k_probe_record
@@ -15,18 +11,17 @@
 //                                        (one wave per quantity)
 //   extrema_record_wide                  inside k_mid_ensemble, after commit_step, from the workspace planes in device memory
 //                                        (the whole block walks the interior once)
-// k_extrema_partial runs one 256-thread workgroup per interior row; thread t owns the column pairs (1 + 2k, 2 + 2k) for
-// k = t, t + 256, ..., fetched with one 16-byte load per plane where the buffers allow it (series_wide_ok) and with 8-byte loads
-// otherwise; the ghost column an odd Ny reaches is loaded and never compared.  It reads 4 planes (rho, jx, jy, h: 32 B per
-// cell) and stores seven (value, iy) pairs per row; k_extrema_fold folds the Nx rows in one workgroup.
+// k_extrema_partial runs one 256-thread workgroup per interior row (extrema_row_first, which the slabs' row kernel shares); it
+// reads 4 planes (rho, jx, jy, h: 32 B per cell) and stores seven (value, iy) pairs per row; k_extrema_fold folds the Nx rows in
+// one workgroup.
 #pragma once
 
-#include "series_rows.hpp"
+#include "series_first.hpp"
 
 namespace gpf {
 
 constexpr int EXTREMA_NQ = 7;       // p_max p_min rho_max rho_min h_min u_max v_max
-constexpr int EXTREMA_NO_CELL = 0x7fffffff;
+constexpr unsigned EXTREMA_MIN_MASK = 0b0011010;
 
 struct ExtremaArgs {
     double* val;            // [cap + 1][7]
@@ -36,79 +31,24 @@ struct ExtremaArgs {
     long long every, cap;   // recording stride; records a batch may leave (slot cap: gpf_extrema_now's)
 };
 
-__device__ __forceinline__ bool extrema_is_min(int k) { return k == 1 || k == 3 || k == 4; }
+using ExtAcc = FirstAcc<EXTREMA_NQ, EXTREMA_MIN_MASK>;
 
-// THE comparison: does candidate a come before candidate b?  A total order on (value, ix, iy) for values without NaN.
-__device__ __forceinline__ bool extrema_before(bool want_min, double a, int ax, int ay, double b, int bx, int by) {
-    if (a != b) return want_min ? a < b : a > b;
-    return ax != bx ? ax < bx : ay < by;
+__device__ __forceinline__ bool extrema_is_min(int k) { return ExtAcc::is_min(k); }
+
+// One cell's seven candidates
+__device__ __forceinline__ void extrema_cell(ExtAcc& a, double p, double rho, double jx, double jy, double h, int cx, int cy) {
+    a.take(0, p, cx, cy); a.take(1, p, cx, cy);
+    a.take(2, rho, cx, cy); a.take(3, rho, cx, cy);
+    a.take(4, h, cx, cy);
+    a.take(5, fabs(jx / rho), cx, cy);
+    a.take(6, fabs(jy / rho), cx, cy);
 }
 
-struct ExtAcc {
-    double v[EXTREMA_NQ];
-    int ix[EXTREMA_NQ], iy[EXTREMA_NQ];
-    // the candidate every cell comes before
-    __device__ __forceinline__ void none() {
-#pragma unroll
-        for (int k = 0; k < EXTREMA_NQ; ++k) {
-            v[k] = extrema_is_min(k) ? __builtin_huge_val() : -__builtin_huge_val();
-            ix[k] = EXTREMA_NO_CELL; iy[k] = EXTREMA_NO_CELL;
-        }
-    }
-    __device__ __forceinline__ void take(int k, double x, int cx, int cy) {
-        if (extrema_before(extrema_is_min(k), x, cx, cy, v[k], ix[k], iy[k])) { v[k] = x; ix[k] = cx; iy[k] = cy; }
-    }
-    __device__ __forceinline__ void cell(double p, double rho, double jx, double jy, double h, int cx, int cy) {
-        take(0, p, cx, cy); take(1, p, cx, cy);
-        take(2, rho, cx, cy); take(3, rho, cx, cy);
-        take(4, h, cx, cy);
-        take(5, fabs(jx / rho), cx, cy);
-        take(6, fabs(jy / rho), cx, cy);
-    }
-    __device__ __forceinline__ void merge(const ExtAcc& o) {
-#pragma unroll
-        for (int k = 0; k < EXTREMA_NQ; ++k) take(k, o.v[k], o.ix[k], o.iy[k]);
-    }
-};
-
-// The first candidate of all threads of the workgroup (blockDim.x a multiple of 64, at most 512), valid in thread 0.  Only
-// threads 0 .. nactive - 1 (nactive >= 1, block-uniform) hold candidates: the waves among them fold their lanes 32, 16, .. 1
-// apart, then thread 0 folds those waves; a wave wholly beyond nactive holds nothing and does nothing.  `sm` is written by
-// lane 0 of every such wave and read by thread 0 only: a caller that uses it again puts a barrier in between.
-__device__ __forceinline__ ExtAcc extrema_block_first(ExtAcc a, ExtAcc* sm, int nactive) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if ((w << 6) < nactive) {                           // wave-uniform
-        for (int s = 32; s >= 1; s >>= 1) {
-            ExtAcc o;
-#pragma unroll
-            for (int k = 0; k < EXTREMA_NQ; ++k) { o.v[k] = __shfl_down(a.v[k], s); o.ix[k] = __shfl_down(a.ix[k], s); o.iy[k] = __shfl_down(a.iy[k], s); }
-            a.merge(o);
-        }
-        if (lane == 0) sm[w] = a;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int nw = (nactive + 63) >> 6;
-        for (int i = 1; i < nw; ++i) a.merge(sm[i]);
-    }
-    return a;
-}
-
-__device__ __forceinline__ void extrema_store(const ExtremaArgs& x, long long slot, const ExtAcc& r) {
-    double* v = x.val + slot * EXTREMA_NQ;
-    int* c = x.cell + slot * 2 * EXTREMA_NQ;
-#pragma unroll
-    for (int k = 0; k < EXTREMA_NQ; ++k) { v[k] = r.v[k]; c[2 * k] = r.ix[k]; c[2 * k + 1] = r.iy[k]; }
-}
-
+// The first candidates of interior row ix of the state q over the gap topo, by the row's 256-thread workgroup, valid in thread 0.
+// The pair walk is plane_pairs' rule on this function's own code: through plane_pairs the two row kernels took 6 scalar registers
+// fewer in every instantiation and a record on a 260 x 522 grid 0.5 us (2 %) longer.
 template <int EOS>
-__global__ __launch_bounds__(256) void k_extrema_partial(const double* qa, const double* qb, const double* topo, const StepState* st,
-                                                         const Layout L, const Phys P, const ExtremaArgs x, int wide, long long expect,
-                                                         long long slot) {
-    __shared__ ExtAcc sm[4];
-    if (series_skip(st, expect, slot, x.cap)) return;
-    const int ix = 1 + blockIdx.x;
-    const double* q = st->parity ? qb : qa;
+__device__ __forceinline__ ExtAcc extrema_row_first(const double* q, const double* topo, const Layout& L, const Phys& P, int wide, int ix, ExtAcc* sm) {
     ExtAcc a;
     a.none();
     const int npair = (L.Ny + 1) / 2;
@@ -127,31 +67,28 @@ __global__ __launch_bounds__(256) void k_extrema_partial(const double* qa, const
             for (int p = 0; p < 3; ++p) in[p] = series_d2{q[p * L.plane + o], q[p * L.plane + o1]};
             in[3] = series_d2{topo[o], topo[o1]};
         }
-        a.cell(eos_pressure<EOS>(in[0].x, P), in[0].x, in[1].x, in[2].x, in[3].x, ix, iy);
-        if (two) a.cell(eos_pressure<EOS>(in[0].y, P), in[0].y, in[1].y, in[2].y, in[3].y, ix, iy + 1);
+        extrema_cell(a, eos_pressure<EOS>(in[0].x, P), in[0].x, in[1].x, in[2].x, in[3].x, ix, iy);
+        if (two) extrema_cell(a, eos_pressure<EOS>(in[0].y, P), in[0].y, in[1].y, in[2].y, in[3].y, ix, iy + 1);
     }
-    const ExtAcc r = extrema_block_first(a, sm, npair < 256 ? npair : 256);
-    if (threadIdx.x == 0) {
-        double* v = x.row_val + (long long)(ix - 1) * EXTREMA_NQ;
-        int* c = x.row_iy + (long long)(ix - 1) * EXTREMA_NQ;
-#pragma unroll
-        for (int k = 0; k < EXTREMA_NQ; ++k) { v[k] = r.v[k]; c[k] = r.iy[k]; }
-    }
+    return block_first(a, sm, npair < 256 ? npair : 256);
+}
+
+template <int EOS>
+__global__ __launch_bounds__(256) void k_extrema_partial(const double* qa, const double* qb, const double* topo, const StepState* st,
+                                                         const Layout L, const Phys P, const ExtremaArgs x, int wide, long long expect,
+                                                         long long slot) {
+    __shared__ ExtAcc sm[4];
+    if (series_skip(st, expect, slot, x.cap)) return;
+    const int ix = 1 + blockIdx.x;
+    const ExtAcc r = extrema_row_first<EOS>(st->parity ? qb : qa, topo, L, P, wide, ix, sm);
+    if (threadIdx.x == 0) store_row_first(x.row_val, x.row_iy, ix - 1, r);
 }
 
 __global__ __launch_bounds__(256) void k_extrema_fold(const StepState* st, const ExtremaArgs x, int Nx, long long expect, long long slot) {
     __shared__ ExtAcc sm[4];
     if (series_skip(st, expect, slot, x.cap)) return;
-    ExtAcc a;
-    a.none();
-    for (int row = threadIdx.x; row < Nx; row += 256) {
-        const double* v = x.row_val + (long long)row * EXTREMA_NQ;
-        const int* c = x.row_iy + (long long)row * EXTREMA_NQ;
-#pragma unroll
-        for (int k = 0; k < EXTREMA_NQ; ++k) a.take(k, v[k], row + 1, c[k]);
-    }
-    const ExtAcc r = extrema_block_first(a, sm, Nx < 256 ? Nx : 256);
-    if (threadIdx.x == 0) extrema_store(x, slot, r);
+    const ExtAcc r = block_first(first_of_rows<ExtAcc>(x.row_val, x.row_iy, Nx), sm, Nx < 256 ? Nx : 256);
+    if (threadIdx.x == 0) store_first(x.val, x.cell, slot, r);
 }
 
 // The same record from the dense LDS field of k_small_steps (q: planes of nc cells, rows of w; h: the gap plane): the whole
@@ -197,10 +134,9 @@ __device__ __forceinline__ void extrema_record_block(const ExtremaArgs& x, const
 // interior cells: one wave per quantity would leave each lane some 250 cells, a division per cell and seven walks, against a
 // step whose passes give a thread about 32 cells.  So here the WHOLE block (blockDim.x threads, a multiple of 64, at most 512)
 // walks the interior once -- thread t takes the interior cells t, t + blockDim.x, ... in row-major order, a MidCursor of width
-// Ny in place of a division per cell --, every thread keeps all seven candidates (ExtAcc::cell: the expressions of
-// k_extrema_partial, so p, u_max and v_max carry the same bits), and extrema_block_first folds them: lanes, then the waves'
-// firsts in `sm` (one ExtAcc per wave).  A thread without a cell holds none(), which every cell comes before.  The order is
-// total, so the walk's shape does not show in the record.
+// Ny in place of a division per cell --, every thread keeps all seven candidates (extrema_cell: the expressions of
+// k_extrema_partial, so p, u_max and v_max carry the same bits), and block_first folds them through `sm` (one ExtAcc per wave).
+// The order is total, so the walk's shape does not show in the record.
 // Block-uniform; reads only.  The caller has a workgroup barrier between the stores that made q and this call (the planes are
 // in device memory: the barrier is their release / acquire), and one between two calls (`sm` is used again).
 template <int EOS>
@@ -215,10 +151,10 @@ __device__ __forceinline__ void extrema_record_wide(const ExtremaArgs& x, const 
         const int ix = 1 + k.ix, iy = 1 + k.iy;
         const int c = ix * w + iy;
         const double rho = q[c];
-        a.cell(eos_pressure<EOS>(rho, P), rho, q[nc + c], q[2 * nc + c], h[c], ix, iy);
+        extrema_cell(a, eos_pressure<EOS>(rho, P), rho, q[nc + c], q[2 * nc + c], h[c], ix, iy);
     }
-    const ExtAcc r = extrema_block_first(a, sm, nt);
-    if (threadIdx.x == 0) extrema_store(x, slot, r);
+    const ExtAcc r = block_first(a, sm, nt);
+    if (threadIdx.x == 0) store_first(x.val, x.cell, slot, r);
 }
 
 }  // namespace gpf

@@ -14,7 +14,8 @@
 // record is a pure function of the state -- no floating-point atomics, no arrival order, no ticket.  The series' bit-for-bit
 // claims (a plane of ones reproduces the film integrals, a region equals the weighted integral of its mask, film_record_block
 // replays the two launches) hold because this walk, this tree and this row loop are the only ones.
-// k_extrema_partial walks its row the same way on its own code: through row_pairs its scalar registers differ from before.
+// The series that keep a maximum or a minimum with its cell walk their rows the same way over their own planes and fold their
+// first candidates through the companion header, series_first.hpp.
 // A new row-reduced series is a plane selection, a cell functor and the epilogues of its two kernels.
 #pragma once
 

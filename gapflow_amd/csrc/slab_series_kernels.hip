@@ -8,15 +8,17 @@
 //                           centre x is spelled from the GLOBAL row, ((double)(ix + row0) - 0.5) * dx -- for the global row
 //                           ix + row0 the very expression k_film_partial evaluates.  The row's [FILM_NV] goes into this rank's
 //                           message at local row ix - 1.  The y-sections' columns are global already.
-//   k_slab_extrema_partial  k_extrema_partial's walk (ExtAcc, extrema_block_first); the row's seven (value, iy) go into the message
-//                           behind the film vector, iy as a double (exact), so that ONE all-gather of doubles carries both series.
+//   k_slab_extrema_partial  k_extrema_partial's row (extrema_kernels.hip: extrema_row_first); the row's seven (value, iy) go into the
+//                           message behind the film vector, iy as a double (exact), so that ONE all-gather of doubles carries both
+//                           series.
 //   (the host gathers the messages: gathered[world][max_nx][SLAB_SERIES_W], slab_rows.hpp)
 //   k_slab_film_fold        one workgroup on every rank: thread t adds the vectors of the global rows t, t + 256, ... in that order
 //                           to +0.0 (add_rows' loop, each row found through slab_rows.hpp), block_sum, then k_film_fold's epilogue:
 //                           dx dy on the nine sums, the gathered row of global section sx[k] times dy, the folded section slots
 //                           times dx.  The same expression tree over the same operands as fold_rows + k_film_fold: the same bits.
-//   k_slab_extrema_fold     k_extrema_fold's fold with ix = g + 1, the global row in the ghosted index space.  The order on
-//                           (value, ix, iy) is total, so the bracket is free.
+//   k_slab_extrema_fold     k_extrema_fold's fold with ix = g + 1, the global row in the ghosted index space, on a row loop of its
+//                           own (the rows are found through slab_rows.hpp, the columns read back from doubles); block_first and
+//                           store_first are series_first.hpp's.  The order on (value, ix, iy) is total, so the bracket is free.
 // Every rank folds the same gathered buffer in the same order, so every rank holds the same record, as it holds the same dt.
 // A record is a pure function of the domain's state: no floating-point atomics, no arrival order.  Padding rows of the gathered
 // buffer (local rows >= a rank's own count) are never read.  All four kernels are guarded by series_skip like every recorder; the
@@ -109,31 +111,8 @@ template <int EOS>
 __global__ __launch_bounds__(256) void k_slab_extrema_partial(const SlabExtremaArgs e, const Phys P, long long expect) {
     __shared__ ExtAcc sm[4];
     if (series_skip(e.st, expect, e.slot, e.x.cap)) return;
-    const Layout& L = e.L;
     const int ix = 1 + blockIdx.x;
-    const double* q = e.st->parity ? e.qb : e.qa;
-    ExtAcc a;
-    a.none();
-    const int npair = (L.Ny + 1) / 2;
-    for (int k = threadIdx.x; k < npair; k += 256) {
-        const int iy = 1 + 2 * k;
-        const bool two = iy + 1 <= L.Ny;
-        const long long o = L.at(ix, iy);
-        series_d2 in[4];
-        if (e.wide) {
-#pragma unroll
-            for (int p = 0; p < 3; ++p) in[p] = *reinterpret_cast<const series_d2*>(q + p * L.plane + o);
-            in[3] = *reinterpret_cast<const series_d2*>(e.topo + o);
-        } else {
-            const long long o1 = two ? o + 1 : o;
-#pragma unroll
-            for (int p = 0; p < 3; ++p) in[p] = series_d2{q[p * L.plane + o], q[p * L.plane + o1]};
-            in[3] = series_d2{e.topo[o], e.topo[o1]};
-        }
-        a.cell(eos_pressure<EOS>(in[0].x, P), in[0].x, in[1].x, in[2].x, in[3].x, ix, iy);
-        if (two) a.cell(eos_pressure<EOS>(in[0].y, P), in[0].y, in[1].y, in[2].y, in[3].y, ix, iy + 1);
-    }
-    const ExtAcc r = extrema_block_first(a, sm, npair < 256 ? npair : 256);
+    const ExtAcc r = extrema_row_first<EOS>(e.st->parity ? e.qb : e.qa, e.topo, e.L, P, e.wide, ix, sm);
     if (threadIdx.x == 0) {
         double* out = e.msg + (long long)(ix - 1) * SLAB_SERIES_W + SLAB_SERIES_EXT;
 #pragma unroll
@@ -151,9 +130,9 @@ __global__ __launch_bounds__(256) void k_slab_extrema_fold(const SlabExtremaArgs
 #pragma unroll
         for (int k = 0; k < EXTREMA_NQ; ++k) a.take(k, in[k], g + 1, (int)in[EXTREMA_NQ + k]);
     }
-    const ExtAcc r = extrema_block_first(a, sm, e.nx_global < 256 ? e.nx_global : 256);
+    const ExtAcc r = block_first(a, sm, e.nx_global < 256 ? e.nx_global : 256);
     if (threadIdx.x == 0) {
-        extrema_store(e.x, e.slot, r);
+        store_first(e.x.val, e.x.cell, e.slot, r);
         e.time[e.slot] = e.st->simtime;
     }
 }

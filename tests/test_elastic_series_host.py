@@ -151,7 +151,7 @@ def tree_sum(term):
 
 
 def before(want_min, a, ax, ay, b, bx, by):
-    """extrema_kernels.hip: extrema_before."""
+    """series_first.hpp: extrema_before."""
     if a != b:
         return a < b if want_min else a > b
     return ax < bx if ax != bx else ay < by

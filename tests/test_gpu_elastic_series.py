@@ -53,6 +53,7 @@ GRIDS = {
     '48x30': "Lx: 0.0762, Ly: 0.04, Nx: 48, Ny: 30",
     '48x31': "Lx: 0.0762, Ly: 0.04, Nx: 48, Ny: 31",
     '260x6': "Lx: 0.0762, Ly: 0.04, Nx: 260, Ny: 6",
+    '6x150': "Lx: 0.009525, Ly: 0.2, Nx: 6, Ny: 150",           # the cells of 48x30; 75 column pairs: two waves, the second partly filled
     'free-48x30': f"Lx: 0.0762, Ly: 0.04, Nx: 48, Ny: 30, {DN}",
 }
 SHAPES = sorted(GRIDS)

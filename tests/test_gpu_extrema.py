@@ -270,8 +270,33 @@ def test_narrow_loads_give_the_same_bits(hiplib, tmp_path):
 # ---------------------------------------------------------------------------------------------------------------------------
 # 3. ties
 # ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('nx,ny', [(12, 9), (40, 70)], ids=['small-kernel-size', 'two-launch-size'])
+# Tied cells planted into the flat state, per shape a list of (cells of the maxima, cells of the minima), chosen so that a tie
+# crosses every boundary of the shared fold (csrc/series_first.hpp).  A row's workgroup gives thread t the column pairs
+# (1 + 2k, 2 + 2k), k = t, t + 256, ...; lanes fold inside a wave of 64, thread 0 folds the waves, and the fold kernel gives thread
+# t the rows t, t + 256, ...:
+#   3 x 5      3 pairs: one partly filled wave
+#   5 x 130    65 pairs: columns 128 | 129 are lane 63 of wave 0 and lane 0 of wave 1
+#   2 x 515    258 pairs, the pair loop wraps: columns 513, 514 are thread 0's second pair, columns 3, 4 thread 1's first -- the
+#              lower thread holds the later cell; column 515 shares its pair with the ghost column
+#   258 x 4    the row loop wraps: row 257 is thread 0's second, row 2 thread 1's first
+TIED = {
+    (12, 9): [([(5, 9), (5, 2), (11, 1)], [(12, 9), (3, 3), (3, 8)])],
+    (40, 70): [([(20, 66), (20, 65), (39, 1)], [(7, 70), (7, 1), (40, 2)])],
+    (3, 5): [([(2, 5), (2, 3), (3, 1)], [(1, 5), (1, 4), (3, 2)]), ([(3, 5), (3, 4)], [(3, 1), (2, 2)])],
+    (5, 130): [([(3, 129), (3, 128), (5, 1)], [(2, 130), (2, 129), (4, 64)]), ([(4, 130), (4, 127)], [(1, 129), (1, 128)])],
+    (2, 515): [([(1, 513), (1, 4), (2, 1)], [(2, 515), (2, 512), (2, 3)]), ([(1, 513), (1, 512)], [(2, 515), (2, 514)]),
+               ([(2, 514), (2, 259)], [(1, 515), (1, 258), (1, 257)])],
+    (258, 4): [([(257, 1), (2, 3), (258, 1)], [(257, 4), (258, 2), (3, 1)]), ([(257, 1), (256, 4)], [(257, 2), (1, 4)]),
+               ([(258, 4), (258, 3)], [(130, 2), (129, 3)])],
+}
+
+
+@pytest.mark.parametrize('nx,ny', list(TIED), ids=['small-kernel-size', 'two-launch-size'] + [f'{nx}x{ny}' for nx, ny in list(TIED)[2:]])
 def test_ties_go_to_the_first_cell(hiplib, nx, ny):
+    """The flat gap under the uniform state ties in every cell: every record belongs to (1, 1).  Then the tied sets of TIED,
+    written into p.q and topo.h before the first step: rho (so p_max, rho_max) and jy (v_max) raised in the cells of the maxima,
+    rho (p_min, rho_min, and u_max through |jx / rho|) and h (h_min) lowered in the cells of the minima, to one value each.  The
+    expectation is NumPy's first hit in the row-major interior of the planted arrays; the library is not asked."""
     p = build(FLAT.format(nx=nx, ny=ny))
     q, h = p.q, p.topo.h
     for f in state_fields(q, h).values():
@@ -280,6 +305,61 @@ def test_ties_go_to_the_first_cell(hiplib, nx, ny):
     for name in NAMES:
         assert r[name + '_cell'] == (1, 1), name
     assert bits(r['rho_max']) == bits(q[0, 1, 1]) and bits(r['h_min']) == bits(h[1, 1]) and bits(r['u_max']) == bits(abs(q[1, 1, 1] / q[0, 1, 1]))
+    q0, h0 = q.copy(), h.copy()
+    assert q0[0, 1, 1] > 0. and q0[1, 1, 1] != 0. and h0[1, 1] > 0.
+    for hi, lo in TIED[(nx, ny)]:
+        assert not set(hi) & set(lo) and all(1 <= ix <= nx and 1 <= iy <= ny for ix, iy in hi + lo)
+        q, hp = p.q, h0.copy()
+        q[...] = q0
+        for ix, iy in hi:
+            q[0, ix, iy] = (1. + 2. ** -10) * q0[0, 1, 1]
+            q[2, ix, iy] = 1e-3
+        for ix, iy in lo:
+            q[0, ix, iy] = (1. - 2. ** -10) * q0[0, 1, 1]
+            hp[ix, iy] = 0.5 * h0[1, 1]
+        p.topo.h = hp
+        rec, cells = now_record(p)
+        first_hi, first_lo = min(hi), min(lo)           # the row-major first of each set ...
+        assert first_hi != hi[0] and first_lo != lo[0], 'the sets list a later cell first'
+        what = f"{nx} x {ny}, ties at {hi} and {lo}"
+        assert_record_is_the_states(rec, cells, p.q, p.topo.h, what, prop=p.prop)
+        # ... which is what NumPy found, and every quantity has its tie (no comparison above passed on a unique cell)
+        for name in NAMES:
+            assert cells[name] == (first_lo if name in ('p_min', 'rho_min', 'h_min', 'u_max') else first_hi), f"{what}: {name} at {cells[name]}"
+        for name, f in state_fields(p.q, p.topo.h).items():
+            assert occurrences(f, want_min(name)) == len(lo if name in ('rho_min', 'h_min', 'u_max') else hi), f"{what}: {name} does not tie"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 3b. a single extreme at every position
+# ---------------------------------------------------------------------------------------------------------------------------
+PLANT_PARTS = 2
+
+
+@pytest.mark.parametrize('nx,ny,part', [(nx, ny, k) for nx, ny in ((5, 130), (258, 4)) for k in range(PLANT_PARTS)],
+                         ids=lambda v: str(v))
+def test_planted_extreme_is_found_at_every_position(hiplib, nx, ny, part):
+    """One strict maximum of rho and one strict minimum of h, planted into the flat state at every interior cell in turn (rho at
+    the cell, h at its point mirror, so that the two walk the grid in opposite directions), one field_extrema() per plant: the
+    values and the cells are the planted ones, whichever thread, lane, wave and trip of the shared fold holds them.  5 x 130: 65
+    pairs, two waves in a row's workgroup.  258 x 4: the fold's row loop wraps.  The positions are dealt to PLANT_PARTS cases."""
+    p = build(FLAT.format(nx=nx, ny=ny))
+    q0, h0 = p.q.copy(), p.topo.h.copy()
+    rho_up, h_down = (1. + 2. ** -10) * q0[0, 1, 1], 0.5 * h0[1, 1]
+    positions = [(ix, iy) for ix in range(1, nx + 1) for iy in range(1, ny + 1)][part::PLANT_PARTS]
+    for ix, iy in positions:
+        mx, my = nx + 1 - ix, ny + 1 - iy
+        q, hp = p.q, h0.copy()
+        q[...] = q0
+        q[0, ix, iy] = rho_up
+        hp[mx, my] = h_down
+        p.topo.h = hp
+        r = p.field_extrema()
+        assert r['rho_max_cell'] == (ix, iy) and bits(r['rho_max']) == bits(rho_up), f"rho_max planted at {(ix, iy)}: {r['rho_max']!r} at {r['rho_max_cell']}"
+        assert r['p_max_cell'] == (ix, iy), f"p_max with rho_max planted at {(ix, iy)}: at {r['p_max_cell']}"
+        assert r['h_min_cell'] == (mx, my) and bits(r['h_min']) == bits(h_down), f"h_min planted at {(mx, my)}: {r['h_min']!r} at {r['h_min_cell']}"
+        assert r['rho_min_cell'] == ((1, 1) if (ix, iy) != (1, 1) else (1, 2) if ny > 1 else (2, 1)), 'the cells left flat tie: the first of them'
+    assert len(positions) >= nx * ny // PLANT_PARTS
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
