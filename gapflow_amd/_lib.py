@@ -49,6 +49,10 @@ ENSEMBLE_FORCE_WORKSPACE = 1        # gpf_ensemble_create2: flags
 ENSEMBLE_TIERS = ('lds', 'workspace')       # gpf_ensemble_member_info: tier
 EXTREMA_NAMES = ('p_max', 'p_min', 'rho_max', 'rho_min', 'h_min', 'u_max', 'v_max')     # gpf_extrema_*: the record's order
 ELASTIC_SERIES_NAMES = ('d_sum', 'd2_sum', 'p_d', 'h_sum', 'd_max', 'd_min')     # gpf_elastic_series_*: the record's order; cells: d_max's, d_min's
+# gpf_thinning_series_*: the record's order (eleven sums, three extrema); cells: eta_min's, eta_max's, rate_max's
+THINNING_SERIES_NAMES = ('load', 'tau_xz_bot', 'tau_yz_bot', 'tau_xz_top', 'tau_yz_top', 'tau0_xz_bot', 'tau0_yz_bot', 'tau0_xz_top', 'tau0_yz_top',
+                         'eta_sum', 'rate_sum', 'eta_min', 'eta_max', 'rate_max')
+THINNING_SERIES_EXTREMA = ('eta_min', 'eta_max', 'rate_max')
 # gpf_changes_*: the record's order; cells: dmax_rho's, dmax_jx's, dmax_jy's
 CHANGE_NAMES = ('d2_rho', 'd2_jx', 'd2_jy', 'q2_rho', 'q2_jx', 'q2_jy', 'dmass', 'dmax_rho', 'dmax_jx', 'dmax_jy', 'dt')
 CHANGE_MAXIMA = ('dmax_rho', 'dmax_jx', 'dmax_jy')
@@ -216,6 +220,11 @@ SIGNATURES = {
     'gpf_elastic_series_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'gpf_elastic_series_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32)]),
     'gpf_elastic_series_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
+    'gpf_thinning_series_set': (C.c_int, [C.c_void_p, C.c_int64]),
+    'gpf_thinning_series_clear': (C.c_int, [C.c_void_p]),
+    'gpf_thinning_series_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'gpf_thinning_series_now': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32)]),
+    'gpf_thinning_series_time': (C.c_int, [C.c_void_p, C.c_int64, C.c_int, _DP]),
     'gpf_changes_set': (C.c_int, [C.c_void_p, C.c_int64]),
     'gpf_changes_clear': (C.c_int, [C.c_void_p]),
     'gpf_changes_read': (C.c_int, [C.c_void_p, _DP, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -34,6 +34,7 @@
 #include "frame_kernels.hip"
 #include "resample_kernels.hip"
 #include "elastic_series_kernels.hip"
+#include "thinning_series_kernels.hip"
 #include "change_kernels.hip"
 #include "slab_series_kernels.hip"
 
@@ -172,6 +173,11 @@ struct gpf_handle {
     // gpf_elastic_update (the store's `pending`)
     struct : SeriesStore { double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
              bool narrow = false; } eldef;
+    // shear-thinning series (api_thinning_series.inc): the device records ([log_cap + 1][14] doubles, [log_cap + 1][6] int32) and
+    // the row scratch, allocated on first use (`narrow`: as above); on an elastic handle every record is written behind
+    // gpf_elastic_update (the store's `pending`)
+    struct : SeriesStore { double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
+             bool narrow = false; } thin;
     // step-change series (api_changes.inc): the device records ([log_cap + 1][11] doubles, [log_cap + 1][6] int32) and the row
     // scratch, allocated on first use (`narrow`: as above)
     struct : SeriesStore { double* rec = nullptr; int* cell = nullptr; double* part = nullptr; double* row_val = nullptr; int* row_iy = nullptr;
@@ -1136,6 +1142,7 @@ static int enqueue_small_steps(gpf_handle* h, int nsteps, int honor_stop, long l
 #include "api_weighted.inc"
 #include "api_extrema.inc"
 #include "api_elastic_series.inc"
+#include "api_thinning_series.inc"
 #include "api_changes.inc"
 #include "api_regions.inc"
 #include "api_lines.inc"

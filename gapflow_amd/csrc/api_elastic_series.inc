@@ -109,7 +109,7 @@ extern "C" int gpf_elastic_series_now(gpf_handle* h, double values[6], int32_t c
 }
 
 // Diagnostic (tools/elastic_series_time.py): n steps as a host takes them on an elastic handle -- the stage-wise calls and
-// gpf_elastic_update (series_time_elastic_steps) --, with `mode` 0 nothing (the armed series is put aside for the call), 1
+// gpf_elastic_update (series_time_stagewise_steps) --, with `mode` 0 nothing (the armed series is put aside for the call), 1
 // recording at the armed stride; *ms = first launch to last on the handle's stream, the host's share of such steps included
 // (series_time).
 extern "C" int gpf_elastic_series_time(gpf_handle* h, int64_t n, int mode, double* ms) {
@@ -121,7 +121,7 @@ extern "C" int gpf_elastic_series_time(gpf_handle* h, int64_t n, int mode, doubl
     std::vector<long long> steps;
     const int rc = series_time(h, "gpf_elastic_series_time", aside,
                                [&](long long) {
-                                   return series_time_elastic_steps(h, n, [&] {
+                                   return series_time_stagewise_steps(h, n, [&] {
                                        cells.insert(cells.end(), h->eldef.cells.begin(), h->eldef.cells.end());
                                        h->eldef.cells.clear();
                                        series_time_keep(h->eldef.host, h->eldef.steps, host, steps);

@@ -152,7 +152,7 @@ extern "C" int gpf_integrals_time(gpf_handle* h, int64_t n, int mode, double* ms
         std::vector<double> host;
         std::vector<long long> steps;
         const int rc = series_time(h, "gpf_integrals_time", aside,
-                                   [&](long long) { return series_time_elastic_steps(h, n, [&] { series_time_keep(h->integ.host, h->integ.steps, host, steps); }); },
+                                   [&](long long) { return series_time_stagewise_steps(h, n, [&] { series_time_keep(h->integ.host, h->integ.steps, host, steps); }); },
                                    [&](long long, long long) { h->integ.host.swap(host); h->integ.steps.swap(steps); return (int)GPF_OK; }, ms);
         prev_state_lost(h, PREV_LOST_STAGEWISE);    // (series_resync speaks of fused steps: a closed step leaves its working field in the other buffer)
         return rc;

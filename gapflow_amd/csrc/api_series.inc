@@ -1,5 +1,6 @@
 // Part of api.hip (included there, not compiled on its own): what the per-step recorders of a handle -- probes, film integrals,
-// weighted integrals, regions, lines, extrema, statistics, step changes, reduced frames, an elastic handle's deformation series
+// weighted integrals, regions, lines, extrema, statistics, step changes, reduced frames, an elastic handle's deformation series,
+// a thinning handle's series
 // (api_<name>.inc, included behind this file) -- have in common: the arithmetic of a stride's records, their way to the host and out of it, the
 // alignment test of the 16-byte loads, the arguments and the two launches of the row-reduced series (device side:
 // series_rows.hpp), the cases the film reductions refuse, the table of the series (SERIES) and every walk over it -- the records
@@ -171,15 +172,15 @@ static long long stats_next_record(gpf_handle* h, const Series& r, long long at)
     static int x##_begin(gpf_handle*); static int x##_launch(gpf_handle*, long long, long long);                                \
     static int x##_collect(gpf_handle*, long long, long long); static int x##_release(gpf_handle*); static SeriesBuffers x##_owned(gpf_handle*);
 SERIES_HOOKS(probes) SERIES_HOOKS(integrals) SERIES_HOOKS(weighted) SERIES_HOOKS(regions) SERIES_HOOKS(lines) SERIES_HOOKS(extrema)
-SERIES_HOOKS(stats) SERIES_HOOKS(changes) SERIES_HOOKS(frames) SERIES_HOOKS(eldef)
+SERIES_HOOKS(stats) SERIES_HOOKS(changes) SERIES_HOOKS(frames) SERIES_HOOKS(eldef) SERIES_HOOKS(thin)
 #undef SERIES_HOOKS
 // The first columns of a row whose struct in gpf_handle derives from SeriesStore; the hooks' columns
 #define SERIES_STORE(field) [](gpf_handle* h) { return &h->field.every; }, [](gpf_handle* h) { h->field.forget(); }, [](gpf_handle* h) -> SeriesStore* { return &h->field; }
 #define SERIES_HOOKS(x) x##_begin, x##_launch, x##_collect, x##_release, x##_owned
 
 // In gpf_step's order -- of the refusals a caller sees first, and of the recording launches on the stream --, the deformation
-// series, which gpf_step does not record, behind them
-enum { S_PROBES, S_INTEGRALS, S_WEIGHTED, S_REGIONS, S_LINES, S_EXTREMA, S_STATS, S_CHANGES, S_FRAMES, S_ELDEF };
+// series and the thinning series, which gpf_step does not record, behind them
+enum { S_PROBES, S_INTEGRALS, S_WEIGHTED, S_REGIONS, S_LINES, S_EXTREMA, S_STATS, S_CHANGES, S_FRAMES, S_ELDEF, S_THIN };
 static const Series SERIES[] = {
     {"probes", [](gpf_handle* h) { return &h->probes.n; }, [](gpf_handle* h) { h->probes.host.clear(); h->probes.first_step = h->host_step + 1; }, nullptr,
      SERIES_HOOKS(probes), true, nullptr, SERIES_AT_CLOSE},
@@ -193,12 +194,13 @@ static const Series SERIES[] = {
     {"changes", SERIES_STORE(chg), SERIES_HOOKS(changes), true, series_next_record, SERIES_NOT_STAGEWISE},
     {"frames", SERIES_STORE(frames), SERIES_HOOKS(frames), true, series_next_record, SERIES_NOT_STAGEWISE},
     {"elastic_series", SERIES_STORE(eldef), SERIES_HOOKS(eldef), false, nullptr, SERIES_BEHIND_UPDATE},
+    {"thinning_series", SERIES_STORE(thin), SERIES_HOOKS(thin), false, nullptr, SERIES_AT_CLOSE_UNLESS_ELASTIC},
 };
 #undef SERIES_STORE
 #undef SERIES_HOOKS
 // gpf_close_step's order, and gpf_elastic_update's: extrema before film integrals, where gpf_step has them the other way round
 // (kept apart: the order decides which of two refusals a caller sees)
-static const int SERIES_STAGEWISE[] = {S_PROBES, S_EXTREMA, S_INTEGRALS, S_ELDEF, S_STATS};
+static const int SERIES_STAGEWISE[] = {S_PROBES, S_EXTREMA, S_INTEGRALS, S_ELDEF, S_STATS, S_THIN};
 
 // The records every series holds on the host for _read go: a stepping call in which a series records nothing leaves none
 static void series_forget_records(gpf_handle* h) {
@@ -417,11 +419,11 @@ template <class Behind> static int series_time_steps(gpf_handle* h, int64_t n, l
     return GPF_OK;
 }
 
-// n steps of an elastic handle as a host takes them: the stage-wise calls, then gpf_elastic_update, behind whose launches the
-// film integrals and the deformation series write the closed step's record (every call synchronises, so *ms of series_time is
-// the host's time too).  Every gpf_close_step begins its series' records afresh: `keep()` behind each update moves what the step
-// left to where the call's collect finds it.  Stops at a step that did not commit.
-template <class Keep> static int series_time_elastic_steps(gpf_handle* h, int64_t n, Keep&& keep) {
+// n steps of a handle that steps stage-wise as a host takes them: the stage-wise calls, then, on an elastic handle,
+// gpf_elastic_update, behind whose launches the film integrals and the deformation series write the closed step's record (every
+// call synchronises, so *ms of series_time is the host's time too).  Every gpf_close_step begins its series' records afresh:
+// `keep()` behind each step moves what it left to where the call's collect finds it.  Stops at a step that did not commit.
+template <class Keep> static int series_time_stagewise_steps(gpf_handle* h, int64_t n, Keep&& keep) {
     for (int64_t i = 0; i < n; ++i) {
         GPF_TRY(gpf_open_step(h));
         for (int stage = 0; stage < 2; ++stage) {
@@ -431,7 +433,7 @@ template <class Keep> static int series_time_elastic_steps(gpf_handle* h, int64_
         gpf_scalars_t sc;
         GPF_TRY(gpf_close_step(h, &sc));
         if (sc.invalid) break;
-        GPF_TRY(gpf_elastic_update(h));
+        if (h->el.on) GPF_TRY(gpf_elastic_update(h));
         keep();
     }
     return GPF_OK;

@@ -80,6 +80,63 @@ __device__ __forceinline__ void row_pairs(const Args& f, const double* wp, int i
     }
 }
 
+// The densities around a cell whose own is CellIn::rho: rows ix - 1, ix + 1 at its column, columns iy - 1, iy + 1 of its row
+struct RhoCross {
+    double xm, xp, ym, yp;
+};
+
+// row_pairs' companion for a series whose cell needs the 5-point stencil of the density (thinning_series_kernels.hip: grad p):
+// the same pairs in the same order from the same loads of the row's own planes, and cell(c, s, iy) with s the four
+// neighbours' densities, ghost cells among them.  Of rows ix - 1 and ix + 1 (the ghost rows 0 and Nx + 1 for the first and the
+// last interior row) the pair's two columns are fetched as the own row's are -- the pitch is even where `wide` holds, so they
+// are aligned alike --; the pair's neighbours inside the row are the column iy - 1 before it (the ghost 0 for the first pair) and
+// the column iy + 2 behind it.  Two rules for an odd Ny: the upper column of the last pair is the row's ghost Ny + 1, which is
+// the lower cell's neighbour and is never handed on as a cell; and iy + 2 = Ny + 2 then lies outside the row and is not read.
+// No weight plane.  `f`: as row_pairs'.
+template <class Planes, class Args, class Cell>
+__device__ __forceinline__ void row_pairs_cross(const Args& f, int ix, Cell cell) {
+    const Layout& L = f.L;
+    const double* q = f.st->parity ? f.qb : f.qa;
+    const int npair = (L.Ny + 1) / 2;
+    for (int k = threadIdx.x; k < npair; k += 256) {
+        const int iy = 1 + 2 * k;
+        const bool two = iy + 1 <= L.Ny;
+        const long long o = L.at(ix, iy), om = o - L.pitch, op = o + L.pitch;
+        series_d2 in[7], rm, rp;
+        in[6] = series_d2{0.0, 0.0};
+        if (f.wide) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) in[p] = *reinterpret_cast<const series_d2*>(q + p * L.plane + o);
+#pragma unroll
+            for (int p = 0; p < 3; ++p) in[3 + p] = *reinterpret_cast<const series_d2*>(f.topo + p * L.plane + o);
+            if (Planes::has_ls) in[6] = *reinterpret_cast<const series_d2*>(f.Ls + o);
+            rm = *reinterpret_cast<const series_d2*>(q + om);
+            rp = *reinterpret_cast<const series_d2*>(q + op);
+        } else {
+            const long long o1 = two ? o + 1 : o;
+            in[0] = series_d2{q[o], q[o + 1]};              // (the ghost Ny + 1 of an odd Ny: the lower cell's neighbour)
+#pragma unroll
+            for (int p = 1; p < 3; ++p) in[p] = series_d2{q[p * L.plane + o], q[p * L.plane + o1]};
+#pragma unroll
+            for (int p = 0; p < 3; ++p) in[3 + p] = series_d2{f.topo[p * L.plane + o], f.topo[p * L.plane + o1]};
+            if (Planes::has_ls) in[6] = series_d2{f.Ls[o], f.Ls[o1]};
+            rm = series_d2{q[om], q[om + (o1 - o)]};
+            rp = series_d2{q[op], q[op + (o1 - o)]};
+        }
+        const double before = q[o - 1];
+        CellIn c;
+        RhoCross s;
+        c.rho = in[0].x; c.jx = in[1].x; c.jy = in[2].x; c.h = in[3].x; c.hx = in[4].x; c.hy = in[5].x; c.Ls = in[6].x;
+        s.xm = rm.x; s.xp = rp.x; s.ym = before; s.yp = in[0].y;
+        cell(c, s, iy);
+        if (two) {
+            c.rho = in[0].y; c.jx = in[1].y; c.jy = in[2].y; c.h = in[3].y; c.hx = in[4].y; c.hy = in[5].y; c.Ls = in[6].y;
+            s.xm = rm.y; s.xp = rp.y; s.ym = in[0].x; s.yp = q[o + 2];
+            cell(c, s, iy + 1);
+        }
+    }
+}
+
 // A thread's (a row's, a record's) N sums
 template <int N> struct RowAcc {
     double v[N];

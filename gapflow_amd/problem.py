@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from . import __version__
 from .io import read_yaml_input, write_yaml, create_output_directory, history_to_csv
-from .series import (ALL_SERIES, SERIES, _Series, _changes_stride, _domain_series_entry, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
+from .series import (ALL_SERIES, SERIES, SERIES_STAGEWISE, _Series, _thinning_series_stride, _changes_stride, _domain_series_entry, _elastic_series_stride, _extrema_stride, _integral_records, _integral_sections,  # noqa: F401
                      _integral_stride, _line_centre, _line_entries, _line_span, _lines_stride, _probe_cells, _region_entries,
                      _regions_stride, _statistics_fields, _statistics_stride, _stride, _weight_planes, _weighted_stride,
                      _frame_axes, _frame_shape, _frame_spec, _frame_window, _frames_stride)
@@ -45,6 +45,8 @@ FieldExtrema = namedtuple('FieldExtrema', ('step', 'time') + _lib.EXTREMA_NAMES 
 FieldExtrema.__doc__ = """Time series of Problem.extrema: step, time and the seven values (nrecords,), cells (nrecords, 7, 2) -- (ix, iy) of each value in the ghosted index space --, index: name -> position along the cells' second axis."""
 ElasticSeries = namedtuple('ElasticSeries', ('step', 'time') + _lib.ELASTIC_SERIES_NAMES + ('cells',))
 ElasticSeries.__doc__ = """Time series of Problem.elastic_series: step, time, the four sums and d_max, d_min (nrecords,), cells (nrecords, 2, 2) -- (ix, iy) of d_max, then of d_min, in the ghosted index space."""
+ThinningSeries = namedtuple('ThinningSeries', ('step', 'time') + _lib.THINNING_SERIES_NAMES + ('cells',))
+ThinningSeries.__doc__ = """Time series of Problem.thinning_series: step, time, the eleven sums and eta_min, eta_max, rate_max (nrecords,), cells (nrecords, 3, 2) -- (ix, iy) of eta_min, then of eta_max, then of rate_max, in the ghosted index space."""
 StepChanges = namedtuple('StepChanges', ('step', 'time') + _lib.CHANGE_NAMES + ('cells', 'index'))
 StepChanges.__doc__ = """Time series of Problem.changes: step, time and the eleven values (nrecords,), cells (nrecords, 3, 2) -- (ix, iy) of dmax_rho, dmax_jx, dmax_jy in the ghosted index space --, index: name of a maximum -> position along the cells' second axis."""
 
@@ -192,6 +194,9 @@ class Problem:
         self._elastic_series_every = None
         if options.get('elastic_series'):           # options.elastic_series (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
             self.set_elastic_series(options['elastic_series'])
+        self._thinning_series_every = None
+        if options.get('thinning_series'):          # options.thinning_series (from the YAML text, or carried by a checkpoint's dictionaries); 0: off
+            self.set_thinning_series(options['thinning_series'])
         self._frames_every, self._frames_nc = None, None
         if options.get('frames'):                   # options.frames / options.frame_spec (from the YAML text, or a checkpoint's dictionaries); 0: off
             self.set_frames(options['frames'], **(options.get('frame_spec') or {}))
@@ -537,7 +542,7 @@ class Problem:
 
         Allowed at any time.  Before the first step the run simply begins from the new state; after steps the run starts
         over at step 0 (`_pre_run`), as it would from a state assigned to ``q``, and the probes', integrals', weighted
-        integrals', regions', lines' and extrema series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
+        integrals', regions', lines', extrema and thinning series start afresh.  `source` is only read.  A path is loaded into a temporary problem on this problem's device,
         which is destroyed before the call returns.
         ValueError: the domains differ (Lx or Ly by more than 1e-12 relative), or a direction is periodic on one side only.
         NotImplementedError: surrogate closures here, or a SlabProblem as the source."""
@@ -1306,6 +1311,83 @@ class Problem:
         np.savez(os.path.join(self.outdir, 'elastic_series.npz'), **self.elastic_series._asdict())
 
     # -------------------------------------------------------------------------------------
+    # shear-thinning series (no reference counterpart)
+    # -------------------------------------------------------------------------------------
+    def _thinning_series_refusal(self):
+        if not self._cfg.thinning:
+            raise NotImplementedError("thinning series: this problem has no shear thinning (properties.thinning: Eyring or Carreau)")
+        if self._gp_models:
+            raise NotImplementedError("thinning series: the record evaluates the analytic pressure and wall stress; this problem's closures are surrogates")
+
+    def set_thinning_series(self, every=1):
+        """Record what a shear-thinning film carries and what it costs its walls after every step whose count is a multiple of
+        `every`, on the device, behind the step (a thinning problem steps stage-wise, `update()` and `run()` alike).
+
+        Per record, over the interior cells 1..Nx x 1..Ny of the committed state, with grad p the central differences of the
+        equation of state's pressure over the four neighbours (ghost cells included), mu0 the Newtonian viscosity
+        (piezo-viscosity included), rate = models.viscosity.shear_rate_avg(grad p, h, U, V, mu0) and eta = mu0
+        shear_thinning_factor(rate, mu0) -- cell by cell what ``wall_stress_xz`` / ``wall_stress_yz`` are made of once the
+        closures are refreshed for that state: `load` (the pressure ``integrals`` sums as `load`), tau_xz_bot, tau_yz_bot,
+        tau_xz_top, tau_yz_top (the wall shear stresses with eta), tau0_* (the same with mu0: what the film would cost without
+        thinning), eta_sum and rate_sum (mean viscosity: eta_sum / area), each summed in the order ``integrals`` adds and
+        multiplied by dx dy once; and eta_min, eta_max, rate_max with their cells (ix, iy) of the ghosted index space, ties
+        going to the smallest ix, then the smallest iy, as in ``extrema``.  The same state and gap give the same bits whatever
+        the stride.  With an elastic gap too the record is taken behind the deformation that follows the step, of the
+        deformed gap.  A step that is rolled back as invalid leaves no record.  Starts a new series (see ``thinning_series``).
+        Checkpoints do not carry the series: a problem restored from one whose options hold `thinning_series` has it armed
+        again and its series begins at the restart step.  May be armed beside probes, extrema and statistics.  Not available
+        without shear thinning, nor with surrogate closures."""
+        self._thinning_series_refusal()
+        every = _thinning_series_stride(every, allow_zero=False)
+        _lib.check(self._lib.gpf_thinning_series_set(self._h, every))
+        self._thinning_series_every, self._thinning_series_rec = every, _Series('thinning series', every)
+
+    def clear_thinning_series(self):
+        """Stop recording and drop the series."""
+        if self._thinning_series_every is not None:
+            _lib.check(self._lib.gpf_thinning_series_clear(self._h))
+        self._thinning_series_every = None
+
+    @property
+    def thinning_series(self):
+        """ThinningSeries(step, time, load, tau_*, tau0_*, eta_sum, rate_sum, eta_min, eta_max, rate_max, cells) of every
+        recorded step since set_thinning_series (or _pre_run), across `update()` and `run()` calls; None when the series is not
+        armed.  cells[n, 0] is the (ix, iy) of eta_min, cells[n, 1] that of eta_max, cells[n, 2] that of rate_max."""
+        if self._thinning_series_every is None:
+            return None
+        rec, nq = self._thinning_series_rec, len(_lib.THINNING_SERIES_NAMES)
+        vals = rec.stacked(0, (nq,))
+        return ThinningSeries(rec.step_array(), rec.time_array(), *[vals[:, k] for k in range(nq)],
+                              rec.stacked(1, (len(_lib.THINNING_SERIES_EXTREMA), 2), np.int32))
+
+    def film_thinning(self):
+        """The same record for the current state and gap, as a dict: the fourteen names of ``thinning_series`` and
+        `eta_min_cell`, `eta_max_cell`, `rate_max_cell` = (ix, iy).  Bit for bit what a step leaving them would have recorded.
+        Armed or not.  Reads only."""
+        self._thinning_series_refusal()
+        self._sync_to_device()
+        vals = np.empty(len(_lib.THINNING_SERIES_NAMES))
+        cells = np.zeros((len(_lib.THINNING_SERIES_EXTREMA), 2), dtype=np.int32)
+        _lib.check(self._lib.gpf_thinning_series_now(self._h, _lib.as_dp(vals), cells.ctypes.data_as(C.POINTER(C.c_int32))))
+        res = {name: np.float64(vals[k]) for k, name in enumerate(_lib.THINNING_SERIES_NAMES)}
+        for k, name in enumerate(_lib.THINNING_SERIES_EXTREMA):
+            res[name + '_cell'] = (int(cells[k, 0]), int(cells[k, 1]))
+        return res
+
+    def _collect_thinning_series(self, entries, before):
+        """The records of the step that took the step count from `before` through `entries` (its committed step)."""
+        if self._thinning_series_every is None:
+            return
+
+        def read(b, n, steps, have):
+            _lib.check(self._lib.gpf_thinning_series_read(self._h, _lib.as_dp(b[0]), b[1].ctypes.data_as(C.POINTER(C.c_int32)), n, steps, have))
+        self._thinning_series_rec.collect(read, entries, before, [((len(_lib.THINNING_SERIES_NAMES),), np.float64),
+                                                                  ((len(_lib.THINNING_SERIES_EXTREMA), 2), np.int32)])
+
+    def _write_thinning_series(self):
+        np.savez(os.path.join(self.outdir, 'thinning_series.npz'), **self.thinning_series._asdict())
+
+    # -------------------------------------------------------------------------------------
     # step changes (no reference counterpart; DESIGN.md 3.3p)
     # -------------------------------------------------------------------------------------
     def _changes_refusal(self):
@@ -1466,7 +1548,7 @@ class Problem:
         self.dt = sc.dt
         self.tol = self.numerics['tol']
         self.max_it = self.numerics['max_it']
-        for row in ALL_SERIES:                      # the step count starts over: so does every armed series
+        for row in ALL_SERIES + SERIES_STAGEWISE:   # the step count starts over: so does every armed series
             if row.recorder is not None and getattr(self, row.marker) is not None:
                 getattr(self, row.recorder).reset()
 
@@ -1557,6 +1639,7 @@ class Problem:
         self._absorb([sc])
         self._collect_probes([sc])
         self._collect_extrema([sc], before)     # (an elastic gap's record was taken behind gpf_elastic_update, of the deformed gap)
+        self._collect_thinning_series([sc], before)     # (likewise)
         if self._elastic:                       # likewise its film integrals and its deformation series
             self._collect_integrals([sc], before)
             self._collect_elastic_series([sc], before)
@@ -1650,7 +1733,7 @@ class Problem:
         print(33 * '=')
         if not silent:
             history_to_csv(os.path.join(self.outdir, 'history.csv'), self.history)
-            for row in ALL_SERIES:                  # (the statistics last of SERIES, the later series behind them)
+            for row in ALL_SERIES + SERIES_STAGEWISE:       # (the statistics last of SERIES, the later series behind them)
                 if getattr(self, row.marker) is not None:
                     getattr(self, row.write)()
             for name, m in self._gp_models.items():  # problem.py:490-503
@@ -1784,6 +1867,12 @@ def _own_elastic_series(input_dict, opts, base_dir):
         input_dict['options']['elastic_series'] = _elastic_series_stride(opts['elastic_series'])
 
 
+def _own_thinning_series(input_dict, opts, base_dir):
+    """`options.thinning_series: N` (the stride; 0 or absent: off)."""
+    if opts.get('thinning_series') is not None:
+        input_dict['options']['thinning_series'] = _thinning_series_stride(opts['thinning_series'])
+
+
 def _own_weighted(input_dict, opts, base_dir):
     """`options.weighted_integrals: N` (the stride; 0 or absent: off) and `options.weights: [{box: ...}, {mode: ...}, {file: ...}]`
     (gapflow_amd/weights.py: parse_entries); a `file` becomes an absolute path, relative ones taken from the YAML file's directory."""
@@ -1857,7 +1946,7 @@ def _own_init_from(input_dict, opts, base_dir):
 
 
 _OWN_KEYS = (_own_checkpoint_freq, _own_probes, _own_integrals, _own_extrema, _own_elastic_series, _own_weighted, _own_statistics,
-             _own_regions, _own_lines, _own_frames, _own_changes, _own_domain_series, _own_init_from)
+             _own_regions, _own_lines, _own_frames, _own_changes, _own_domain_series, _own_thinning_series, _own_init_from)
 
 
 def _keep(keys, input_dict, ymlstring, base_dir=None):
@@ -1888,6 +1977,7 @@ def _keep_regions(input_dict, ymlstring): _keep([_own_regions], input_dict, ymls
 def _keep_lines(input_dict, ymlstring): _keep([_own_lines], input_dict, ymlstring)
 def _keep_frames(input_dict, ymlstring): _keep([_own_frames], input_dict, ymlstring)
 def _keep_changes(input_dict, ymlstring): _keep([_own_changes], input_dict, ymlstring)
+def _keep_thinning_series(input_dict, ymlstring): _keep([_own_thinning_series], input_dict, ymlstring)
 def _keep_domain_series(input_dict, ymlstring): _keep([_own_domain_series], input_dict, ymlstring)
 def _keep_init_from(input_dict, ymlstring, base_dir=None): _keep([_own_init_from], input_dict, ymlstring, base_dir)
 

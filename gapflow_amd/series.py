@@ -101,6 +101,13 @@ SERIES_MORE = (
     _Row('_changes_every', '_changes_rec', '_collect_changes', '_write_changes', 'changes', 'clear_changes', (7, CUTS), True),
 )
 ALL_SERIES = SERIES + SERIES_MORE
+# The series that exist on the stage-wise path alone and were added since (the elastic series is the one in SERIES): never
+# collected by a fused batch, never an Ensemble's concern (it refuses such a problem before it looks at its series).  Problem's
+# _pre_run and _post_run walk them behind ALL_SERIES.
+SERIES_STAGEWISE = (
+    _Row('_thinning_series_every', '_thinning_series_rec', '_collect_thinning_series', '_write_thinning_series', 'thinning series',
+         'clear_thinning_series', None, False),
+)
 
 
 def _stride(label, value, low, what='the stride'):
@@ -116,6 +123,7 @@ def _regions_stride(every, allow_zero=False): return _stride('regions', every, 0
 def _lines_stride(every, allow_zero=False): return _stride('lines', every, 0 if allow_zero else 1)
 def _extrema_stride(every, allow_zero=True): return _stride('extrema', every, 0 if allow_zero else 1)
 def _elastic_series_stride(every, allow_zero=True): return _stride('elastic series', every, 0 if allow_zero else 1)
+def _thinning_series_stride(every, allow_zero=True): return _stride('thinning series', every, 0 if allow_zero else 1)
 def _changes_stride(every, allow_zero=True): return _stride('changes', every, 0 if allow_zero else 1)
 def _frames_stride(every, allow_zero=False): return _stride('frames', every, 0 if allow_zero else 1)
 def _statistics_stride(v, key, low): return _stride('statistics', v, low, key)

@@ -606,6 +606,14 @@ class SlabProblem:
         """The deformation series is taken on unsliced problems only."""
         raise NotImplementedError("elastic series: not available on a SlabProblem")
 
+    def set_thinning_series(self, *args, **kwargs):
+        """The thinning series is recorded on unsliced problems only (options.thinning_series is kept and never armed here)."""
+        raise NotImplementedError("thinning series: not available on a SlabProblem")
+
+    def film_thinning(self, *args, **kwargs):
+        """The thinning series is taken on unsliced problems only."""
+        raise NotImplementedError("thinning series: not available on a SlabProblem")
+
     def set_changes(self, *args, **kwargs):
         """Step changes are recorded on unsliced problems only."""
         raise NotImplementedError("changes: not available on a SlabProblem")
@@ -1114,6 +1122,7 @@ class SlabProblem:
             from .problem import Problem
             d = deepcopy(self.input)
             d['options'].pop('frames', None)        # stored, never armed: the writer steps nothing, and frames are not recorded on slabs
+            d['options'].pop('thinning_series', None)       # likewise the thinning series
             # with surrogates the writer shares this rank's database and mirrors its models (same data, same
             # hyper-parameters), so the closures of a frame are the surrogates' means as in a serial run
             self._writer_problem = Problem(d['options'], d['grid'], d['numerics'], d['properties'], d['geometry'],

@@ -695,6 +695,56 @@ int gpf_elastic_series_now(gpf_handle* h, double values[6], int32_t cells[4]);
  * (before the point probes). */
 int gpf_elastic_series_time(gpf_handle* h, int64_t n, int mode, double* ms);
 
+/* ---- shear-thinning series (no reference counterpart: its users download the stress planes after every step) --------------- */
+/* What a shear-thinning film (gpf_config.thinning: Eyring, Carreau) carries and what it costs its walls, reduced on the device.
+ * The other film reductions refuse such a handle ("shear thinning needs grad p"); this one evaluates grad p.  Per interior cell
+ * (ix, iy) of the COMMITTED state, exactly as gpf_update_closures evaluates an interior cell of a thinning handle: p = the
+ * equation of state's pressure of the density at the cell and its four neighbours (ghost cells are neighbours), dpx = (p[ix+1,iy]
+ * - p[ix-1,iy]) / (2 dx), dpy = (p[ix,iy+1] - p[ix,iy-1]) / (2 dy), mu0 the Newtonian viscosity (piezo-viscosity included), rate
+ * the mean wall shear rate of the Newtonian profile (models/viscosity.py shear_rate_avg of dpx, dpy, h, U, V, mu0), eta = mu0
+ * times the thinning factor of rate.  A record is fourteen doubles and three cells, over the interior cells 1..Nx x 1..Ny:
+ *   0 load                      sum of the pressure the film integrals' `load` sums, times dx dy (tau / load: a friction coefficient)
+ *   1 tau_xz_bot, 2 tau_yz_bot, 3 tau_xz_top, 4 tau_yz_top        the wall shear stresses with eta, summed, times dx dy: what
+ *                               GPF_FIELD wall-stress planes hold for the committed state (gpf_update_closures), bit for bit
+ *   5 tau0_xz_bot .. 8 tau0_yz_top    the same with mu0: what the film would cost without thinning; bit for bit the film
+ *                               integrals' tau_* of a handle without thinning that holds the same state
+ *   9 eta_sum, 10 rate_sum      sums of eta and of rate, times dx dy (means: divided by the area)
+ *   11 eta_min, 12 eta_max, 13 rate_max    each with its cell (ix, iy) of the ghosted index space
+ * Host layout: values [record][14] doubles, cells [record][3][2] int32 (eta_min's ix, iy, then eta_max's, then rate_max's).  The
+ * sums are added in the film integrals' order (k_film_partial's pair walk, its fold tree, k_film_fold's row loop), eta and rate
+ * rounded on their own, and multiplied by dx dy once; the extrema are ordered by the field extrema's one comparison (value, then
+ * the smaller ix, then the smaller iy; a NaN never wins).  A record is a pure function of (q, gap, slip length): no
+ * floating-point atomics, the same bits whatever the stride, behind a step or from gpf_thinning_series_now.  Recording only reads.
+ * WHEN: a thinning handle steps stage-wise; the record of a closed step is written behind gpf_close_step's launches, at the armed
+ * stride, if the step commits.  Where the gap is elastic too it deforms after the step closes: the record is pending at
+ * gpf_close_step and written behind the gpf_elastic_update that follows, with the gap the handle then holds (the extrema's rule).
+ *   gpf_thinning_series_set    arms recording after every committed step whose new step count is a multiple of `every` (>= 1,
+ *                              else GPF_ERR_INVALID) and starts with empty records.  GPF_ERR_STATE on a handle without shear
+ *                              thinning ("no shear thinning"), on a slab and while a stage-wise step is open; GPF_ERR_INVALID
+ *                              with any surrogate closure (the analytic pressure or wall stress is replaced).
+ *   gpf_thinning_series_clear  disarms and frees the buffers.
+ *   gpf_thinning_series_read   the records of the LAST gpf_close_step (and its gpf_elastic_update) and the step count of each in
+ *                              steps_out (values, cells, steps_out may be NULL); *n_records how many the call left,
+ *                              min(*n_records, capacity_records) are copied.  GPF_ERR_STATE unless armed.
+ *   gpf_thinning_series_now    the same record for the state and gap the handle holds, armed or not; GPF_ERR_STATE on an invalid
+ *                              run state.
+ * Where they are written: k_thin_partial (one workgroup per interior row; 6 planes read, 7 with a slip-length field, and the
+ * density of the two neighbouring rows; six equations of state per cell) + k_thin_fold (csrc/thinning_series_kernels.hip),
+ * guarded by the device's run state like every recording kernel.  Buffers ((log_cap + 1) records and a row scratch) are
+ * allocated on first use and freed by gpf_thinning_series_clear / gpf_destroy once the stream is idle.  Pairs of columns are
+ * fetched with one 16-byte load per plane where the planes are aligned for it and with 8-byte loads otherwise; GPF_FILM_NARROW
+ * (read when the buffers are allocated) asks for the 8-byte loads regardless -- a test switch; the records are the same in every
+ * bit.  With nothing armed no launch and no HIP call is added to a step. */
+int gpf_thinning_series_set(gpf_handle* h, int64_t every);
+int gpf_thinning_series_clear(gpf_handle* h);
+int gpf_thinning_series_read(gpf_handle* h, double* values, int32_t* cells, int64_t capacity_records, int64_t* steps_out, int64_t* n_records);
+int gpf_thinning_series_now(gpf_handle* h, double values[14], int32_t cells[6]);
+/* Diagnostic: n steps (1..4096) as a host takes them on a thinning handle -- gpf_open_step, two stages, gpf_close_step per step,
+ * gpf_elastic_update where the gap is elastic --, *ms from the first launch to the last on the handle's stream (every such call
+ * synchronises: the host's share is part of it), with mode 0 no recording, 1 recording at the armed stride
+ * (tools/thinning_series_time.py). */
+int gpf_thinning_series_time(gpf_handle* h, int64_t n, int mode, double* ms);
+
 /* ---- step changes (no reference counterpart: its users download q after every step and subtract on the host) --------------- */
 /* How far the committed step n moved each conserved field, reduced on the device.  With d = q^n - q^(n-1) per field (rho, jx,
  * jy) over the interior cells 1..Nx x 1..Ny, a record is eleven doubles and three cells:
